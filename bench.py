@@ -1,13 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on its quoted configuration, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, K timed steps, the held-out PSNR, one JSON line
+(metric, value, unit, ms_per_step, ...).  `--dump-outputs DIR` also writes what the timed path computes (dump_outputs(), run_leg()): under
+DIR/after_timed_steps/ what the LAST timed launch left its caller -- the model as the K steps trained it, the image and radii of the last
+iteration, its losses, the loss sum -- which float-atomic ordering and Adam make differ between runs by 1e-2 of an array's maximum after 27 steps;
+and as DIR/<name>.npy the same launch once more from the seeded start (losses of its chained iterations; image, radii and updated
+parameters after the first of them), which two runs and two builds reproduce to float32 rounding.  `--full` adds every other measurement described
+below: the four repeated regions, per-stage timings and the roofline, the fine_all-shaped leg, SH degree 3, the unchanged-trainer
+and eager legs, configs B / D, the trained scene, the CPU baseline.
 N > 1 launched plainly re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 ...`; launched by torchrun / the driver it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 
 Workload (config C of BASELINE.md): synthetic scene S(500k Gaussians, 540, 960, seed 0), the 300-frame synthetic orbit, SH
-degree 0 (`--sh-degree 3` for the 16-coefficient colour model the reference ends training with; the default single-GPU
-run measures that too, in a child process, and reports it as `sh_degree_3`).
+degree 0 (`--sh-degree 3` for the 16-coefficient colour model the reference ends training with; the single-GPU
+`--full` run measures that too, in a child process, and reports it as `sh_degree_3`).
 One step = one full training iteration of /root/reference/trainers/train_static.py:67-138 without densification or
 logging: covariance (the reference forces compute_cov3D_python, /root/reference/train.py:49; here built inside the
 rasterizer's preprocess kernel from the raw parameters) -> render() forward (HIP) -> 0.8 L1 + 0.2 (1 - SSIM) ->
@@ -15,12 +23,12 @@ backward (HIP + autograd) -> Adam; replayed from one hipGraph per step (`--no-gr
 Frames are sharded round-robin over ranks (1 frame per GPU per step); ranks exchange only
 scalars (loss / PSNR sums) through one RCCL all-reduce; `value` = steps of all ranks / max-over-ranks time.
 
-Second leg, `fine_all_shape` in the same JSON line (BASELINE.json config 4, /root/reference/trainers/fine_all.py:74-101): 30 % of
+Second leg (`--full`), `fine_all_shape` in the same JSON line (BASELINE.json config 4, the reference's trainers/fine_all.py:74-101): 30 % of
 the Gaussians are the object; every frame carries its own accumulated object rotation and a hand mask; the step is
 render(..., rot_cov=True, accum_R=R_k, which_object=1) -> hand-mask-gated loss -> backward -> Adam, replayed from its own
 hipGraph.  Same sharding, same timing rules.  `--dynamic` makes that leg the headline instead (the static one is then skipped).
 
-The JSON line also carries
+With `--full` the JSON line also carries
   roofline      the dominant rasterizer stage: algorithmic bytes per launch / its mean duration, measured with HIP
                 events recorded by the library on the launch stream inside the timed region; pixel-splat pair throughput;
                 HBM traffic and VALU counters from profiles/*.json when those were collected on THESE kernel sources;
@@ -462,17 +470,47 @@ def hand_gate(k, H, W, device):
     return g
 
 
+DUMP_BUDGET_BYTES = 60 << 20          # --dump-outputs writes at most this much (the limit is 64 MB)
+
+
+def dump_outputs(directory, arrays):
+    """{name: tensor or array, first axis = items} -> directory/<name>.npy, float32 (float64 stays float64).  Everything is written as it
+    is while the total fits DUMP_BUDGET_BYTES; otherwise every array of 64 items or more keeps the same fraction of them, chosen by a generator seeded
+    with 0 from the item count alone (arrays of equal length keep the same items, every run keeps the same ones), in ascending order."""
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32).reshape(a.shape[0] if a.ndim else 1, -1)
+    short = sum(a.nbytes for a in host.values() if a.shape[0] < 64)
+    keep = min(1.0, (DUMP_BUDGET_BYTES - short) / max(sum(a.nbytes for a in host.values()) - short, 1))
+    for name, a in host.items():
+        if keep < 1.0 and a.shape[0] >= 64:                          # (a short array -- the losses -- is kept whole)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+        os.makedirs(os.path.dirname(os.path.join(directory, name)), exist_ok=True)      # (a name may carry a sub-directory)
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     t_process = time.perf_counter()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: four more timed regions (value_median / value_spread), per-stage timings, "
+                         "roofline, the fine_all-shaped leg, SH degree 3, the unchanged-trainer and eager legs, configs B / D, the trained scene, "
+                         "the CPU baseline (the --no-* options below drop single ones of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed, float32 .npy: DIR/after_timed_steps/ = what the last timed launch left (trained parameters, "
+                         "image, radii, losses, loss sum; differs between runs by up to 1e-2 of an array's maximum: float-atomic ordering amplified by "
+                         "Adam); DIR/ = the same launch once more from the seeded start (reproducible to float32 rounding)")
     ap.add_argument("--gaussians", type=int, default=500_000)
     ap.add_argument("--height", type=int, default=540)
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--sh-degree", type=int, default=0, help="spherical-harmonics degree of the colours (0..3; the reference ends training at 3)")
-    ap.add_argument("--no-sh3-leg", action="store_true", help="skip the extra SH-degree-3 measurement of the default single-GPU run")
+    ap.add_argument("--no-sh3-leg", action="store_true", help="skip the extra SH-degree-3 measurement of the single-GPU --full run")
     ap.add_argument("--no-fine-all-leg", action="store_true", help="skip the fine_all-shaped (dynamic object) leg")
     ap.add_argument("--dynamic", action="store_true", help="headline = the fine_all call shape (rot_cov + accum_R + hand-mask gate) instead of the static step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -498,12 +536,12 @@ def main():
     ap.add_argument("--no-force-dist", action="store_true",
                     help="N = 1 only: do not create the one-rank RCCL group (by default the single-GPU run initialises RCCL with device_id, and its "
                          "barriers and scalar all-reduces are real collectives -- the same code path as N > 1)")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the config B (100k forward-only) and config D (1M @ 1080p op-only) legs of the default run")
-    ap.add_argument("--footprints", action="store_true", help="also measure the heavier-footprint legs (scale x3 scene; densified model): profiles/r3_footprint_sweep.md")
+    ap.add_argument("--no-config-legs", action="store_true", help="skip the config B (100k forward-only) and config D (1M @ 1080p op-only) legs of the --full run")
+    ap.add_argument("--footprints", action="store_true", help="with --full: also measure the heavier-footprint legs (scale x3 scene; densified model): profiles/r3_footprint_sweep.md")
     ap.add_argument("--teacher-seed", type=int, default=0, help="seed of the teacher scene S(N,H,W,seed)")
     ap.add_argument("--unchanged-trainer-legs", action="store_true",
                     help="run ONLY the legs of the reference's unchanged loop (reference_shaped_step, import_swap_only_step, label_phase_shape) and print them "
-                         "as one JSON line; the default run starts this in a child process (a fresh interpreter, as a trainer would be)")
+                         "as one JSON line; the --full run starts this in a child process (a fresh interpreter, as a trainer would be)")
     ap.add_argument("--verify-ranks", action="store_true", help="add per-rank frame lists, start-of-run parameter checksums and loss sums to the JSON line")
     args = ap.parse_args()
 
@@ -600,6 +638,7 @@ def main():
         r_sum = [0, 0]
 
         host_t = [0.0, 0.0, 0]                                      # host seconds inside render() / loss.backward(), calls
+        last = {}                                                   # what the latest eager step returned (--dump-outputs)
         # eager loop on the fast paths: no host wait for the instance count either -- the frame is checked at the next forward, a frame
         # that did not fit is voided on the device (egogaussian_amd/_C.py StepGuard(deferred=True))
         eguard = _C.StepGuard(dev, deferred=True) if eager_fast else None
@@ -633,6 +672,8 @@ def main():
             loss_acc.add_(loss.detach())
             r_sum[0] += _C.stats["num_rendered"]; r_sum[1] += 1
             host_t[0] += th1 - th0; host_t[1] += th3 - th2; host_t[2] += 1
+            if args.dump_outputs:
+                last["image"], last["radii"], last["loss"] = out["render"], out["radii"], loss
 
         psnr_start = eval_psnr()
         step, graphed = eager_step, None
@@ -693,10 +734,29 @@ def main():
         torch.cuda.synchronize()
         loss_first = (graphed.loss_sum if graphed is not None else loss_acc).clone()      # the loss sum of the contract's region
         r_first = list(r_sum)
+
+        def leg_outputs(g):
+            """What the latest launch of the timed path (g: the captured step that was replayed; None: the eager step) left its caller: the
+            model it updated, the image and radii of its last iteration, the loss of each of its iterations (copies)."""
+            src = ({"image": g.image, "radii": g.radii, "losses": torch.stack(g.losses)} if g is not None else
+                   {"image": last["image"], "radii": last["radii"], "losses": last["loss"].reshape(1)})
+            with torch.no_grad():
+                o = {"xyz": pc._xyz, "features_dc": pc._features_dc.reshape(N, -1), "opacity": pc._opacity, "scaling": pc._scaling,
+                     "rotation": pc._rotation, **({"features_rest": pc._features_rest.reshape(N, -1)} if D > 0 else {}),
+                     "image": src["image"].permute(1, 2, 0).reshape(H * W, -1), "radii": src["radii"], "losses": src["losses"]}
+                return {k_: v_.detach().float().clone() for k_, v_ in o.items()}
+        # --dump-outputs, first half: what the LAST timed launch left, taken before anything else moves the model on.  Same arguments, same
+        # inputs -- but this state is not the same from run to run: the backward sums with float atomics in an order that varies, and the
+        # chained steps of Adam at eps = 1e-15 amplify those last bits.  Two runs of one build, 500k @ 960x540, relative to each array's
+        # maximum: 3 steps 3e-6, 7 steps 1e-3, 27 steps 1e-2 (a handful of elements; losses 1e-6), 222 steps 2e-2 (losses 1e-3).  Kept under
+        # DIR/after_timed_steps/ for a comparer that brings such a tolerance ...
+        after = None
+        if args.dump_outputs and dynamic == args.dynamic:           # (the headline leg)
+            after = dict(leg_outputs(graphed), loss_sum=loss_first.clone())
         # the SAME region four more times (training goes on: the workload sheds pairs as the student converges, DESIGN.md section 5):
         # `value` stays the first -- the contract's -- and the line adds the median and the spread of the five
         reps = [elapsed]
-        for rep in range(1, 5):
+        for rep in range(1, 5 if args.full else 1):
             t_r = time.perf_counter()
             for i in range(0, args.steps, spr):
                 step(n_warm + rep * args.steps + i)
@@ -715,6 +775,7 @@ def main():
         if graphed is not None:
             overflow = {"capacity": graphed.capacity, "max_instances": graphed.max_instances(), "ok": graphed.ok()}
             assert graphed.ok(), f"a replayed frame exceeded the captured capacity ({graphed.max_instances()} > {graphed.capacity}); its update was skipped"
+        if graphed is not None and args.full:
             # Kernels replayed from a hipGraph are not bracketed by the library's events (those are host-side records), so the
             # per-stage durations come from a second, eager timed pass over the same workload right after the replayed one.
             n_ev = min(args.steps, 50)
@@ -736,19 +797,61 @@ def main():
         kept = rect = pairs = visits = 0
         list_mean, list_max = [], []
         with torch.no_grad():
-            for i in range(0, n_used, max(1, n_used // 4)):
+            for i in range(0, n_used, max(1, n_used // 4)) if args.full else ():
                 render(cams[i], pc, Pipe, bg, **rkw(rot[i] if dynamic else None))
                 kept += int(_C.stats["total_view"].item()); rect += _C.stats["num_rendered"]
                 ls = tile_list_stats(_C, _C.stats["image_buffer"], W, H)
                 pairs += ls["pairs_Q"]; visits += ls["visits"]
                 list_mean.append(ls["tile_list_len_mean"]); list_max.append(ls["tile_list_len_max"])
         n_s = len(range(0, n_used, max(1, n_used // 4)))
+        dumped = None
+        if after is not None:                                       # --dump-outputs, second half (last of all in the leg)
+            # ... and, in DIR itself, what two runs and two builds CAN be compared by to float32 rounding: the launch that ended the timed
+            # region once more from the seeded start -- student parameters, zero Adam moments and step counts.
+            #   losses   of the steps_per_replay chained iterations of THE captured graph the loop replayed, on the frames of its last
+            #            replay (frame copy, forward, loss, backward, Adam with its moments and bias correction, overflow guard): bit-identical
+            #            between runs as measured, while the model after those five iterations already is not (1e-4; image 1e-3);
+            #   the rest after the FIRST of those iterations alone (the same step captured with steps_per_replay = 1 where the loop's graph
+            #            holds more; the eager step without a graph): image / radii bit-identical, parameters within 1e-5 (one element at 7e-6, the rest
+            #            below 1e-6 of their array's maximum).
+            # The trained state is put back afterwards (the --full legs go on with it).
+            tensors = list(pc.parameters()) + [st[name] for st in opt.state.values() for name in ("exp_avg", "exp_avg_sq", "step") if torch.is_tensor(st.get(name))]
+            kept_state, r_kept = [t.detach().clone() for t in tensors], list(r_sum)
+
+            def to_seeded_start():
+                with torch.no_grad():
+                    for p, a in zip(pc.parameters(), SynthGaussians(student, device=dev, sh_degree=D, requires_grad=False).parameters()):
+                        p.copy_(a)
+                    for t in tensors[len(pc.parameters()):]:
+                        t.zero_()
+            i0 = n_warm + args.steps - spr                          # first iteration of the last timed launch
+            to_seeded_start()
+            step(i0)
+            torch.cuda.synchronize()
+            assert graphed is None or graphed.ok(), "the replay from the seeded start exceeded the captured capacity"
+            first = leg_outputs(graphed)
+            if spr > 1:
+                losses, k0 = first["losses"], i0 % n_used
+                one = GraphedTrainStep(pc, opt, bg, 0.2, dynamic=dynamic, gated=dynamic, steps_per_replay=1)
+                one.capture(cams[k0], gts[k0], warmup=1, accum_R=rot[k0] if dynamic else None, gate=gates[k0] if dynamic else None, capacity=graphed.capacity)
+                to_seeded_start()
+                one(frames[k0:k0 + 1])
+                torch.cuda.synchronize()
+                assert one.ok(), "the single step from the seeded start exceeded the captured capacity"
+                first = dict(leg_outputs(one), losses=losses)
+                opt.guard = graphed.guard
+                del one
+            dumped = dict(first, **{"after_timed_steps/" + k_: v_ for k_, v_ in after.items()})
+            with torch.no_grad():
+                for t, a in zip(tensors, kept_state):
+                    t.copy_(a)
+            r_sum[:] = r_kept
         return dict(lg_in_blend=bool(graphed is not None and getattr(graphed, "loss_grad_in_blend", False)),
-                    elapsed=elapsed, stages=stages, stage_timing=stage_timing, loss=loss_acc.item(), psnr_end=psnr_end, psnr_start=psnr_start,
+                    elapsed=elapsed, stages=stages, stage_timing=stage_timing, loss=loss_first.item(), psnr_end=psnr_end, psnr_start=psnr_start,
                     R_mean=float(r_sum[0]) / max(r_sum[1], 1), kept_ratio=kept / max(rect, 1), pairs=pairs / n_s, visits=visits / n_s,
-                    list_mean=float(np.mean(list_mean)), list_max=int(max(list_max)),
+                    list_mean=float(np.mean(list_mean or [0])), list_max=int(max(list_max or [0])),
                     use_graph=use_graph, checksum=checksum, overflow=overflow, pc=pc, cams=cams, spr=spr, host_us=host_us, t_timed_start=t_timed_start, reps=reps,
-                    eager_overflows=eager_overflows)
+                    eager_overflows=eager_overflows, dumped=dumped)
 
     def reduce_leg(r):
         """Scalars only (RCCL over xGMI): max-over-ranks time, sums of loss / PSNR / instance counts."""
@@ -762,7 +865,7 @@ def main():
     if not args.dynamic:
         legs["static"] = run_leg(False)
         legs["static"]["red"] = reduce_leg(legs["static"])
-    if args.dynamic or not (args.no_fine_all_leg or args.op_only or args.torch_host_ops or args.no_graph or D > 0):
+    if args.dynamic or args.full and not (args.no_fine_all_leg or args.op_only or args.torch_host_ops or args.no_graph or D > 0):
         legs["dynamic"] = run_leg(True)
         legs["dynamic"]["red"] = reduce_leg(legs["dynamic"])
     head_name = "dynamic" if args.dynamic else "static"
@@ -783,6 +886,51 @@ def main():
 
     if rank != 0:
         egs_dist.shutdown()
+        return
+
+    total_steps = world * args.steps
+    step_text = {
+        "static": ("rasterizer fwd+bwd only (seeded upstream grads on colour/depth/alpha)" if args.op_only else
+                   ("cov3D(torch) + render fwd (HIP) + 0.8 L1 + 0.2 (1-SSIM) (torch) + bwd + Adam" if args.torch_host_ops else
+                    "render fwd (HIP; activations and cov3D inside its preprocess kernel) + 0.8 L1 + 0.2 (1-SSIM) (HIP) + bwd (HIP+autograd) + Adam (HIP)")),
+        "dynamic": "fine_all shape: object-rotated cov3D + opacity (HIP, one launch) + render(rot_cov=True, accum_R=R_k, which_object=1) fwd (HIP) + "
+                   "hand-mask-gated 0.8 L1 + 0.2 (1-SSIM) (HIP) + bwd + Adam (HIP); 30 % object Gaussians"}
+    out = {
+        "metric": "train iters/s (fwd+bwd render) + PSNR, 500k Gaussians @ 960x540",
+        "value": round(total_steps / red["elapsed_max"], 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * red["elapsed_max"] / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "collective": egs_dist.collective_name(), **({"collective_error": collective_error} if collective_error else {}),
+        "rccl_world_seen": world_seen if egs_dist.collective_name() == "rccl" else None, "collective_world_seen": world_seen,
+        "config": {"workload": f"S({N},{H},{W},seed{args.teacher_seed}) teacher/student, 300-frame orbit, 1 frame per GPU per step; step = " + step_text[head_name],
+                   "gaussians": N, "image": [H, W], "sh_degree": D,
+                   "teacher_seed": args.teacher_seed,
+                   "teacher_seed_note": "SURVEY.md 8d names instance C as S(500k,540,960,seed 0) and, in its ground-truth sentence, a teacher of seed 1; "
+                                        "the instance list is followed (as in rounds 1-3, so the numbers stay comparable); --teacher-seed 1 runs the other",
+                   "parallelism": f"frames sharded over {world} GPU(s), scalar all-reduce only",
+                   "launch": (f"one hipGraph replay per {head['spr']} steps ({head['spr']} complete iterations, each on its own frame, captured back to back)"
+                              if head["spr"] > 1 else "one hipGraph replay per step") if head["use_graph"] else "eager (one launch per kernel)",
+                   "optimizer": "Adam steps of all five parameters inside the rasterizer backward (egs_backward_adam), no gradient arrays" if head["use_graph"] else "FusedAdam.step(), one launch",
+                   "spinup_ms": args.spinup_ms,
+                   "spinup": "forward-only renders (no training) for that many ms of wall clock right before the warm-up steps: GPU clocks out of idle"},
+        "psnr_db": round(red["psnr"], 3), "psnr_db_before": round(red["psnr_before"], 3),
+        "psnr_views": "8 held-out views at half-frame phases across the orbit (never trained on)", "mean_loss": round(red["mean_loss"], 6),
+        **({"host_us_per_forward": round(head["host_us"][0], 1), "host_us_per_backward": round(head["host_us"][1], 1),
+            "host_us_note": "host time inside render() and inside loss.backward() per step (Python, ctypes, launches, the wait for the instance count), "
+                            "GPU not waited for"} if head.get("host_us") else {}),
+        **({"eager_frames_voided": head["eager_overflows"]} if head.get("eager_overflows") is not None else {}),
+        **({"valid": False, "invalid_reason": f"{head['eager_overflows']} frame(s) of the timed loop exceeded the instance capacity and were voided on the device: "
+                                              "`value` counts steps that did no update"} if head.get("eager_overflows") else {}),
+    }
+    if ranks_info is not None:
+        out["ranks"] = ranks_info
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["dumped"])
+        out["dumped_outputs"] = sorted(head["dumped"])
+    if not args.full:                                                   # a plain run ends here
+        egs_dist.shutdown()
+        sys.stdout.flush()
+        print(json.dumps(out), flush=True)                              # the ONE line of stdout, and the last thing written to it
         return
 
     npix = H * W
@@ -927,53 +1075,21 @@ def main():
                "sample": f"{n_cpu} rasterizer forward+backward passes (op only, no loss/optimizer) over the first frames of the same "
                          f"{N}@{W}x{H} workload, oracle/raster_oracle.c with OpenMP over tiles ({tcpu:.1f} s of wall clock on {cores} cores)"}
 
-    total_steps = world * args.steps
-    step_text = {
-        "static": ("rasterizer fwd+bwd only (seeded upstream grads on colour/depth/alpha)" if args.op_only else
-                   ("cov3D(torch) + render fwd (HIP) + 0.8 L1 + 0.2 (1-SSIM) (torch) + bwd + Adam" if args.torch_host_ops else
-                    "render fwd (HIP; activations and cov3D inside its preprocess kernel) + 0.8 L1 + 0.2 (1-SSIM) (HIP) + bwd (HIP+autograd) + Adam (HIP)")),
-        "dynamic": "fine_all shape: object-rotated cov3D + opacity (HIP, one launch) + render(rot_cov=True, accum_R=R_k, which_object=1) fwd (HIP) + "
-                   "hand-mask-gated 0.8 L1 + 0.2 (1-SSIM) (HIP) + bwd + Adam (HIP); 30 % object Gaussians"}
-    out = {
-        "metric": "train iters/s (fwd+bwd render) + PSNR, 500k Gaussians @ 960x540",
-        "value": round(total_steps / red["elapsed_max"], 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(1e3 * red["elapsed_max"] / args.steps, 4), "higher_is_better": True,
+    out.update({
         "value_median": round(total_steps / sorted(red["reps_max"])[len(red["reps_max"]) // 2], 3),
         "value_spread": [round(total_steps / max(red["reps_max"]), 3), round(total_steps / min(red["reps_max"]), 3)],
         "value_note": "`value` is the first timed region of exactly --steps steps after --warmup (the contract); the same region is then repeated "
                       "four times while training continues: value_median / value_spread = median and [min, max] of the five",
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "collective": egs_dist.collective_name(), **({"collective_error": collective_error} if collective_error else {}),
-        "rccl_world_seen": world_seen if egs_dist.collective_name() == "rccl" else None, "collective_world_seen": world_seen,
-        "config": {"workload": f"S({N},{H},{W},seed{args.teacher_seed}) teacher/student, 300-frame orbit, 1 frame per GPU per step; step = " + step_text[head_name],
-                   "gaussians": N, "image": [H, W], "sh_degree": D, "instances_R": int(R_mean), "instances_after_tile_culling": int(R_kept),
-                   "teacher_seed": args.teacher_seed,
-                   "teacher_seed_note": "SURVEY.md 8d names instance C as S(500k,540,960,seed 0) and, in its ground-truth sentence, a teacher of seed 1; "
-                                        "the instance list is followed (as in rounds 1-3, so the numbers stay comparable); --teacher-seed 1 runs the other",
-                   "tile_list_len_mean": round(head["list_mean"], 1), "tile_list_len_max": head["list_max"],
-                   "sort_passes_max": passes,
-                   "parallelism": f"frames sharded over {world} GPU(s), scalar all-reduce only",
-                   "launch": (f"one hipGraph replay per {head['spr']} steps ({head['spr']} complete iterations, each on its own frame, captured back to back)"
-                              if head["spr"] > 1 else "one hipGraph replay per step") if head["use_graph"] else "eager (one launch per kernel)",
-                   "optimizer": "Adam steps of all five parameters inside the rasterizer backward (egs_backward_adam), no gradient arrays" if head["use_graph"] else "FusedAdam.step(), one launch",
-                   "spinup_ms": args.spinup_ms,
-                   "spinup": "forward-only renders (no training) for that many ms of wall clock right before the warm-up steps: GPU clocks out of idle"},
-        "psnr_db": round(red["psnr"], 3), "psnr_db_before": round(red["psnr_before"], 3),
-        "psnr_views": "8 held-out views at half-frame phases across the orbit (never trained on)", "mean_loss": round(red["mean_loss"], 6),
         "rasterizer_ms_per_step": round(op_ms, 4),
-        **({"host_us_per_forward": round(head["host_us"][0], 1), "host_us_per_backward": round(head["host_us"][1], 1),
-            "host_us_note": "host time inside render() and inside loss.backward() per step (Python, ctypes, launches, the wait for the instance count), "
-                            "GPU not waited for"} if head.get("host_us") else {}),
         "roofline": roofline, "stages": stage_rows,
         **({"replayed_step_kernels": step_table,
             "replayed_step_kernels_note": f"profiles/graph_step_budget.json (rocprofv3 --kernel-trace, {budget['steps']} replayed steps, same kernel sources: {src_hash}); "
                                           "counter_MB = (2 FETCH_SIZE + WRITE_SIZE) x 1024 per launch from profiles/pmc_traffic.json where a PMC pass covers exactly that launch "
                                           "(the bucketing's scan + scatter were counted together: 'tile_bucket' there)"} if step_table else {}),
         "cpu_baseline": cpu,
-        **({"eager_frames_voided": head["eager_overflows"]} if head.get("eager_overflows") is not None else {}),
-        **({"valid": False, "invalid_reason": f"{head['eager_overflows']} frame(s) of the timed loop exceeded the instance capacity and were voided on the device: "
-                                              "`value` counts steps that did no update"} if head.get("eager_overflows") else {}),
-    }
+    })
+    out["config"].update({"instances_R": int(R_mean), "instances_after_tile_culling": int(R_kept),
+                          "tile_list_len_mean": round(head["list_mean"], 1), "tile_list_len_max": head["list_max"], "sort_passes_max": passes})
     if head_name == "static" and "dynamic" in legs:
         dl, dr = legs["dynamic"], legs["dynamic"]["red"]
         out["fine_all_shape"] = {
@@ -984,8 +1100,6 @@ def main():
             "launch": (f"one hipGraph replay per {dl['spr']} steps" if dl["spr"] > 1 else "one hipGraph replay per step") if dl["use_graph"] else "eager",
             "step": step_text["dynamic"],
             "reference": "/root/reference/trainers/fine_all.py:74-101 (BASELINE.json config 4)"}
-    if ranks_info is not None:
-        out["ranks"] = ranks_info
     if world == 1 and D == 0 and not args.no_sh3_leg and not (args.op_only or args.torch_host_ops or args.no_graph or args.dynamic):
         # The same step with the colour model the reference ends training with (max_sh_degree = 3: 16 coefficients per channel,
         # /root/reference/arguments/__init__.py), measured by this script in a child process on the same GPU and reported beside
@@ -993,7 +1107,7 @@ def main():
         import subprocess
         torch.cuda.synchronize()
         try:
-            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--sh-degree", "3", "--steps", str(min(args.steps, 100)), "--warmup",
+            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--sh-degree", "3", "--steps", str(min(args.steps, 100)), "--warmup",
                                   str(min(args.warmup, 10)), "--no-cpu-baseline", "--gaussians", str(N), "--height", str(H), "--width", str(W)],
                                  capture_output=True, text=True, timeout=600)
             j = json.loads(leg.stdout.strip().splitlines()[-1])
@@ -1017,7 +1131,7 @@ def main():
         # (/root/reference/trainers/train_static.py:112).  What a trainer gets from `import egogaussian_amd; egogaussian_amd.attach(gaussians)`
         # plus this package's render() and loss, with its loop otherwise unchanged.
         try:
-            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-graph", "--item-every-step", "--eager-fast", "--steps", str(min(args.steps, 200)),
+            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-graph", "--item-every-step", "--eager-fast", "--steps", str(min(args.steps, 200)),
                                   "--warmup", "20", "--no-cpu-baseline", "--gaussians", str(N), "--height", str(H), "--width", str(W)],
                                  capture_output=True, text=True, timeout=600)
             j = json.loads(leg.stdout.strip().splitlines()[-1])
@@ -1032,7 +1146,7 @@ def main():
         # ... and the same loop for a trainer that reads the loss only now and then: with the instance count checked at the NEXT forward
         # (StepGuard(deferred=True)) nothing in the iteration waits for the GPU, so the host runs ahead and the two overlap
         try:
-            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-graph", "--eager-fast", "--steps", str(min(args.steps, 200)),
+            leg = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-graph", "--eager-fast", "--steps", str(min(args.steps, 200)),
                                   "--warmup", "20", "--no-cpu-baseline", "--gaussians", str(N), "--height", str(H), "--width", str(W)],
                                  capture_output=True, text=True, timeout=600)
             j = json.loads(leg.stdout.strip().splitlines()[-1])

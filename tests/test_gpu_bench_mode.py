@@ -220,6 +220,74 @@ def test_training_psnr_parity_300_steps_float_and_8bit():
     assert abs(res["gpu"][0] - res["cpu"][0]) <= 0.05 and abs(res["gpu"][1] - res["cpu"][1]) <= 0.05
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline fields and nothing that takes a run of its own.
+    DIR/after_timed_steps holds what the last timed launch left (a trained model; its image and loss belong to the last frame); DIR
+    itself the same launch from the seeded start (losses of the graph's chained iterations; image, radii and parameters after the first
+    of them), checked against a render and a loss computed here, and equal between two runs to float32 rounding."""
+    from egogaussian_amd.losses import training_loss
+    from egogaussian_amd.renderer import render
+    from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
+    n, H, W, steps, warm = 20000, 135, 240, 6, 4
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    outs = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--gaussians", str(n), "--height", str(H),
+               "--width", str(W), "--dump-outputs", str(tmp_path / name)]
+        run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert run.returncode == 0, run.stderr[-3000:]
+        j = json.loads(run.stdout.strip().splitlines()[-1])
+        root = str(tmp_path / name)
+        outs.append({os.path.relpath(os.path.join(d, f), root)[:-4]: np.load(os.path.join(d, f)) for d, _, fs in os.walk(root) for f in fs})
+    assert j["unit"] == "iters/s" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["steps"] == steps and j["value"] > 0
+    assert abs(j["ms_per_step"] - 1e3 / j["value"]) < 1e-3 * j["ms_per_step"] and 0 < j["mean_loss"] < 1
+    for moved in ("roofline", "stages", "cpu_baseline", "fine_all_shape", "sh_degree_3", "reference_shaped_step", "config_B_forward_only", "value_median"):
+        assert moved not in j, moved
+    out = outs[0]
+    names = ["xyz", "features_dc", "opacity", "scaling", "rotation", "image", "radii", "losses"]
+    assert sorted(out) == sorted(j["dumped_outputs"]) == sorted(names + ["after_timed_steps/" + k for k in names + ["loss_sum"]])
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    aft = {k[len("after_timed_steps/"):]: v for k, v in out.items() if k.startswith("after_timed_steps/")}
+    spr = 3                                                              # the largest divisor of 6 steps below --steps-per-replay 5
+    assert out["xyz"].shape == (n, 3) and out["rotation"].shape == (n, 4) and out["image"].shape == (H * W, 3) and out["radii"].shape == (n, 1)
+    assert out["losses"].shape == aft["losses"].shape == (spr, 1)
+    # references computed here: the teacher's and the student's renders of the frames in question, the loss by its PyTorch statement
+    dev = "cuda:0"
+    teacher = make_scene(n, H, W, seed=0)
+    start = perturb_student(teacher)
+    bg = torch.zeros(3, device=dev)
+    k_first, k_last = warm + steps - spr, warm + steps - 1              # frames of the last timed launch (frame k = step k of this one rank)
+    chw = lambda a: torch.tensor(a, device=dev).reshape(H, W, 3).permute(2, 0, 1).contiguous()
+    with torch.no_grad():
+        tpc, spc = SynthGaussians(teacher, device=dev, requires_grad=False), SynthGaussians(start, device=dev, requires_grad=False)
+        gt_first = render(make_camera(k_first, H, W, device=dev), tpc, Pipe, bg)["render"]
+        gt_last = render(make_camera(k_last, H, W, device=dev), tpc, Pipe, bg)["render"]
+        ref = render(make_camera(k_first, H, W, device=dev), spc, Pipe, bg)
+        loss_first = float(training_loss(chw(out["image"]), gt_first, 0.2))
+        loss_last = float(training_loss(chw(aft["image"]), gt_last, 0.2))
+    # from the seeded start: the image and radii are the student's on the first frame of the last launch, the first loss is that image's
+    assert np.abs(out["image"] - ref["render"].permute(1, 2, 0).reshape(H * W, 3).cpu().numpy()).max() <= 1e-6 * out["image"].max()
+    assert np.array_equal(out["radii"][:, 0], ref["radii"].float().cpu().numpy())
+    assert abs(out["losses"][0, 0] - loss_first) <= 5e-6, (out["losses"][0, 0], loss_first)          # (HIP loss against its PyTorch mirror: tests/test_install.py's bar)
+    assert np.all(np.diff(out["losses"][:, 0]) != 0)                                                  # the chained iterations are different ones
+    # Adam's first step from zero moments is lr * g / (|g| + 1e-15): every coordinate that has a gradient moves by its learning rate
+    for key, src, lr in (("xyz", "xyz", 1.6e-4), ("opacity", "opacity_logit", 0.05), ("scaling", "log_scale", 5e-3), ("rotation", "quat", 1e-3)):
+        moved_by = np.abs(out[key] - start[src]).max()
+        assert 0.99 * lr < moved_by < 1.01 * lr + 1e-6 * np.abs(start[src]).max(), (key, moved_by)
+    # after the timed steps: a model that trained (several steps away from the student), the image and loss of the LAST timed frame, the
+    # loss sum of the timed region
+    assert np.abs(aft["xyz"] - start["xyz"]).max() > 3 * 1.6e-4 and np.abs(aft["opacity"] - start["opacity_logit"]).max() > 3 * 0.05
+    assert abs(aft["losses"][-1, 0] - loss_last) <= 5e-6, (aft["losses"][-1, 0], loss_last)
+    assert abs(aft["loss_sum"].item() / steps - j["mean_loss"]) < 1e-5
+    # two runs, the part that is from the seeded start: the forward sums in a fixed order (image, radii, losses: float32 rounding at
+    # most); the backward's float atomics do not, but a gradient's last bits do not move lr * sign(g): 1e-5 of the array's maximum is ~100
+    # float32 ulps and below every learning rate here.  (after_timed_steps is not held to this: bench.py says how far it spreads.)
+    assert np.array_equal(out["radii"], outs[1]["radii"])
+    for key in names:
+        tol = (1e-6 if key in ("image", "losses") else 1e-5) * np.abs(out[key]).max()
+        assert np.abs(out[key] - outs[1][key]).max() <= tol, (key, np.abs(out[key] - outs[1][key]).max(), tol)
+
+
 def test_bench_two_ranks_plain_launch():
     """`python bench.py --gpus 2` with no launcher around it: the script re-executes itself as two ranks.  The test box has one
     GPU, so both ranks share device 0 and talk over gloo (RCCL refuses two ranks on one device)."""
@@ -227,7 +295,7 @@ def test_bench_two_ranks_plain_launch():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--gaussians", "60000", "--height", "270",
-           "--width", "480", "--no-cpu-baseline", "--no-sh3-leg", "--verify-ranks"]
+           "--width", "480", "--full", "--no-cpu-baseline", "--no-sh3-leg", "--verify-ranks"]      # --full: the fine_all leg and the roofline
     run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert run.returncode == 0, run.stderr[-3000:]
     line = [l for l in run.stdout.strip().splitlines() if l.startswith("{")][-1]

@@ -73,7 +73,7 @@ def test_bench_two_ranks_over_rccl_on_two_devices():
                                                             "EGS_BENCH_BACKEND")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "5", "--gaussians", "60000", "--height", "270",
-           "--width", "480", "--no-cpu-baseline", "--no-sh3-leg", "--verify-ranks"]
+           "--width", "480", "--full", "--no-cpu-baseline", "--no-sh3-leg", "--verify-ranks"]      # --full: the fine_all leg
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])

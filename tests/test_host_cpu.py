@@ -74,6 +74,28 @@ def test_bench_fine_all_inputs():
     assert bench.algorithmic_bytes("tile_sort", 0, 7, 0) == 84 and bench.algorithmic_bytes("preprocess_backward", 10, 0, 0) == 2160
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: float32 files, everything while it fits the budget, else the same seeded share of every array's items --
+    the same items in arrays of equal length and in every run."""
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES <= 64 << 20
+    n = 1000
+    arrays = {"xyz": torch.rand(n, 3), "index": torch.arange(n), "loss": torch.tensor(0.5), "image": torch.rand(50, 3).double()}
+    load = lambda d: {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    full = load(str(tmp_path / "all"))
+    assert sorted(full) == sorted(arrays) and full["xyz"].dtype == np.float32 and full["index"].dtype == np.float32 and full["image"].dtype == np.float64
+    assert np.array_equal(full["xyz"], arrays["xyz"].numpy()) and full["loss"].shape == (1, 1) and full["index"].shape == (n, 1)
+    bench.DUMP_BUDGET_BYTES = 8000
+    bench.dump_outputs(str(tmp_path / "a"), arrays); bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a, b = load(str(tmp_path / "a")), load(str(tmp_path / "b"))
+    assert sum(v.nbytes for v in a.values()) <= 8000 and 0 < a["xyz"].shape[0] < n
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    rows = a["index"][:, 0].astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a["xyz"], arrays["xyz"].numpy()[rows])
+
+
 def test_ready_to_pin_harness_inputs_are_reproducible():
     """tools/compare_upstream_npz.py: the committed input half (tests/golden/upstream) is what the seeds regenerate -- a holder of the
     reference's CUDA build who regenerates the inputs gets the same bytes, checked by hash before any comparison."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""profiles/r3_footprint_sweep.md from the JSON lines of `bench.py --footprints` and of the default `bench.py` run (config B / D legs)."""
+"""profiles/r3_footprint_sweep.md from the JSON lines of `bench.py --full --footprints` and of the `bench.py --full` run (config B / D legs)."""
 import json, sys
 foot = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])["footprints"]
 base = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]) if len(sys.argv) > 2 else {}
@@ -11,7 +11,7 @@ if "config_D_op_only" in base:
 legs.update({"S(500k), splats x2": foot.get("S500k_scale_x2", {}), "S(500k), splats x3": foot.get("S500k_scale_x3", {}),
              "densified model": foot.get("densified_model", {})})
 print("# Round 3: the rasterizer at heavier footprints than the headline scene\n")
-print("`python bench.py --footprints` (+ the config B / D legs of the default run), one MI355X; rasterizer forward + backward with colour, depth and")
+print("`python bench.py --full --footprints` (+ the config B / D legs of the `--full` run), one MI355X; rasterizer forward + backward with colour, depth and")
 print("alpha gradients (config B: forward only); per-stage times from HIP events the library records around each stage (us per launch).")
 print("S(500k) itself: 67 pixel-splat pairs per pixel, 918 instances per tile after culling, 37 of 64 lanes kept per (wave, splat) visit.\n")
 cols = ["preprocess", "tile_bucket", "tile_sort", "render_forward", "render_backward", "preprocess_backward"]

@@ -243,6 +243,35 @@ def _object_rotation_struct(object_rotation, dev, P):
     return st, tuple(keep)
 
 
+def _object_motion_struct(object_motion, dev, P, want_grad=False):
+    """(egs_object_motion struct or None, tensors to keep alive, grad float32[21] or None) from (A12 [3,4] or [12], moved uint8[P] / bool[P]
+    or None, M [3,3] / [9] or None, selected or None, row-0 gradient multiplier) -- the last three as in object_rotation; M None: the
+    covariances are not turned."""
+    if object_motion is None:
+        return None, (), None
+    A12, moved, M, sel, mult = object_motion
+    st = _lib.ObjectMotion()
+    keep = []
+    if M is not None:
+        rot_st, rot_keep = _object_rotation_struct((M, sel, mult), dev, P)
+        st.rot = rot_st; keep.extend(rot_keep)
+    else:
+        st.rot.row0_grad_mult = 1.0
+    A12 = _f32c(A12.detach(), "object motion").reshape(12)
+    st.A12 = A12.data_ptr(); keep.append(A12)
+    if moved is not None:
+        moved = moved.reshape(-1).to(torch.uint8).contiguous()
+        if moved.numel() != P or moved.device != dev:
+            raise RuntimeError("object_motion: `moved` must hold one byte per Gaussian on the rasterizer's device")
+        st.moved = moved.data_ptr(); keep.append(moved)
+    grad = None
+    if want_grad and P != 0:
+        grad = torch.empty((21,), device=dev, dtype=torch.float32)
+        scratch = torch.empty((max(int(_lib.load().egs_object_motion_scratch_bytes(int(P))), 4),), device=dev, dtype=torch.uint8)
+        st.grad, st.scratch = grad.data_ptr(), scratch.data_ptr(); keep.append(scratch)
+    return st, tuple(keep), grad
+
+
 def _f32c(t, name):
     if t is None:
         return None
@@ -270,13 +299,17 @@ COLORS_ONLY_BACKWARD = True        # measurement switch (bench.py label_phase_sh
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, activation_flags=0, sh_rest=None, active_count=None, guard=None, object_rotation=None, color_only=False):
+                        prefiltered, debug, activation_flags=0, sh_rest=None, active_count=None, guard=None, object_rotation=None, color_only=False,
+                        object_motion=None):
     """-> (num_rendered, color[3,H,W], depth[1,H,W], alpha[1,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer)
     color_only (extension, ABI 4): depth and alpha are not produced (None) -- the blend skips their sums and planes.
     active_count (extension): int32[1] device tensor, the number of live rows of a capacity-sized model (include/egs_raster.h);
     guard (extension): a StepGuard whose words a captured forward writes.
     object_rotation (extension): (M, selected, row-0 gradient multiplier) -- the `fine_all` call shape's rotated covariance built
     inside the rasterizer from scales + rotations (include/egs_raster.h egs_object_rotation); pass the same to the backward.
+    object_motion (extension, instead of object_rotation): (A12, moved, M, selected, row-0 gradient multiplier) -- the rows of `moved` are
+    placed, p' = A p + b, inside the preprocess kernels, and with M the covariance is turned as with object_rotation (include/egs_raster.h
+    egs_object_motion); pass the same to the backward.
     sh_rest (extension): `sh` is then the DC block [P,1,3] and `sh_rest` the other coefficients [P,M-1,3] -- the two parameters the
     reference's GaussianModel stores, without the torch.cat of get_features (include/egs_raster.h: split spherical harmonics)."""
     L = _lib.load()
@@ -317,8 +350,14 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             pinned = _pinned_counts[key] = torch.empty((max(nb, 4096),), dtype=torch.int32, pin_memory=True)
         capturing = torch.cuda.is_current_stream_capturing()
         place = None if _NO_PLACEMENT else placement_buffer(dev, W, H)
-        rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
-        rot_arg = C.byref(rot_st) if rot_st is not None else None
+        if object_motion is not None:
+            if object_rotation is not None:
+                raise RuntimeError("object_motion and object_rotation are mutually exclusive (the motion carries the rotation)")
+            rot_st, _rot_keep, _ = _object_motion_struct(object_motion, dev, P)
+            activation_flags = int(activation_flags) | _lib.ACT_OBJECT_MOTION
+        else:
+            rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
+        rot_arg = _lib.rot_pointer(rot_st)
         deferred = guard is not None and getattr(guard, "deferred", False) and not capturing and P != 0
         if deferred:
             _settle(guard)                                       # the previous frame of this guard: did it fit?
@@ -400,7 +439,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                  dL_dout_alpha, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, alpha,
                                  debug, activation_flags=0, sh_rest=None, densify_stats=None, guard=None, sink=None,
-                                 prologue_scratch=None, object_rotation=None, grad_mask=0, loss_grad=None):
+                                 prologue_scratch=None, object_rotation=None, grad_mask=0, loss_grad=None, object_motion=None, motion_grad=False):
     """-> (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
            dL_dscales[P,3], dL_drotations[P,4]); with sh_rest, dL_dsh is [P,1,3] and a ninth element dL_dsh_rest[P,M-1,3] follows.
     densify_stats (extension): (xyz_gradient_accum[P,1], denom[P,1], max_radii2D[P] or None), float32, updated in place by the kernel
@@ -414,7 +453,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     image loss's gradient itself from what the loss forward left (include/egs_raster.h egs_backward_lossgrad; fused.l1_ssim_loss(raster_lossgrad=True)).
     grad_mask (extension, ABI 4): GRAD_* bits of the inputs whose gradient the caller reads (autograd's needs_input_grad), 0 = all.
     GRAD_COLORS alone with `colors` given -- the reference's label call, /root/reference/gaussian_renderer/render_helper.py:38-54 --
-    takes the colours-only backward: only dL_dcolors is produced, every other position of the result is None."""
+    takes the colours-only backward: only dL_dcolors is produced, every other position of the result is None.
+    object_motion (extension): as given to the forward; dL_dmeans3D is then the gradient of the CANONICAL positions, and one more element
+    follows the result: with motion_grad the pose gradient float32[21] (dL/dA12 [12] in A12's layout, dL/dM9 [9]), else None."""
     L = _lib.load()
     means3D = _f32c(means3D, "means3D")
     dev = means3D.device
@@ -430,7 +471,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     sh_rest = _opt(_f32c(sh_rest, "sh_rest"))
     M = 0 if sh is None else sh.shape[1] + (0 if sh_rest is None else sh_rest.shape[1])
     if COLORS_ONLY_BACKWARD and P != 0 and grad_mask == GRAD_COLORS and colors is not None and sink is None and densify_stats is None and object_rotation is None \
-            and loss_grad is None:          # (a loss gradient computed in the blend needs the full path: dL_dout_color is uninitialised then)
+            and loss_grad is None and object_motion is None:          # (a loss gradient computed in the blend needs the full path: dL_dout_color is uninitialised then)
         with _hip.device_ctx(dev):
             dcolors = torch.empty((P, 3), device=dev, dtype=torch.float32)
             scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
@@ -467,7 +508,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if not own_cov:                                      # absent inputs get empty gradients (the autograd Function maps them to None)
             dscales = None if fused(_lib.SINK_SCALES) else e(0, 3)
             drots = None if fused(_lib.SINK_ROTATIONS) else e(0, 4)
-        rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
+        pose_grad = None
+        if object_motion is not None:
+            rot_st, _rot_keep, pose_grad = _object_motion_struct(object_motion, dev, P, motion_grad)
+            activation_flags = int(activation_flags) | _lib.ACT_OBJECT_MOTION
+            if motion_grad and P == 0:
+                pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32)
+        else:
+            rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
         if P != 0 and loss_grad is not None:
             if g_depth is not None or g_alpha is not None:
                 raise RuntimeError("loss_grad: the loss must depend on the colour output only")
@@ -480,7 +528,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
                 _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
                 C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
-                C.byref(rot_st) if rot_st is not None else None, 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
             if owned:
                 sink.mark_stepped()
         elif P != 0 and (owned or prologue_scratch is not None or rot_st is not None):
@@ -493,7 +541,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
                 _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
                 C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
-                C.byref(rot_st) if rot_st is not None else None, 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
             if owned:
                 sink.mark_stepped()
         elif P != 0:
@@ -506,9 +554,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dopacity), _ptr(dmeans3D), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
                 _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
                 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+    tail = () if object_motion is None else (pose_grad,)
     if sh_rest is not None:
-        return dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots, dsh_rest
-    return dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots
+        return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots, dsh_rest) + tail
+    return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots) + tail
 
 
 def _stat_ptrs(stats_tensors, P, dev):

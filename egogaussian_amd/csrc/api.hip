@@ -3,6 +3,7 @@
 // Replaces the pybind `_C` entry points of the upstream extension bound at
 // /root/reference/gaussian_renderer/__init__.py:14.
 #include "egs_common.h"
+#include "object_motion.h"
 #include "backward_prologue.h"
 #include <string.h>
 #include <vector>
@@ -93,7 +94,7 @@ static inline bool misaligned(const void* a, const void* b = nullptr, const void
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 255u) != 0;
 }
 int check_modes(const float* shs, const float* colors, const float* scales, const float* rots, const float* cov, int act) {
-    if (act & ~(EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS | EGS_ACT_LOGIT_OPACITY)) return EGS_ERR_MODE;
+    if (act & ~(EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS | EGS_ACT_LOGIT_OPACITY | EGS_ACT_OBJECT_MOTION)) return EGS_ERR_MODE;
     if ((act & (EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS)) && cov != nullptr) return EGS_ERR_MODE;   // nothing to activate: the covariance is given
     if ((shs != nullptr) == (colors != nullptr)) return EGS_ERR_MODE;
     const bool sr = scales != nullptr && rots != nullptr;
@@ -263,6 +264,23 @@ static int obj_rot_args(const egs_object_rotation* rot, const float* scales, Egs
     r.M = rot->M9; r.sel = rot->selected; r.mult = rot->row0_grad_mult; r.mult_dev = rot->row0_grad_mult_dev;
     return 0;
 }
+// With EGS_ACT_OBJECT_MOTION the `rot` argument points to an egs_object_motion (HOST struct): the rotation as above (rot.M9 may be NULL:
+// covariances are not turned) plus the placement of the positions and, optionally, where the pose gradient goes.
+struct MotionHost { EgsMotion k; float* grad; };
+static int obj_motion_args(int act, const egs_object_rotation* rot, const float* scales, int P, EgsObjRot& r, MotionHost& m) {
+    m = MotionHost{ EgsMotion{ nullptr, nullptr, nullptr, nullptr }, nullptr };
+    if (!(act & EGS_ACT_OBJECT_MOTION)) return obj_rot_args(rot, scales, r);
+    const egs_object_motion* om = reinterpret_cast<const egs_object_motion*>(rot);
+    if (!om) return EGS_ERR_MODE;                                     // the bit without its struct: no such mode
+    if (!om->A12 || (om->grad && !om->scratch)) return EGS_ERR_ARG;
+    int rc = obj_rot_args(&om->rot, scales, r); if (rc) return rc;
+    m.k.A = om->A12; m.k.moved = om->moved; m.grad = om->grad;
+    if (om->grad) {
+        m.k.pose_partial = (float*)om->scratch;
+        if (r.M) m.k.dM_partial = (float*)om->scratch + egs_motion_rot_offset(P);
+    }
+    return 0;
+}
 
 int egs_forward_geometry(int P, int sh_degree, int sh_coeffs, const float* means3D, const float* shs, const float* shs_rest,
                          const float* colors_precomp, const float* opacities, const float* scales,
@@ -281,14 +299,14 @@ int egs_forward_geometry(int P, int sh_degree, int sh_coeffs, const float* means
     if (shs && (sh_degree < 0 || sh_degree > EGS_MAX_SH_DEGREE || sh_coeffs < (sh_degree + 1) * (sh_degree + 1))) return EGS_ERR_RANGE;
     if (shs_rest && (!shs || sh_coeffs < 2)) return EGS_ERR_MODE;
     hipStream_t s = (hipStream_t)stream;
-    EgsObjRot orot; rc = obj_rot_args(rot, scales, orot); if (rc) return rc;
+    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     EgsGeomPtrs g = geom_ptrs(geom_buffer, P);
     EgsCamera cam = { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy };
     egs_prof_start(EGS_K_PREPROCESS, s);
     const bool sh_apart = shs && (sh_coeffs > 1 || shs_rest);         // rows of 12 M bytes: the wave-tiled kernel (preprocess.hip)
     EGS_TRY(egs_launch_preprocess(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
-                                  rotations, activation_flags, cov3D_precomp, cam, radii, g, nullptr, 0, active_count, nullptr, orot, s));
-    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, s));
+                                  rotations, activation_flags, cov3D_precomp, cam, radii, g, nullptr, 0, active_count, nullptr, orot, mh.k, s));
+    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, mh.k, s));
     egs_prof_stop(EGS_K_PREPROCESS, s);
     EGS_SYNC_IF_DEBUG(s);
     // R = sum of the per-block instance counts (a few KB device->host; the only host wait of the forward)
@@ -331,7 +349,7 @@ static int forward_impl(int wait_for_count, int P, int sh_degree, int sh_coeffs,
     rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
     if (shs && (sh_degree < 0 || sh_degree > EGS_MAX_SH_DEGREE || sh_coeffs < (sh_degree + 1) * (sh_degree + 1))) return EGS_ERR_RANGE;
     if (shs_rest && (!shs || sh_coeffs < 2)) return EGS_ERR_MODE;
-    EgsObjRot orot; rc = obj_rot_args(rot, scales, orot); if (rc) return rc;
+    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     static thread_local hipEvent_t ev = nullptr;
     if (wait_for_count && !ev) EGS_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     EgsGeomPtrs g = geom_ptrs(geom_buffer, P);
@@ -359,12 +377,12 @@ static int forward_impl(int wait_for_count, int P, int sh_degree, int sh_coeffs,
         placement_sums(placement, width, height, &b_spec.chunk_sum, &b_spec.zero_after_n);
         b_spec.zero_after = b_spec.chunk_sum;
         EGS_TRY(egs_launch_preprocess_count(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
-                                            rotations, activation_flags, cov3D_precomp, cam, radii, g, b_spec, active_count, &im_spec, orot, cull_on(debug), s));
+                                            rotations, activation_flags, cov3D_precomp, cam, radii, g, b_spec, active_count, &im_spec, orot, mh.k, cull_on(debug), s));
     } else
     EGS_TRY(egs_launch_preprocess(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
                                   rotations, activation_flags, cov3D_precomp, cam, radii, g, capacity > 0 ? b_spec.chunk_sum : nullptr, n_sums,
-                                  active_count, (capacity > 0 && placement) ? &im_spec : nullptr, orot, s));
-    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, s));
+                                  active_count, (capacity > 0 && placement) ? &im_spec : nullptr, orot, mh.k, s));
+    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, mh.k, s));
     egs_prof_stop(EGS_K_PREPROCESS, s);
     const size_t nb = ((size_t)P + 255) / 256;
     if (pinned_host_counts) EGS_TRY(hipMemcpyAsync(pinned_host_counts, g.scan_scratch, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -480,7 +498,7 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
                  const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
                  void* stream, int debug, const egs_loss_grad* loss_grad = nullptr) {
     int rc = check_dims(P, width, height); if (rc) return rc;
-    EgsObjRot orot; rc = obj_rot_args(rot, scales, orot); if (rc) return rc;
+    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     // the image loss's gradient computed by the blend itself (egs_backward_lossgrad): colour gradients only, three channels
     EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr;
     if (loss_grad) {
@@ -493,7 +511,11 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
         lgp = &lgh;
         if (!dL_dout_color) dL_dout_color = q.image;                 // (never read: the checks below want a pointer)
     }
-    if (P == 0) { if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, (hipStream_t)stream)); return 0; }
+    if (P == 0) {
+        if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, (hipStream_t)stream));
+        if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, (hipStream_t)stream));
+        return 0;
+    }
     if (R < 0 || R >= (1ll << 31)) return EGS_ERR_RANGE;
     if (grad_mask & ~EGS_GRAD_MASK_BITS) return EGS_ERR_ARG;
     // Only the precomputed colours' gradient is wanted (the reference's label call): a blend that sums w dL/dC alone, no preprocess backward
@@ -518,6 +540,7 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
         EGS_SYNC_IF_DEBUG(s);
         egs_prof_start(EGS_K_PREPROCESS_BWD, s);
         EGS_TRY(egs_launch_colors_from_acc(P, grad_acc, g.clamped, radii, dL_dcolors, s));
+        if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, s));       // (the positions carry no gradient on this path)
         egs_prof_stop(EGS_K_PREPROCESS_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
         return 0;
@@ -589,9 +612,14 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
     EGS_TRY(egs_launch_preprocess_backward(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, scales, scale_modifier, rotations,
                                            cov3D_precomp, activation_flags, cam, radii, g, grad_acc, colors_precomp != nullptr, dL_dmeans2D,
                                            dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, sh_apart ? nullptr : dL_dsh, dL_dscales,
-                                           dL_drotations, stat_grad_accum, stat_denom, stat_max_radii, skip_flag, pp_sinks ? &ks : nullptr, orot, s));
+                                           dL_drotations, stat_grad_accum, stat_denom, stat_max_radii, skip_flag, pp_sinks ? &ks : nullptr, orot, mh.k,
+                                           sh_apart ? 1 : 0, s));
     if (sh_apart) EGS_TRY(egs_launch_sh_backward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, radii, g, dL_dcolors, dL_dsh,
-                                                 dL_dsh_rest, dL_dmeans3D, sh_sinks ? &ks_sh : nullptr, s));
+                                                 dL_dsh_rest, dL_dmeans3D, sh_sinks ? &ks_sh : nullptr, mh.k, s));
+    // the pose gradient: the lines the launch that finished the positions' gradient wrote (one per 64 rows from the spherical-harmonics
+    // launch, per 256 otherwise), and the rotation lines of the preprocess backward, added up by one workgroup
+    if (mh.grad) EGS_TRY(egs_launch_motion_finish(mh.k.pose_partial, (int)(sh_apart ? egs_motion_pose_lines_max(P) : egs_motion_rot_lines(P)),
+                                                  mh.k.dM_partial, mh.k.dM_partial ? (int)egs_motion_rot_lines(P) : 0, mh.grad, s));
     egs_prof_stop(EGS_K_PREPROCESS_BWD, s);
     EGS_SYNC_IF_DEBUG(s);
     return 0;

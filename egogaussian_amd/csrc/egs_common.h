@@ -149,6 +149,12 @@ __device__ __forceinline__ void egs_adam_tick(const EgsAdamTick& t, unsigned lan
 // The `fine_all` call shape inside the preprocess kernels (include/egs_raster.h egs_object_rotation): rows with sel[i] != 0 (all rows if
 // sel == NULL) get cov3D = (M R S)(M R S)^T.  M == NULL: nothing is moved.
 struct EgsObjRot { const float* M; const uint8_t* sel; float mult; const float* mult_dev; };
+// Rigid object motion inside the same kernels (include/egs_raster.h egs_object_motion, csrc/object_motion.h): rows with moved[i] != 0 (all rows if
+// moved == NULL) are placed, p' = A p + b.  A == NULL: no motion (the instantiations without it run).  pose_partial / dM_partial: where the
+// backward's workgroups write their lines of the pose / rotation sums; NULL = that gradient is not asked for (no shuffles).
+struct EgsMotion { const float* A; const uint8_t* moved; float* pose_partial; float* dM_partial; };
+// adds the lines up (float64, index order) and writes grad21 = dL/dA12 [12], dL/dM9 [9] (zeros where no lines were written)
+hipError_t egs_launch_motion_finish(const float* pose_partial, int pose_lines, const float* dM_partial, int dM_lines, float* grad21, hipStream_t s);
 
 // ---- launchers (host side, one per translation unit) -------------------------------------------
 struct EgsCamera {
@@ -161,23 +167,24 @@ hipError_t egs_launch_preprocess(int P, int D, int M, const float* means3D, cons
                                  const float* opac, const float* scales, float mod, const float* rots, int act,
                                  const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
                                  const int32_t* active_count, const EgsImgPtrs* place /*NULL, or: also order im.fwd_cost into im.fwd_order*/,
-                                 EgsObjRot rot, hipStream_t s);
+                                 EgsObjRot rot, EgsMotion mot, hipStream_t s);
 hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* means3D, const float* shs,
                                           const float* scales, float mod, const float* rots, const float* cov3D, int act,
                                           EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const float* grad_acc,
                                           int colors_given, float* dmeans2D, float* dcolors, float* dopac,
                                           float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
                                           float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
-                                          const EgsSink* sink /*NULL: gradients only*/, EgsObjRot rot, hipStream_t s);
+                                          const EgsSink* sink /*NULL: gradients only*/, EgsObjRot rot, EgsMotion mot,
+                                          int motion_finished_later /*egs_launch_sh_backward follows and finishes the positions' gradient*/, hipStream_t s);
 // Spherical harmonics as separate launches (M > 1 coefficients, or DC / rest given as two arrays: sh_rest != NULL).  The
 // preprocess launchers are then called with shs = NULL: the forward leaves the record's colour open, the backward leaves
 // dL/dSH and the view-direction part of dL/dmean3D to egs_launch_sh_backward (which must run after it).
 hipError_t egs_launch_sh_forward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                 EgsGeomPtrs g, hipStream_t s);
+                                 EgsGeomPtrs g, EgsMotion mot, hipStream_t s);
 // sink (may be NULL; only with egs_sh_backward_can_sink): the Adam step of features_dc / features_rest / positions taken by this launch
 hipError_t egs_launch_sh_backward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
                                   const int32_t* radii, EgsGeomPtrs g, const float* dcolors, float* dsh_a, float* dsh_rest,
-                                  float* dmeans3D, const EgsSink* sink, hipStream_t s);
+                                  float* dmeans3D, const EgsSink* sink, EgsMotion mot, hipStream_t s);
 bool egs_sh_backward_can_sink(int M, const float* sh_a, const float* sh_rest);      // the M = 16 split-array kernel will run
 hipError_t egs_launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
@@ -202,7 +209,7 @@ bool egs_can_fuse_count(int P, int W, int H, int cull);
 hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
                                        const float* opac, const float* scales, float mod, const float* rots, int act,
                                        const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
-                                       const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, int cull, hipStream_t s);
+                                       const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, int cull, hipStream_t s);
 // placed: im.fwd_order holds this frame's placement (the preprocess launch carried the ordering job); else the static mapping
 // sort (may be NULL, or table_scanned == NULL in it): the blend sorts every tile's bucket itself first (egs_launch_binning made no sort launch)
 hipError_t egs_launch_render_forward(int W, int H, const float* bg, EgsGeomPtrs g, const uint32_t* point_list,

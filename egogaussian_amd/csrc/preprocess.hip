@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include "bin_walk.h"              // the count pass of the tile bucketing, carried by k_preprocess_count
 #include "backward_prologue.h"
+#include "object_motion.h"          // the rigid object motion of the positions (EGS_ACT_OBJECT_MOTION)
 
 namespace {
 
@@ -140,6 +141,8 @@ __device__ __forceinline__ float sh_channel(int deg, const float* sh, int ch, fl
 
 struct PreOut { uint2 rect; float4 r0, r1, r2; };
 // Returns the number of tiles the Gaussian touches (0 = culled).
+// MOTION: a moved row is placed first, p <- A p + b (object_motion.h), and everything below sees the placed position.
+template <bool MOTION>
 __device__ __forceinline__ uint32_t preprocess_one(
     int i, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ colors, const float* __restrict__ opac, const float* __restrict__ scales, float mod,
@@ -147,11 +150,14 @@ __device__ __forceinline__ uint32_t preprocess_one(
     const float* __restrict__ PM, const float* __restrict__ campos, int W, int H, float tanfovx, float tanfovy,
     int32_t* __restrict__ radii, float4* __restrict__ rec, uint2* __restrict__ rect_out,
     uint32_t* __restrict__ tiles_touched, uint8_t* __restrict__ clamped_out, uint8_t* __restrict__ visible, const EgsObjRot rot,
-    bool& hot, PreOut* out = nullptr /*the rectangle and the record as written (left alone when culled, i.e. on a zero return): k_preprocess_count walks them*/) {
+    const EgsMotion mot, bool& hot, PreOut* out = nullptr /*the rectangle and the record as written (left alone when culled, i.e. on a zero return): k_preprocess_count walks them*/) {
     const int gx = (W + EGS_TILE - 1) / EGS_TILE, gy = (H + EGS_TILE - 1) / EGS_TILE;
     radii[i] = 0; tiles_touched[i] = 0; visible[i] = 0;
 
-    const float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    if constexpr (MOTION) {
+        if (!mot.moved || mot.moved[i]) { const float p0[3] = { p[0], p[1], p[2] }; egs_motion_point(mot.A, p0, p); }   // (i < live: the caller's test)
+    }
     float c6[6];
     if (cov3D_in) {
 #pragma unroll
@@ -245,7 +251,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
 
 // PLACE: the first eight workgroups do not preprocess anything -- each orders one XCD band of the forward blend's tiles by the
 // costs the image buffer holds (backward_prologue.h), a job that needs doing before that blend and fits under this launch.
-template <bool PLACE>
+template <bool PLACE, bool MOTION>
 __global__ __launch_bounds__(256) void k_preprocess(
     int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ colors, const float* __restrict__ opac, const float* __restrict__ scales, float mod,
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(256) void k_preprocess(
     int32_t* __restrict__ radii, float4* __restrict__ rec, uint2* __restrict__ rect_out,
     uint32_t* __restrict__ tiles_touched, uint8_t* __restrict__ clamped_out, uint8_t* __restrict__ visible,
     uint32_t* __restrict__ block_sums, uint32_t* __restrict__ block_hot, uint32_t* __restrict__ zero_words, size_t zero_n,
-    const int32_t* __restrict__ active_count, EgsPrologueArgs place, EgsObjRot rot) {
+    const int32_t* __restrict__ active_count, EgsPrologueArgs place, EgsObjRot rot, EgsMotion mot) {
     __shared__ uint32_t wsum[4], whot[4];
     if (PLACE) {
         __shared__ EgsOrderLds order_lds;
@@ -268,8 +274,8 @@ __global__ __launch_bounds__(256) void k_preprocess(
     const int live = active_count ? min(P, max(*active_count, 0)) : P;
     if (i >= live && i < P) { radii[i] = 0; tiles_touched[i] = 0; visible[i] = 0; }
     bool hot = false;
-    if (i < live) my_tiles = preprocess_one(i, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H,
-                                         tanfovx, tanfovy, radii, rec, rect_out, tiles_touched, clamped_out, visible, rot, hot);
+    if (i < live) my_tiles = preprocess_one<MOTION>(i, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H,
+                                         tanfovx, tanfovy, radii, rec, rect_out, tiles_touched, clamped_out, visible, rot, mot, hot);
     hot = hot && my_tiles != 0;
     const uint64_t hot_wave = __ballot(hot);
     // per-block instance count; the host adds the block sums to get R (no contended atomic, deterministic)
@@ -310,8 +316,8 @@ struct EgsCountArgs { int gpr, gx, n_tiles; uint32_t nblocks; int cull, use_map;
 extern __shared__ __attribute__((aligned(16))) uint32_t pc_dyn_lds[];
 // ONE_ROUND: every workgroup's groups fit one round (no loop: what the projection loads is dead before the walk starts -- inside a loop the
 // camera matrices and the argument pointers stayed live through it and the kernel needed 105 VGPRs; 64 keep the 16-wave workgroups two per CU).
-template <bool PLACE, bool ONE_ROUND>
-__global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_preprocess_count(EgsPreArgs a, EgsCountArgs c, EgsPrologueArgs place, EgsObjRot rot) {
+template <bool PLACE, bool ONE_ROUND, bool MOTION>
+__global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_preprocess_count(EgsPreArgs a, EgsCountArgs c, EgsPrologueArgs place, EgsObjRot rot, EgsMotion mot) {
     __shared__ uint32_t wsum[EGS_BIN_WAVES], whot[EGS_BIN_WAVES];
     if (PLACE) {
         if (blockIdx.x < EGS_XCDS) { egs_order_band<EGS_BIN_THREADS>(place, (int)blockIdx.x, *reinterpret_cast<EgsOrderLds*>(pc_dyn_lds)); return; }
@@ -338,8 +344,8 @@ __global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu
             const float* V = a.V; const float* PM = a.PM; const float* campos = a.campos;
             if (!ONE_ROUND) asm volatile("" : "+s"(V), "+s"(PM), "+s"(campos));     // (re-read every round instead of held in 35 scalar registers through the walk)
             if (i >= 0 && i < live)
-                my_tiles = preprocess_one(i, a.D, a.M, a.means3D, a.shs, a.colors, a.opac, a.scales, a.mod, a.rots, a.cov3D_in, a.act, V, PM, campos,
-                                          a.W, a.H, a.tanfovx, a.tanfovy, a.radii, a.rec, a.rect_out, a.tiles_touched, a.clamped_out, a.visible, rot, hot, &o);
+                my_tiles = preprocess_one<MOTION>(i, a.D, a.M, a.means3D, a.shs, a.colors, a.opac, a.scales, a.mod, a.rots, a.cov3D_in, a.act, V, PM, campos,
+                                          a.W, a.H, a.tanfovx, a.tanfovy, a.radii, a.rec, a.rect_out, a.tiles_touched, a.clamped_out, a.visible, rot, mot, hot, &o);
             hot = hot && my_tiles != 0;
             hot_wave = __ballot(hot);
             if (my_tiles == 0) { o.rect = make_uint2(0u, 0u); o.r0 = o.r1 = o.r2 = make_float4(0.f, 0.f, 0.f, 0.f); }      // (culled: preprocess_one left `o` alone)
@@ -383,7 +389,9 @@ __global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu
 #define ST_SCALES 1024
 #define ST_ROTS 1792
 #define ST_SH 2816
-template <bool SINK>
+// MOT (object motion, object_motion.h): 0 none; 1 the row is placed, its gradient stays dL/dp' (the spherical-harmonics launch finishes it);
+// 2 the gradient is finished here: dL/dp = A^T dL/dp', the row's pose terms go to red[0..12).  MOT != 0: a rotated row's dL/dM terms go to red[12..21).
+template <bool SINK, int MOT>
 __device__ __forceinline__ void pp_bwd_one(
     const int i, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ scales, float mod, const float* __restrict__ rots, const float* __restrict__ cov3D_in, int act,
@@ -393,7 +401,7 @@ __device__ __forceinline__ void pp_bwd_one(
     float* __restrict__ dopac, float* __restrict__ dmeans3D, float* __restrict__ dcov3D, float* __restrict__ dsh,
     float* __restrict__ dscales, float* __restrict__ drots,
     float* __restrict__ stat_grad_accum, float* __restrict__ stat_denom, float* __restrict__ stat_max_radii,
-    const uint32_t* __restrict__ skip_flag, float* __restrict__ stage, const unsigned fused, const EgsObjRot rot) {
+    const uint32_t* __restrict__ skip_flag, float* __restrict__ stage, const unsigned fused, const EgsObjRot rot, const EgsMotion mot, float* red) {
     // SINK: the gradients of the leaves in `fused` (bit = EGS_SINK_*) also go to `stage` (LDS), from where the workgroup applies
     // Adam to its 256 rows; their dX arrays may then be NULL (nothing written)
     const unsigned tid = threadIdx.x;
@@ -460,7 +468,11 @@ __device__ __forceinline__ void pp_bwd_one(
         }
         return;
     }
-    const float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    [[maybe_unused]] const float p0[3] = { p[0], p[1], p[2] };       // the canonical position (pose terms)
+    if constexpr (MOT != 0) {
+        if (!mot.moved || mot.moved[i]) egs_motion_point(mot.A, p0, p);       // (visible: a live row)
+    }
     float c6[6], s[3] = { 0.f, 0.f, 0.f }, q[4] = { 1.f, 0.f, 0.f, 0.f }, qinv = 1.f;
     if (cov3D_in) {
 #pragma unroll
@@ -585,6 +597,13 @@ __device__ __forceinline__ void pp_bwd_one(
         const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
         gmean[0] += (gdir[0] - x * dot) * inv; gmean[1] += (gdir[1] - y * dot) * inv; gmean[2] += (gdir[2] - z * dot) * inv;
     }
+    if constexpr (MOT == 2) {                                          // gmean is dL/dp', complete: chain it through the placement
+        if (!mot.moved || mot.moved[i]) {
+            if (mot.pose_partial) egs_motion_pose_terms(gmean, p0, red);
+            const float gp[3] = { gmean[0], gmean[1], gmean[2] };
+            egs_motion_point_backward(mot.A, gp, gmean);
+        }
+    }
     if (dmeans3D) { dmeans3D[3 * i] = gmean[0]; dmeans3D[3 * i + 1] = gmean[1]; dmeans3D[3 * i + 2] = gmean[2]; }
     if (SINK && (fused & (1u << EGS_SINK_MEANS3D))) { stage[ST_MEANS + 3 * tid] = gmean[0]; stage[ST_MEANS + 3 * tid + 1] = gmean[1]; stage[ST_MEANS + 3 * tid + 2] = gmean[2]; }
 
@@ -618,6 +637,20 @@ __device__ __forceinline__ void pp_bwd_one(
 #pragma unroll
             for (int k = 0; k < 3; k++)
                 gL[3 * a + k] = (Gs[3 * a] * L[k] + Gs[3 * a + 1] * L[3 + k] + Gs[3 * a + 2] * L[6 + k]) * (2.f * mult);
+        if constexpr (MOT != 0) {
+            if (moved && mot.dM_partial) {                            // dL/dM = gL L0^T, operation for operation k_cov3d_backward's gM (the row-0 multiplier is in gL)
+                float L0[9];
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int k = 0; k < 3; k++) L0[3 * a + k] = Rm[3 * a + k] * sc[k];
+#pragma unroll
+                for (int a = 0; a < 3; a++)
+#pragma unroll
+                    for (int b = 0; b < 3; b++)
+                        red[EGS_MOTION_POSE_SUMS + 3 * a + b] = gL[3 * a] * L0[3 * b] + gL[3 * a + 1] * L0[3 * b + 1] + gL[3 * a + 2] * L0[3 * b + 2];
+            }
+        }
         if (moved) {
             float g0[9];
 #pragma unroll
@@ -658,7 +691,8 @@ __device__ __forceinline__ void pp_bwd_one(
 // rows 256 b .. 256 b + 255 of a [P, k] array are one contiguous span).  The gradients never reach HBM and the parameters are not
 // read a second time by another launch: 16 B in + 12 B out per element become 12 + 12, and the step has one launch less.
 // 896 float4 tasks per workgroup (64 x (3 + 1 + 3 + 4 + 3)), task -> leaf boundaries fall on wave boundaries.
-template <bool SINK>
+// MOT: see pp_bwd_one.  The pose sums are a workgroup-uniform branch on the scratch pointers: a constant pose (no gradient asked for) pays no shuffle.
+template <bool SINK, int MOT>
 __global__ __launch_bounds__(256) void k_preprocess_backward(
     int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ scales, float mod, const float* __restrict__ rots, const float* __restrict__ cov3D_in, int act,
@@ -668,7 +702,7 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(
     float* __restrict__ dopac, float* __restrict__ dmeans3D, float* __restrict__ dcov3D, float* __restrict__ dsh,
     float* __restrict__ dscales, float* __restrict__ drots,
     float* __restrict__ stat_grad_accum, float* __restrict__ stat_denom, float* __restrict__ stat_max_radii,
-    const uint32_t* __restrict__ skip_flag, EgsSink sink, EgsObjRot rot) {
+    const uint32_t* __restrict__ skip_flag, EgsSink sink, EgsObjRot rot, EgsMotion mot) {
     __shared__ __attribute__((aligned(16))) float stage[SINK ? 4 * EGS_SINK_TASKS : 4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned fused = 0;
@@ -676,10 +710,20 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(
 #pragma unroll
         for (int l = 0; l < EGS_SINK_PP_LEAVES; l++) fused |= sink.leaf[l].p ? (1u << l) : 0u;
     }
+    float red[MOT != 0 ? EGS_MOTION_SUMS : 1];
+    if constexpr (MOT != 0) {
+#pragma unroll
+        for (int k = 0; k < EGS_MOTION_SUMS; k++) red[k] = 0.f;
+    }
     if (i < P)
-        pp_bwd_one<SINK>(i, D, M, means3D, shs, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H, tanfovx, tanfovy, radii, clamped, rec,
+        pp_bwd_one<SINK, MOT>(i, D, M, means3D, shs, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H, tanfovx, tanfovy, radii, clamped, rec,
                          grad_acc, grad_acc + (size_t)P * EGS_GRAD_STRIDE, egs_hot_slots((size_t)P), dmeans2D, dcolors, dopac, dmeans3D, dcov3D, dsh, dscales, drots, stat_grad_accum, stat_denom,
-                         stat_max_radii, skip_flag, stage, fused, rot);
+                         stat_max_radii, skip_flag, stage, fused, rot, mot, red);
+    if constexpr (MOT != 0) {
+        __shared__ float wsum_p[4][EGS_MOTION_POSE_SUMS], wsum_m[4][EGS_MOTION_ROT_SUMS];
+        if (MOT == 2 && mot.pose_partial) egs_motion_block_sum<EGS_MOTION_POSE_SUMS>(red, wsum_p, mot.pose_partial + (size_t)blockIdx.x * EGS_MOTION_POSE_SUMS);
+        if (mot.dM_partial) egs_motion_block_sum<EGS_MOTION_ROT_SUMS>(red + EGS_MOTION_POSE_SUMS, wsum_m, mot.dM_partial + (size_t)blockIdx.x * EGS_MOTION_ROT_SUMS);
+    }
     if (!SINK) return;
     __syncthreads();
     if (sink.skip && *sink.skip) return;                            // the frame overflowed its instance capacity: no step (and none was counted)
@@ -815,9 +859,10 @@ __device__ __forceinline__ void sh_store_rows(const float* tile, int ld, int col
 extern __shared__ __attribute__((aligned(16))) float sh_tile[];
 
 // sh_rest == nullptr: sh_a is [P, M, 3]; otherwise sh_a is the DC block [P, 1, 3] and sh_rest [P, M - 1, 3].
+template <bool MOTION>
 __global__ __launch_bounds__(64) void k_sh_forward(int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ campos,
                                                    const float* __restrict__ sh_a, const float* __restrict__ sh_rest,
-                                                   const uint8_t* __restrict__ visible, float4* __restrict__ rec, uint8_t* __restrict__ clamped) {
+                                                   const uint8_t* __restrict__ visible, float4* __restrict__ rec, uint8_t* __restrict__ clamped, EgsMotion mot) {
     const unsigned lane = threadIdx.x;
     const int i0 = blockIdx.x * 64, i = i0 + (int)lane;
     const bool vis = i < P && visible[i] != 0;
@@ -832,7 +877,10 @@ __global__ __launch_bounds__(64) void k_sh_forward(int P, int D, int M, const fl
     }
     __syncthreads();                                                   // one wave: orders the LDS writes before the row reads
     if (!vis) return;
-    const float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+    if constexpr (MOTION) {
+        if (!mot.moved || mot.moved[i]) { const float p0[3] = { p[0], p[1], p[2] }; egs_motion_point(mot.A, p0, p); }   // (visible: a live row)
+    }
     float dir[3] = { p[0] - campos[0], p[1] - campos[1], p[2] - campos[2] };
     const float inv = 1.f / sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
     dir[0] *= inv; dir[1] *= inv; dir[2] *= inv;
@@ -849,11 +897,14 @@ __global__ __launch_bounds__(64) void k_sh_forward(int P, int D, int M, const fl
     r[6] = rgb[0]; r[7] = rgb[1]; r[8] = rgb[2];
 }
 
+// MOTION (object_motion.h): the row is placed; the positions' gradient is complete here, so this launch chains it through the placement
+// (dL/dp = A^T dL/dp') and writes the wave's line of the pose sums (one wave per workgroup: the six shuffle levels, no LDS).
+template <bool MOTION>
 __global__ __launch_bounds__(64) void k_sh_backward(int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ campos,
                                                     const float* __restrict__ sh_a, const float* __restrict__ sh_rest,
                                                     const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,
                                                     const float* __restrict__ dcolors, float* __restrict__ dsh_a, float* __restrict__ dsh_rest,
-                                                    float* __restrict__ dmeans3D) {
+                                                    float* __restrict__ dmeans3D, EgsMotion mot) {
     const unsigned lane = threadIdx.x;
     const int i0 = blockIdx.x * 64, i = i0 + (int)lane;
     const bool vis = i < P && radii[i] > 0;
@@ -865,8 +916,19 @@ __global__ __launch_bounds__(64) void k_sh_backward(int P, int D, int M, const f
         else sh_load_rows(sh_tile, ld, 0, sh_a, rw, i0, nvalid, vmask, need, lane);
         __syncthreads();
     }
+    float red[MOTION ? EGS_MOTION_POSE_SUMS : 1];
+    if constexpr (MOTION) {
+#pragma unroll
+        for (int k = 0; k < EGS_MOTION_POSE_SUMS; k++) red[k] = 0.f;
+    }
     if (vis) {
-        const float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+        float p[3] = { means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2] };
+        [[maybe_unused]] const float p0[3] = { p[0], p[1], p[2] };
+        [[maybe_unused]] bool row_moved = false;
+        if constexpr (MOTION) {
+            row_moved = !mot.moved || mot.moved[i];
+            if (row_moved) egs_motion_point(mot.A, p0, p);
+        }
         const float d0[3] = { p[0] - campos[0], p[1] - campos[1], p[2] - campos[2] };
         const float inv = 1.f / sqrtf(d0[0] * d0[0] + d0[1] * d0[1] + d0[2] * d0[2]);
         const float x = d0[0] * inv, y = d0[1] * inv, z = d0[2] * inv;
@@ -915,13 +977,28 @@ __global__ __launch_bounds__(64) void k_sh_backward(int P, int D, int M, const f
             for (int k = (D + 1) * (D + 1); k < M; k++) SH(k) = 0.f;      // coefficients above the active degree
 #undef SH
         }
-        if (D > 0) {
+        if constexpr (MOTION) {
+            float gm[3] = { dmeans3D[3 * i], dmeans3D[3 * i + 1], dmeans3D[3 * i + 2] };
+            if (D > 0) {
+                const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
+                gm[0] += (gdir[0] - x * dot) * inv; gm[1] += (gdir[1] - y * dot) * inv; gm[2] += (gdir[2] - z * dot) * inv;
+            }
+            if (row_moved) {
+                if (mot.pose_partial) egs_motion_pose_terms(gm, p0, red);
+                const float gp[3] = { gm[0], gm[1], gm[2] };
+                egs_motion_point_backward(mot.A, gp, gm);
+            }
+            dmeans3D[3 * i] = gm[0]; dmeans3D[3 * i + 1] = gm[1]; dmeans3D[3 * i + 2] = gm[2];
+        } else if (D > 0) {
             const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
             dmeans3D[3 * i] += (gdir[0] - x * dot) * inv; dmeans3D[3 * i + 1] += (gdir[1] - y * dot) * inv;
             dmeans3D[3 * i + 2] += (gdir[2] - z * dot) * inv;
         }
     } else {
         for (int k = 0; k < rw; k++) row[k] = 0.f;
+    }
+    if constexpr (MOTION) {
+        if (mot.pose_partial) egs_motion_wave_line<EGS_MOTION_POSE_SUMS>(red, mot.pose_partial + (size_t)blockIdx.x * EGS_MOTION_POSE_SUMS);
     }
     __syncthreads();
     if (dsh_rest) {
@@ -1054,16 +1131,19 @@ __device__ __forceinline__ void sh16_stage_out(const float* tile, float* __restr
     }
 }
 
-template <int MODE>
+template <int MODE, bool MOTION>
 __global__ __launch_bounds__(64) void k_sh16_forward(int P, int D, const float* __restrict__ means3D, const float* __restrict__ campos,
                                                      const float* __restrict__ sh_a, const float* __restrict__ sh_rest,
-                                                     const uint8_t* __restrict__ visible, float4* __restrict__ rec, uint8_t* __restrict__ clamped) {
+                                                     const uint8_t* __restrict__ visible, float4* __restrict__ rec, uint8_t* __restrict__ clamped, EgsMotion mot) {
     const unsigned lane = threadIdx.x;
     const int i0 = blockIdx.x * 64, i = i0 + (int)lane;
     const bool inb = i < P;
     const bool vis = inb && visible[i] != 0;
     float p[3] = { 0.f, 0.f, 1.f };
     if (inb) { p[0] = means3D[3 * i]; p[1] = means3D[3 * i + 1]; p[2] = means3D[3 * i + 2]; }   // (in flight together with the rows)
+    if constexpr (MOTION) {
+        if (vis && (!mot.moved || mot.moved[i])) { const float p0[3] = { p[0], p[1], p[2] }; egs_motion_point(mot.A, p0, p); }
+    }
     const uint64_t vmask = __ballot(vis);
     if (!vmask) return;
     const int need = 3 * (D + 1) * (D + 1);
@@ -1121,12 +1201,13 @@ __device__ __forceinline__ void sh16_adam_span(const float* t, const EgsSinkLeaf
 
 // SINK (split arrays only; include/egs_raster.h egs_backward_adam): the launch also takes the Adam step of the leaves whose gradient it
 // finishes -- features_dc, features_rest and, because the view-direction term lands here, the positions -- for its 64 rows.
-template <int MODE, bool SINK>
+// MOTION: as in k_sh_backward -- and the Adam step of the positions, when this launch takes it, steps with dL/dp = A^T dL/dp'.
+template <int MODE, bool SINK, bool MOTION>
 __global__ __launch_bounds__(64) void k_sh16_backward(int P, int D, const float* __restrict__ means3D, const float* __restrict__ campos,
                                                       const float* __restrict__ sh_a, const float* __restrict__ sh_rest,
                                                       const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,
                                                       const float* __restrict__ dcolors, float* __restrict__ dsh_a, float* __restrict__ dsh_rest,
-                                                      float* __restrict__ dmeans3D, EgsSink sink) {
+                                                      float* __restrict__ dmeans3D, EgsSink sink, EgsMotion mot) {
     const unsigned lane = threadIdx.x;
     const int i0 = blockIdx.x * 64, i = i0 + (int)lane;
     const bool inb = i < P;
@@ -1137,7 +1218,16 @@ __global__ __launch_bounds__(64) void k_sh16_backward(int P, int D, const float*
         p[0] = means3D[3 * i]; p[1] = means3D[3 * i + 1]; p[2] = means3D[3 * i + 2];
         dc[0] = dcolors[3 * i]; dc[1] = dcolors[3 * i + 1]; dc[2] = dcolors[3 * i + 2];
         cl = clamped[i] & EGS_CLAMP_MASK;
-        if (D > 0 || (SINK && sink.leaf[EGS_SINK_MEANS3D].p)) { gm[0] = dmeans3D[3 * i]; gm[1] = dmeans3D[3 * i + 1]; gm[2] = dmeans3D[3 * i + 2]; }
+        if (MOTION || D > 0 || (SINK && sink.leaf[EGS_SINK_MEANS3D].p)) { gm[0] = dmeans3D[3 * i]; gm[1] = dmeans3D[3 * i + 1]; gm[2] = dmeans3D[3 * i + 2]; }
+    }
+    [[maybe_unused]] const float p0[3] = { p[0], p[1], p[2] };
+    [[maybe_unused]] bool row_moved = false;
+    float red[MOTION ? EGS_MOTION_POSE_SUMS : 1];
+    if constexpr (MOTION) {
+#pragma unroll
+        for (int k = 0; k < EGS_MOTION_POSE_SUMS; k++) red[k] = 0.f;
+        row_moved = vis && (!mot.moved || mot.moved[i]);
+        if (row_moved) egs_motion_point(mot.A, p0, p);
     }
     const uint64_t vmask = __ballot(vis);
     const int nvalid = min(64, P - i0), need = 3 * (D + 1) * (D + 1);
@@ -1195,8 +1285,19 @@ __global__ __launch_bounds__(64) void k_sh16_backward(int P, int D, const float*
         if (D > 0) {
             const float dot = x * gdir[0] + y * gdir[1] + z * gdir[2];
             gm[0] += (gdir[0] - x * dot) * inv; gm[1] += (gdir[1] - y * dot) * inv; gm[2] += (gdir[2] - z * dot) * inv;
-            dmeans3D[3 * i] = gm[0]; dmeans3D[3 * i + 1] = gm[1]; dmeans3D[3 * i + 2] = gm[2];
+            if constexpr (!MOTION) { dmeans3D[3 * i] = gm[0]; dmeans3D[3 * i + 1] = gm[1]; dmeans3D[3 * i + 2] = gm[2]; }
         }
+        if constexpr (MOTION) {
+            if (row_moved) {
+                if (mot.pose_partial) egs_motion_pose_terms(gm, p0, red);
+                const float gp[3] = { gm[0], gm[1], gm[2] };
+                egs_motion_point_backward(mot.A, gp, gm);
+            }
+            if (row_moved || D > 0) { dmeans3D[3 * i] = gm[0]; dmeans3D[3 * i + 1] = gm[1]; dmeans3D[3 * i + 2] = gm[2]; }
+        }
+    }
+    if constexpr (MOTION) {
+        if (mot.pose_partial) egs_motion_wave_line<EGS_MOTION_POSE_SUMS>(red, mot.pose_partial + (size_t)blockIdx.x * EGS_MOTION_POSE_SUMS);
     }
     sh16_regs_to_row<MODE>(sh_tile, lane, g);                          // (a lane touches only its own row: no barrier since the reads above)
     __syncthreads();
@@ -1262,7 +1363,7 @@ hipError_t egs_launch_zero_f4(float4* p, size_t n4, hipStream_t s) {
 hipError_t egs_launch_preprocess(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
                                  const float* opac, const float* scales, float mod, const float* rots, int act,
                                  const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
-                                 const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, hipStream_t s) {
+                                 const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, hipStream_t s) {
     if (P == 0) return hipSuccess;
     if (!zero_words) zero_n = 0;
     EgsPrologueArgs pa = {};
@@ -1271,9 +1372,11 @@ hipError_t egs_launch_preprocess(int P, int D, int M, const float* means3D, cons
     if (place) {
         pa.n_tiles = ((cam.W + EGS_TILE - 1) / EGS_TILE) * ((cam.H + EGS_TILE - 1) / EGS_TILE);
         pa.quad_work = place->fwd_cost; pa.tile_order = place->fwd_order;
-        hipLaunchKernelGGL(k_preprocess<true>, dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, pa, rot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<true, true>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<true, false>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
     } else {
-        hipLaunchKernelGGL(k_preprocess<false>, dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, pa, rot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<false, true>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<false, false>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
     }
 #undef PP_ARGS
     return hipGetLastError();
@@ -1291,7 +1394,7 @@ bool egs_can_fuse_count(int P, int W, int H, int cull) {
 hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
                                        const float* opac, const float* scales, float mod, const float* rots, int act,
                                        const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
-                                       const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, int cull, hipStream_t s) {
+                                       const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, int cull, hipStream_t s) {
     const EgsBinGeometry q = egs_bin_geometry(P, cam.W, cam.H, cull);
     EgsPreArgs a = { P, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.tanfovx, cam.tanfovy,
                      radii, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot, active_count };
@@ -1300,14 +1403,19 @@ hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D
     const unsigned grid = ((q.nblocks + 7) / 8) * 8;
     const bool one = bin_groups_per_block((unsigned)P, q.nblocks) <= (unsigned)q.gpr;
     if (place) { pa.n_tiles = q.n_tiles; pa.quad_work = place->fwd_cost; pa.tile_order = place->fwd_order; }
-#define PC_LAUNCH(PL, ONE) do {                                                                                                       \
+#define PC_LAUNCH(PL, ONE, MO) do {                                                                                                       \
         if (q.lds > 64 * 1024) {                                                                                                      \
-            hipError_t e = hipFuncSetAttribute((const void*)k_preprocess_count<PL, ONE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds); \
+            hipError_t e = hipFuncSetAttribute((const void*)k_preprocess_count<PL, ONE, MO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds); \
             if (e != hipSuccess) return e;                                                                                            \
         }                                                                                                                             \
-        hipLaunchKernelGGL((k_preprocess_count<PL, ONE>), dim3(grid + (PL ? EGS_XCDS : 0)), dim3(EGS_BIN_THREADS), q.lds, s, a, c, pa, rot); } while (0)
-    if (place) { if (one) PC_LAUNCH(true, true); else PC_LAUNCH(true, false); }
-    else { if (one) PC_LAUNCH(false, true); else PC_LAUNCH(false, false); }
+        hipLaunchKernelGGL((k_preprocess_count<PL, ONE, MO>), dim3(grid + (PL ? EGS_XCDS : 0)), dim3(EGS_BIN_THREADS), q.lds, s, a, c, pa, rot, mot); } while (0)
+    if (mot.A) {
+        if (place) { if (one) PC_LAUNCH(true, true, true); else PC_LAUNCH(true, false, true); }
+        else { if (one) PC_LAUNCH(false, true, true); else PC_LAUNCH(false, false, true); }
+    } else {
+        if (place) { if (one) PC_LAUNCH(true, true, false); else PC_LAUNCH(true, false, false); }
+        else { if (one) PC_LAUNCH(false, true, false); else PC_LAUNCH(false, false, false); }
+    }
 #undef PC_LAUNCH
     return hipGetLastError();
 }
@@ -1318,15 +1426,24 @@ hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* mean
                                           int colors_given, float* dmeans2D, float* dcolors, float* dopac,
                                           float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
                                           float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
-                                          const EgsSink* sink, EgsObjRot rot, hipStream_t s) {
+                                          const EgsSink* sink, EgsObjRot rot, EgsMotion mot, int motion_finished_later, hipStream_t s) {
     if (P == 0) return hipSuccess;
     EgsSink none = {};
 #define PPB_ARGS P, D, M, means3D, colors_given ? nullptr : shs, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, \
                  cam.H, cam.tanfovx, cam.tanfovy, radii, g.clamped, g.rec, grad_acc, dmeans2D, dcolors, dopac, dmeans3D, \
                  dcov3D, colors_given ? nullptr : dsh, cov3D ? nullptr : dscales, cov3D ? nullptr : drots, \
                  stat_grad_accum, stat_denom, stat_max_radii, skip_flag
-    if (sink) hipLaunchKernelGGL(k_preprocess_backward<true>, dim3((P + 255) / 256), dim3(256), 0, s, PPB_ARGS, *sink, rot);
-    else hipLaunchKernelGGL(k_preprocess_backward<false>, dim3((P + 255) / 256), dim3(256), 0, s, PPB_ARGS, none, rot);
+    const dim3 grid((P + 255) / 256), block(256);
+    if (!mot.A) {
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 0>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 0>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+    } else if (motion_finished_later) {
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 1>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 1>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+    } else {
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 2>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 2>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+    }
 #undef PPB_ARGS
     return hipGetLastError();
 }
@@ -1339,42 +1456,55 @@ static bool sh16_fast(int M, const void* a, const void* b, const void* c, const 
 }
 
 hipError_t egs_launch_sh_forward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                 EgsGeomPtrs g, hipStream_t s) {
+                                 EgsGeomPtrs g, EgsMotion mot, hipStream_t s) {
     if (P == 0) return hipSuccess;
     const dim3 grid((P + 63) / 64), block(64);
+#define SHF_ARGS means3D, cam.campos, sh_a, sh_rest, g.visible, g.rec, g.clamped, mot
     if (sh16_fast(M, sh_a, sh_rest, nullptr, nullptr)) {
-        if (sh_rest) hipLaunchKernelGGL(k_sh16_forward<SH16_SPLIT>, grid, block, (SH16_REST_WORDS + 192) * sizeof(float), s, P, D, means3D, cam.campos,
-                                        sh_a, sh_rest, g.visible, g.rec, g.clamped);
-        else hipLaunchKernelGGL(k_sh16_forward<SH16_CAT>, grid, block, 64 * 13 * sizeof(float4), s, P, D, means3D, cam.campos, sh_a, sh_rest,
-                                g.visible, g.rec, g.clamped);
+        const size_t lds16 = sh_rest ? (SH16_REST_WORDS + 192) * sizeof(float) : 64 * 13 * sizeof(float4);
+        if (sh_rest) {
+            if (mot.A) hipLaunchKernelGGL((k_sh16_forward<SH16_SPLIT, true>), grid, block, lds16, s, P, D, SHF_ARGS);
+            else hipLaunchKernelGGL((k_sh16_forward<SH16_SPLIT, false>), grid, block, lds16, s, P, D, SHF_ARGS);
+        } else {
+            if (mot.A) hipLaunchKernelGGL((k_sh16_forward<SH16_CAT, true>), grid, block, lds16, s, P, D, SHF_ARGS);
+            else hipLaunchKernelGGL((k_sh16_forward<SH16_CAT, false>), grid, block, lds16, s, P, D, SHF_ARGS);
+        }
         return hipGetLastError();
     }
     const size_t lds = (size_t)64 * (3 * M + 1) * sizeof(float);
-    hipLaunchKernelGGL(k_sh_forward, grid, block, lds, s, P, D, M, means3D, cam.campos, sh_a, sh_rest, g.visible, g.rec, g.clamped);
+    if (mot.A) hipLaunchKernelGGL(k_sh_forward<true>, grid, block, lds, s, P, D, M, SHF_ARGS);
+    else hipLaunchKernelGGL(k_sh_forward<false>, grid, block, lds, s, P, D, M, SHF_ARGS);
+#undef SHF_ARGS
     return hipGetLastError();
 }
 
 hipError_t egs_launch_sh_backward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
                                   const int32_t* radii, EgsGeomPtrs g, const float* dcolors, float* dsh_a, float* dsh_rest,
-                                  float* dmeans3D, const EgsSink* sink, hipStream_t s) {
+                                  float* dmeans3D, const EgsSink* sink, EgsMotion mot, hipStream_t s) {
     if (P == 0) return hipSuccess;
     const dim3 grid((P + 63) / 64), block(64);
     EgsSink none = {};
+#define SHB_ARGS means3D, cam.campos, sh_a, sh_rest, radii, g.clamped, dcolors, dsh_a, dsh_rest, dmeans3D
+    const size_t lds_split = (SH16_REST_WORDS + 192) * sizeof(float), lds_cat = 64 * 13 * sizeof(float4);
     if (sink) {                                                       // (the caller checked egs_sh_backward_can_sink)
-        hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, true>), grid, block, (SH16_REST_WORDS + 192) * sizeof(float), s, P, D, means3D, cam.campos,
-                           sh_a, sh_rest, radii, g.clamped, dcolors, dsh_a, dsh_rest, dmeans3D, *sink);
+        if (mot.A) hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, true, true>), grid, block, lds_split, s, P, D, SHB_ARGS, *sink, mot);
+        else hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, true, false>), grid, block, lds_split, s, P, D, SHB_ARGS, *sink, mot);
         return hipGetLastError();
     }
     if (sh16_fast(M, sh_a, sh_rest, dsh_a, dsh_rest)) {
-        if (sh_rest) hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, false>), grid, block, (SH16_REST_WORDS + 192) * sizeof(float), s, P, D, means3D, cam.campos,
-                                        sh_a, sh_rest, radii, g.clamped, dcolors, dsh_a, dsh_rest, dmeans3D, none);
-        else hipLaunchKernelGGL((k_sh16_backward<SH16_CAT, false>), grid, block, 64 * 13 * sizeof(float4), s, P, D, means3D, cam.campos, sh_a, sh_rest,
-                                radii, g.clamped, dcolors, dsh_a, dsh_rest, dmeans3D, none);
+        if (sh_rest) {
+            if (mot.A) hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, false, true>), grid, block, lds_split, s, P, D, SHB_ARGS, none, mot);
+            else hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, false, false>), grid, block, lds_split, s, P, D, SHB_ARGS, none, mot);
+        } else {
+            if (mot.A) hipLaunchKernelGGL((k_sh16_backward<SH16_CAT, false, true>), grid, block, lds_cat, s, P, D, SHB_ARGS, none, mot);
+            else hipLaunchKernelGGL((k_sh16_backward<SH16_CAT, false, false>), grid, block, lds_cat, s, P, D, SHB_ARGS, none, mot);
+        }
         return hipGetLastError();
     }
     const size_t lds = (size_t)64 * (3 * M + 1) * sizeof(float);
-    hipLaunchKernelGGL(k_sh_backward, grid, block, lds, s, P, D, M, means3D, cam.campos, sh_a, sh_rest, radii, g.clamped,
-                       dcolors, dsh_a, dsh_rest, dmeans3D);
+    if (mot.A) hipLaunchKernelGGL(k_sh_backward<true>, grid, block, lds, s, P, D, M, SHB_ARGS, mot);
+    else hipLaunchKernelGGL(k_sh_backward<false>, grid, block, lds, s, P, D, M, SHB_ARGS, mot);
+#undef SHB_ARGS
     return hipGetLastError();
 }
 

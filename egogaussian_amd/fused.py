@@ -138,6 +138,50 @@ def rotated_covariance_from_scaling_rotation(scaling, scaling_modifier, rotation
     return _Cov3D.apply(scaling, rotation, M, sel, scaling_modifier, mult, scaling_is_log, opacity_raw)
 
 
+class _MovePoints(torch.autograd.Function):
+    """xyz' = A xyz + b for the rows of `moved` (include/egs_raster.h egs_object_move_points / _backward)."""
+
+    @staticmethod
+    def forward(ctx, xyz, A12, moved, active_count):
+        L = _lib.load()
+        xyz, A = _need_hip(xyz, "xyz"), _need_hip(A12, "A12").reshape(12)
+        N, dev = xyz.shape[0], xyz.device
+        mv = None if moved is None else moved.reshape(-1).to(torch.uint8).contiguous()
+        if mv is not None and (mv.numel() != N or mv.device != dev):
+            raise RuntimeError("object_move_points: `moved` must hold one byte per row on the points' device")
+        out = torch.empty_like(xyz)
+        with _hip.device_ctx(dev):
+            _lib.check(L.egs_object_move_points(N, _p(xyz), _p(A), _p(mv), _p(active_count), _p(out), _stream(dev)))
+        ctx.save_for_backward(xyz, A, mv if mv is not None else torch.empty(0, device=dev))
+        ctx.has_mask, ctx.active_count, ctx.A_shape = mv is not None, active_count, A12.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.load()
+        xyz, A, mv = ctx.saved_tensors
+        mv = mv if ctx.has_mask else None
+        N, dev = xyz.shape[0], xyz.device
+        g = g.float().contiguous()
+        dxyz = torch.empty_like(xyz) if ctx.needs_input_grad[0] else None
+        dA = torch.empty(12, device=dev) if ctx.needs_input_grad[1] else None
+        scratch = torch.empty(max(int(L.egs_object_motion_scratch_bytes(N)), 4), device=dev, dtype=torch.uint8) if dA is not None else None
+        if dxyz is not None or dA is not None:
+            with _hip.device_ctx(dev):
+                _lib.check(L.egs_object_move_points_backward(N, _p(xyz), _p(A), _p(mv), _p(ctx.active_count), _p(g), _p(dxyz), _p(dA), _p(scratch),
+                                                             _stream(dev)))
+        return dxyz, (None if dA is None else dA.view(ctx.A_shape)), None, None
+
+
+def object_move_points(xyz, A12, moved=None, active_count=None):
+    """The placed positions [N,3] as a tensor: p' = A p + b for the rows of `moved` (the exact mask, None = every row), a bit-for-bit copy
+    for the others and for rows at or beyond *active_count (int32[1] device tensor).  One launch each way instead of the reference's
+    cat / matmul / slice / where (apply_T_xyz, gaussian_model.py:939-986); differentiable w.r.t. xyz and A12 (motion.ObjectMotion.compose),
+    the pose gradient being a deterministic reduction.  For evaluation, the export of a posed frame and comparisons -- a render takes the
+    motion as an input instead (renderer.render(object_motion=...)).  HIP tensors only; motion.move_points is the tensor expression."""
+    return _MovePoints.apply(xyz, A12, moved, active_count)
+
+
 class _L1SSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, gt, lambda_dssim, gate, running_sum=None, defer_value=False, raster_node=None, lossgrad=False):

@@ -35,7 +35,7 @@ def pack_camera(cam):
     return torch.cat([cam.world_view_transform.reshape(-1), cam.full_proj_transform.reshape(-1), cam.camera_center.reshape(-1)]).float()
 
 
-def frame_layout(n_img, n_pix, dynamic=False, gated=False):
+def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False):
     """Float offsets of the segments of a packed frame (each starts on a 16-byte boundary): -> ({name: (begin, end)}, size)."""
     up4 = lambda x: (x + 3) & ~3
     off = {"gt": (0, n_img)}
@@ -43,21 +43,26 @@ def frame_layout(n_img, n_pix, dynamic=False, gated=False):
     off["cam"] = (end, end + 35); end = up4(end + 35)
     if dynamic:
         off["accum_R"] = (end, end + 9); end = up4(end + 9)
+    if motion:
+        off["accum_T"] = (end, end + 12); end = up4(end + 12)      # the object's accumulated pose as A12 = [A | b], row-major 3x4
     if gated:
         off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
     return off, end
 
 
-def pack_frame(cam, gt, accum_R=None, gate=None):
+def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None):
     """One resident tensor per training frame: the ground-truth image, the camera block and -- for a step captured with
     dynamic=True / gated=True -- the object's accumulated rotation (3x3) and the per-pixel gradient gate (1 - hand mask, [H,W]).
+    accum_T (a step captured with motion=True): the object's accumulated pose, 4x4 or 3x4 -- its first three rows travel as 12 floats.
     GraphedTrainStep(frame) then refreshes every static input of the captured step with ONE device copy."""
-    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None)
+    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None)
     f = torch.zeros(size, device=gt.device, dtype=torch.float32)
     f[off["gt"][0]:off["gt"][1]] = gt.reshape(-1)
     f[off["cam"][0]:off["cam"][1]] = pack_camera(cam).to(gt.device)
     if accum_R is not None:
         f[off["accum_R"][0]:off["accum_R"][1]] = accum_R.reshape(-1).to(gt.device)
+    if accum_T is not None:
+        f[off["accum_T"][0]:off["accum_T"][1]] = accum_T.reshape(-1, 4)[:3].reshape(-1).to(gt.device)
     if gate is not None:
         f[off["gate"][0]:off["gate"][1]] = gate.reshape(-1).to(gt.device)
     return f
@@ -93,11 +98,17 @@ class _StaticCamera:
 
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
-                 which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True):
+                 which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
+                 motion=False):
         """densify_stats: the captured step also keeps the per-iteration densification statistics (trainers/train_static.py:125-127:
                        max_radii2D, xyz_gradient_accum, denom) -- updated by the rasterizer's backward itself, no launch of their own.
         dynamic:       the `fine_all` call shape (/root/reference/trainers/fine_all.py:88-93): render(..., rot_cov=True,
                        accum_R=<static 3x3, refreshed per call>, which_object=which_object, during_training=False).
+        motion:        (with dynamic) the real `fine_all` step: the object's Gaussians are also PLACED by the frame's accumulated pose
+                       (<static 3x4 accum_T, refreshed per call like accum_R>) inside the rasterizer -- render(..., object_motion=) --
+                       instead of by apply_trans_rot_new / reverse_trans_rot_new around the render (fine_all.py:88-116), which would
+                       re-seat `_xyz` every iteration and could not be captured.  The pose is a constant of the captured step; a
+                       trainable pose inside a captured step is not supported.
         gated:         the image gradient is multiplied by a per-pixel gate refreshed per call -- the reference's
                        `render_image.register_hook(lambda grad: grad * (1 - hand_mask))` (train_static.py:91, fine_all.py:94).
         check_every:   K > 0: every K calls read the overflow maximum (one host synchronisation) and re-capture with a larger
@@ -127,6 +138,9 @@ class GraphedTrainStep:
         self.pc, self.opt, self.bg, self.lam, self.pipe = pc, optimizer, bg, lambda_dssim, pipe
         self.densify_stats = densify_stats
         self.dynamic, self.which_object, self.gated = bool(dynamic), which_object, bool(gated)
+        self.motion = bool(motion)
+        if self.motion and not self.dynamic:
+            raise ValueError("GraphedTrainStep(motion=True) goes with dynamic=True (the pose's rotation turns the covariances)")
         self.render_kwargs = dict(render_kwargs or {})
         self.check_every = int(check_every)
         self.steps_per_replay = max(1, int(steps_per_replay))
@@ -138,12 +152,19 @@ class GraphedTrainStep:
         self.skipped_frames_seen = 0      # overflow events noticed by check()
         self._calls = 0
 
+    def _dynamic_kwargs(self, f):
+        kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=self.which_object, during_training=False)
+        if self.motion:
+            from .motion import ComposedMotion
+            kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
+        return kw
+
     def _body(self, k=0):
         """One training iteration on static frame k."""
         f = self._slots[k]
         kw = dict(self.render_kwargs)
         if self.dynamic:
-            kw.update(rot_cov=True, accum_R=f["accum_R"], which_object=self.which_object, during_training=False)
+            kw.update(self._dynamic_kwargs(f))
         out = render(f["cam"], self.pc, self.pipe, self.bg, fused_densify_stats=self.densify_stats, guard=self.guard,
                      optimizer=self.opt if self.fuse_optimizer else None, color_only=True, **kw)      # (the loss reads the colour image only)
         # the loss value and the running sum are produced by the loss BACKWARD kernel (nothing reads them before): two launches less
@@ -154,9 +175,9 @@ class GraphedTrainStep:
         return loss.detach(), out
 
     def _frame_layout(self, gt):
-        return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated)
+        return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion)
 
-    def capture(self, cam, gt, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None):
+    def capture(self, cam, gt, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
         more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
@@ -172,12 +193,15 @@ class GraphedTrainStep:
             self._slots = []
             for k in range(self.steps_per_replay):
                 fr = self._frames[k]
-                slot = {"gt": fr[off["gt"][0]:off["gt"][1]].view(gt.shape), "accum_R": None, "gate": None}
+                slot = {"gt": fr[off["gt"][0]:off["gt"][1]].view(gt.shape), "accum_R": None, "gate": None, "accum_T": None}
                 slot["gt"].copy_(gt)
                 slot["cam"] = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
                 if self.dynamic:
                     slot["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
                     slot["accum_R"].copy_(torch.eye(3, device=dev) if accum_R is None else accum_R)
+                if self.motion:
+                    slot["accum_T"] = fr[off["accum_T"][0]:off["accum_T"][1]].view(3, 4)
+                    slot["accum_T"].copy_(torch.eye(4, device=dev)[:3] if accum_T is None else accum_T.reshape(-1, 4)[:3])
                 if self.gated:
                     slot["gate"] = fr[off["gate"][0]:off["gate"][1]].view(gt.shape[-2], gt.shape[-1])
                     slot["gate"].copy_(torch.ones(gt.shape[-2:], device=dev) if gate is None else gate)
@@ -185,6 +209,7 @@ class GraphedTrainStep:
             self._frame = self._frames[0]
             first = self._slots[0]                                   # (the single-iteration names)
             self.gt, self.cam, self.accum_R, self.gate = first["gt"], first["cam"], first["accum_R"], first["gate"]
+            self.accum_T = first["accum_T"]
         self._one = torch.ones((), device=dev)
         if getattr(self, "loss_sum", None) is None:
             self.loss_sum = torch.zeros((), device=dev)                  # sum of the losses of every iteration run through this object
@@ -197,7 +222,7 @@ class GraphedTrainStep:
             if capacity_cams:
                 kw = dict(self.render_kwargs)
                 if self.dynamic:
-                    kw.update(rot_cov=True, accum_R=self.accum_R, which_object=self.which_object, during_training=False)
+                    kw.update(self._dynamic_kwargs(self._slots[0]))
                 with torch.no_grad():
                     for c in capacity_cams:
                         render(c, self.pc, self.pipe, self.bg, **kw)
@@ -248,10 +273,12 @@ class GraphedTrainStep:
             slots2 = []
             for k in range(self.steps_per_replay):
                 fr, src = frames2[k], self._slots[k]
-                sl = {"gt": fr[off["gt"][0]:off["gt"][1]].view(src["gt"].shape), "accum_R": None, "gate": None}
+                sl = {"gt": fr[off["gt"][0]:off["gt"][1]].view(src["gt"].shape), "accum_R": None, "gate": None, "accum_T": None}
                 sl["cam"] = _StaticCamera(src["cam"], storage=fr[off["cam"][0]:off["cam"][1]])
                 if self.dynamic:
                     sl["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
+                if self.motion:
+                    sl["accum_T"] = fr[off["accum_T"][0]:off["accum_T"][1]].view(3, 4)
                 if self.gated:
                     sl["gate"] = fr[off["gate"][0]:off["gate"][1]].view(src["gt"].shape[-2], src["gt"].shape[-1])
                 slots2.append(sl)
@@ -292,7 +319,7 @@ class GraphedTrainStep:
         self._sets = None
         return self.capture(cam, gt, warmup=warmup, capacity_margin=capacity_margin, capacity_cams=capacity_cams)
 
-    def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None):
+    def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None, accum_T=None):
         """One training iteration (steps_per_replay of them): copy inputs in, replay.  Returns the (device, static) loss tensor of
         the last iteration (`self.losses` has all).  Either (camera, ground-truth image[, accum_R][, gate]) or packed frames from
         pack_frame(): one for a single-iteration step, a [S, frame] tensor (one copy) or a list of S for steps_per_replay = S.
@@ -314,6 +341,8 @@ class GraphedTrainStep:
             self.gt.copy_(gt, non_blocking=True)
             if self.dynamic and accum_R is not None:
                 self.accum_R.copy_(accum_R, non_blocking=True)
+            if self.motion and accum_T is not None:
+                self.accum_T.copy_(accum_T.reshape(-1, 4)[:3], non_blocking=True)
             if self.gated and gate is not None:
                 self.gate.copy_(gate, non_blocking=True)
         if getattr(self.pc, "model_version", 0) != self._model_version:

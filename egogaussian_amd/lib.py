@@ -42,6 +42,20 @@ class ObjectRotation(C.Structure):               # egs_object_rotation
     _fields_ = [("M9", C.c_void_p), ("selected", C.c_void_p), ("row0_grad_mult", C.c_float), ("row0_grad_mult_dev", C.c_void_p)]
 
 
+class ObjectMotion(C.Structure):                 # egs_object_motion; goes where an egs_object_rotation* goes when ACT_OBJECT_MOTION is set
+    _fields_ = [("rot", ObjectRotation), ("A12", C.c_void_p), ("moved", C.c_void_p), ("grad", C.c_void_p), ("scratch", C.c_void_p)]
+
+
+ACT_OBJECT_MOTION = 8                            # EGS_ACT_OBJECT_MOTION
+
+
+def rot_pointer(st):
+    """The `rot` argument for an ObjectRotation or an ObjectMotion struct (None -> NULL)."""
+    if st is None:
+        return None
+    return C.byref(st.rot if isinstance(st, ObjectMotion) else st)         # (`rot` is the motion struct's first member: the same address)
+
+
 class BackwardPrologue(C.Structure):             # egs_backward_prologue
     _fields_ = [("P", C.c_int), ("width", C.c_int), ("height", C.c_int), ("image_buffer", C.c_void_p), ("scratch", C.c_void_p),
                 ("sink", C.POINTER(AdamSink)), ("skip_flag", C.c_void_p), ("geom_buffer", C.c_void_p)]
@@ -87,6 +101,9 @@ SIGNATURES = {
     "egs_cov3d_forward": (C.c_int, [i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "egs_cov3d_dm_scratch_floats": (C.c_size_t, [i32]),
     "egs_cov3d_backward": (C.c_int, [i32, vp, i32, f32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_object_motion_scratch_bytes": (C.c_size_t, [i32]),
+    "egs_object_move_points": (C.c_int, [i32, vp, vp, vp, vp, vp, vp]),
+    "egs_object_move_points_backward": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egs_l1_ssim_partial_count": (C.c_size_t, [i32, i32, i32]),
     "egs_l1_ssim_forward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
     "egs_l1_ssim_backward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

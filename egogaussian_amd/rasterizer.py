@@ -41,7 +41,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 activation_flags=0, sh_rest=None, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                object_rotation=None, color_only=False):
+                object_rotation=None, color_only=False, object_motion=None, motion_A12=None, motion_M=None):
         rs = raster_settings
         if guard is not None and getattr(guard, "deferred", False) and any(ctx.needs_input_grad) and not getattr(optimizer, "capturable", False) \
                 and not getattr(guard, "_warned", False):
@@ -53,6 +53,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             warnings.warn("StepGuard(deferred=True) without a FusedAdam(capturable=True) behind it: a frame that exceeds the instance capacity is "
                           "only counted (guard.overflows), its clipped gradient is NOT voided -- pass optimizer=FusedAdam(..., capturable=True) "
                           "with guard set on it, or check guard.overflows before optimizer.step()", RuntimeWarning)
+        # object_motion: (A12, moved, M, selected, multiplier) -- A12 and M are ALSO the inputs motion_A12 / motion_M of this Function, which is how
+        # autograd hands their gradients on (include/egs_raster.h egs_object_motion: dL/dA12 and dL/dM9, a deterministic reduction)
+        ctx.object_motion = object_motion
         ctx.object_rotation = object_rotation     # (M, selected, multiplier): constants of the loss (include/egs_raster.h egs_object_rotation)
         # optimizer (extension): a FusedAdam(capturable=True) whose leaves among THIS call's inputs take their step inside the backward
         ctx.sink = None if (optimizer is None or not any(ctx.needs_input_grad)) else optimizer.make_sink(
@@ -64,7 +67,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         num_rendered, color, depth, alpha, radii, geom, binning, img = _C.rasterize_gaussians(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
-            rs.campos, rs.prefiltered, rs.debug, activation_flags, sh_rest, active_count, guard, object_rotation, color_only)
+            rs.campos, rs.prefiltered, rs.debug, activation_flags, sh_rest, active_count, guard, object_rotation, color_only, object_motion)
         ctx.guard = guard
         ctx.egs_raster_node = True                  # fused.l1_ssim_loss(raster_prologue=True) recognises its input's grad_fn by this
         ctx.prologue_scratch = None
@@ -127,7 +130,16 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos, geom,
             ctx.num_rendered, binning, img, alpha, rs.debug, ctx.activation_flags, sh_rest if split else None, ctx.densify_stats, ctx.guard,
-            ctx.sink, ctx.prologue_scratch, ctx.object_rotation, grad_mask, loss_grad=None if ctx.loss_grad is None else ctx.loss_grad[0])
+            ctx.sink, ctx.prologue_scratch, ctx.object_rotation, grad_mask, loss_grad=None if ctx.loss_grad is None else ctx.loss_grad[0],
+            object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]))
+        g_A12 = g_M = None
+        if ctx.object_motion is not None:
+            pose = grads[-1]
+            grads = grads[:-1]
+            if pose is not None:
+                A12_in, M_in = ctx.object_motion[0], ctx.object_motion[2]
+                g_A12 = pose[:12].view(A12_in.shape) if need[18] else None
+                g_M = pose[12:].view(M_in.shape) if (need[19] and M_in is not None) else None
         ctx.prologue_scratch = None
         ctx.loss_grad = None
         (g_means2D, g_colors, g_opac, g_means3D, g_cov3D, g_sh, g_scales, g_rots) = grads[:8]
@@ -135,7 +147,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (g_means3D, g_means2D, none_if_absent(g_sh, sh), none_if_absent(g_colors, colors_precomp),
                 g_opac, none_if_absent(g_scales, scales),
                 none_if_absent(g_rots, rotations), none_if_absent(g_cov3D, cov3Ds_precomp), None, None,
-                grads[8] if split else None, None, None, None, None, None, None)
+                grads[8] if split else None, None, None, None, None, None, None, None, g_A12, g_M)
 
 
 def backward_prologue_of(node):
@@ -168,12 +180,13 @@ def backward_prologue_of(node):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, activation_flags=0, sh_rest=None, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                        object_rotation=None, color_only=False):
+                        object_rotation=None, color_only=False, object_motion=None):
     """-> (color, radii, depth, alpha, visible); upstream's function returns the first four, `visible` (bool[P] = radii > 0) is an
     extension GaussianRasterizer keeps for render()."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, activation_flags, sh_rest, densify_stats, active_count, guard, optimizer,
-                                     object_rotation, color_only)
+                                     object_rotation, color_only, object_motion,
+                                     None if object_motion is None else object_motion[0], None if object_motion is None else object_motion[2])
 
 
 class GaussianRasterizer(nn.Module):
@@ -189,7 +202,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, raw_parameters=False, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                object_rotation=None, color_only=False):
+                object_rotation=None, color_only=False, object_motion=None):
         """Same call as upstream's.  raw_parameters=True (an extension): `scales`, `rotations` and `opacities` are the model's RAW
         parameters (log-scales, unnormalised quaternions, opacity logits); the activations run inside the preprocess kernel and
         the gradients come back w.r.t. the raw tensors (include/egs_raster.h, EGS_ACT_*).
@@ -201,6 +214,11 @@ class GaussianRasterizer(nn.Module):
         # object_rotation (an extension): (M [3,3], selected [P] or None, row-0 gradient multiplier) with `scales` + `rotations`: the
         # covariance of the selected rows is (M R S)(M R S)^T, built inside the rasterizer -- the reference's render(rot_cov=True,
         # accum_R, which_object) without a covariance tensor; M is a constant of the loss (include/egs_raster.h egs_object_rotation)
+        # object_motion (an extension; instead of object_rotation): (A12 [3,4], moved [P] or None, M [3,3] or None, selected, row-0 gradient
+        # multiplier) -- the rows of `moved` (the EXACT mask; `selected` carries the reference's row-0 quirk) are placed, p' = A p + b, inside the
+        # preprocess kernels: the reference's apply_trans_rot_new / reverse_trans_rot_new around the render without touching means3D.  With
+        # M (needs `scales` + `rotations`) the covariance is turned as with object_rotation.  A12 and M receive gradients when they require
+        # them (a trainable pose); means3D receives the gradient of the canonical positions (include/egs_raster.h egs_object_motion)
         # optimizer (an extension): a FusedAdam(capturable=True).  Every input of this call that IS one of its parameters takes its
         # Adam step inside the backward (its .grad stays None and optimizer.step() skips it) -- only valid when this call is the
         # sole consumer of those parameters in the backward pass (optim.FusedAdam.make_sink)
@@ -212,7 +230,9 @@ class GaussianRasterizer(nn.Module):
         # get_features).  When those are the untouched results of getters installed by adapter.attach() (provenance.py), the raw parameters
         # they were computed from are rasterized instead: same image and gradients to float rounding, without the activation / covariance /
         # concatenation backward launches and their autograd nodes.
-        if cov3D_precomp is not None and scales is None and rotations is None and not raw_parameters and object_rotation is None:
+        if object_motion is not None and object_rotation is not None:
+            raise Exception("GaussianRasterizer: object_motion and object_rotation are mutually exclusive (the motion carries the rotation)")
+        if cov3D_precomp is not None and scales is None and rotations is None and not raw_parameters and object_rotation is None and object_motion is None:
             sub = _provenance.substitute(opacities, cov3D_precomp, shs, self.raster_settings.scale_modifier)
             if sub is not None:
                 scales, rotations, opacities, shs, object_rotation = sub["scales"], sub["rotations"], sub["opacities"], sub["shs"], sub["object_rotation"]
@@ -234,9 +254,10 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if (raw_parameters or object_rotation is not None) and cov3D_precomp.numel() != 0:
+        if (raw_parameters or object_rotation is not None or (object_motion is not None and object_motion[2] is not None)) and cov3D_precomp.numel() != 0:
             raise Exception("GaussianRasterizer: raw_parameters / object_rotation need `scales` and `rotations`, not `cov3D_precomp`")
         color, radii, depth, alpha, self.visible = rasterize_gaussians(
             means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings,
-            _C.ACT_RAW_PARAMETERS if raw_parameters else 0, shs_rest, densify_stats, active_count, guard, optimizer, object_rotation, color_only)
+            _C.ACT_RAW_PARAMETERS if raw_parameters else 0, shs_rest, densify_stats, active_count, guard, optimizer, object_rotation, color_only,
+            object_motion)
         return color, radii, depth, alpha

@@ -36,8 +36,25 @@ def _screenspace_leaf(xyz):
     return base.detach().requires_grad_(True)
 
 
+def _motion_rows(pc, which_object):
+    """(moved uint8[N] or None -- the EXACT mask of the reference's torch.where --, fused.object_selection's (selected, row-0 multiplier) -- the
+    rows whose covariance turns) for this model, kept until `_is_object` is replaced or edited."""
+    from . import fused
+    from .motion import exact_mask
+    io = pc.get_is_object
+    n, n_live = pc.get_xyz.shape[0], getattr(pc, "n_active", None)
+    key = (which_object, io.data_ptr(), io._version, tuple(io.shape), n_live)
+    cache = pc.__dict__.setdefault("_egs_motion_rows", {})
+    if cache.get("key") != key:
+        moved = exact_mask(io, which_object)
+        cache["key"], cache["moved"] = key, None if moved is None else moved.to(torch.uint8).contiguous()
+        cache["selection"] = fused.object_selection(io, which_object, n, n_live)
+    return cache["moved"], cache["selection"]
+
+
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, rot_cov=False,
-           accum_R=None, which_object=None, during_training=False, fused_densify_stats=False, guard=None, optimizer=None, color_only=False):
+           accum_R=None, which_object=None, during_training=False, fused_densify_stats=False, guard=None, optimizer=None, color_only=False,
+           object_motion=None):
     """Extensions (defaults = the reference's behaviour):
     fused_densify_stats  the backward of this render also updates pc.xyz_gradient_accum, pc.denom and pc.max_radii2D in place
                          (the trainer then skips add_densification_stats / the max_radii2D update for this iteration);
@@ -47,6 +64,13 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
                          inside the rasterizer's backward -- valid when this render is their only use in the iteration's loss;
     color_only           "depth" and "alpha" of the result are None and the blend does not compute them (GraphedTrainStep: the loss reads
                          the colour image only);
+    object_motion        a motion.ObjectMotion (motion.select_motion): the frame's object pose as an INPUT.  The Gaussians of `which_object`
+                         are placed inside the rasterizer (p' = A p + b) instead of by apply_trans_rot_new / reverse_trans_rot_new around
+                         the call: `pc._xyz` is never touched, keeps its optimizer state and its address, and receives the gradient of the
+                         canonical positions.  With rot_cov the covariance turns by the motion's own M = R_t accum_R (the `accum_R` argument
+                         is not read) and the raw-parameter path stays on even while the pose is trained: M and A12 get gradients, which
+                         autograd carries to obj_translation / obj_rotation_6d.  A model without get_raw_parameters() cannot be rendered
+                         with rot_cov and a motion (RuntimeError): the covariance producers would turn by `accum_R`;
     a model with an `active_count` attribute (int32[1] device tensor; capacity.CapacityGaussians) renders only its live rows.
     `visibility_filter` is radii > 0 as written by the preprocess kernel: a fresh tensor in eager calls; while a hipGraph is being
     captured it is a VIEW of the rasterizer's saved state that follows every replay (no launch) -- clone it to keep or edit it."""
@@ -59,7 +83,27 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     scales = rotations = cov3D_precomp = opacity = None
     raw = False
     object_rotation = None
-    if pipe.compute_cov3D_python:
+    motion_arg = None
+    raw3 = None
+    if object_motion is not None:
+        if not xyz.is_cuda:
+            raise RuntimeError("render(object_motion=...): HIP devices only (motion.move_points is the tensor expression for CPU tensors)")
+        A12, M = object_motion.compose(xyz.device)
+        moved, selection = _motion_rows(pc, which_object)
+        motion_arg = (A12, moved, None, None, 1.0)
+        if pipe.compute_cov3D_python and rot_cov and getattr(pc, "get_raw_parameters", None) is not None:
+            raw3 = pc.get_raw_parameters()
+        if pipe.compute_cov3D_python and rot_cov and raw3 is None:
+            # the other routes to a turned covariance read `accum_R` (and the model's own trainable module), not the motion's M: they
+            # would place the positions by this pose and turn the covariances by another one
+            raise RuntimeError("render(object_motion=..., rot_cov=True): the model must offer get_raw_parameters() (adapter.attach adds "
+                               "it); the covariance producers do not take the motion's rotation")
+    if raw3 is not None:
+        # the motion carries the rotation: raw parameters + (A12, moved, M, selected rows, row-0 multiplier), trainable pose included
+        scales, rotations, opacity = raw3
+        raw = True
+        motion_arg = (A12, moved, M) + tuple(selection)
+    elif pipe.compute_cov3D_python:
         rotated_raw = pc.get_raw_parameters_rotated(accum_R, which_object, during_training) \
             if (rot_cov and getattr(pc, "get_raw_parameters_rotated", None) is not None) else None
         if rotated_raw is not None:
@@ -109,7 +153,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
                                             **({"guard": guard} if guard is not None else {}),
                                             **({"optimizer": optimizer} if optimizer is not None else {}),
                                             **({"object_rotation": object_rotation} if object_rotation is not None else {}),
-                                            **({"color_only": True} if color_only else {}))
+                                            **({"color_only": True} if color_only else {}),
+                                            **({"object_motion": motion_arg} if motion_arg is not None else {}))
     visible = rasterizer.visible                           # radii > 0 from the preprocess kernel of THIS call (returned, not shared state)
     if visible is None:
         visible = radii > 0

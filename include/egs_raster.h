@@ -167,6 +167,27 @@ typedef struct egs_object_rotation {
                                          (egogaussian_amd/covariance.py), 1 = none */
     const float* row0_grad_mult_dev;  /* device float[1] used instead of row0_grad_mult, or NULL */
 } egs_object_rotation;
+/* Rigid object motion inside the rasterizer (ABI 6 addition).  Every stage after the static one poses the object's Gaussians per frame
+ * (gaussians.apply_trans_rot_new before render(..., rot_cov=True, accum_R, which_object), reverse_trans_rot_new after it:
+ * /root/reference/trainers/coarse_obj_pose.py:229-239,313-317, /root/reference/trainers/fine_all.py:88-116).  With EGS_ACT_OBJECT_MOTION among the
+ * activation flags the `rot` argument of egs_forward_geometry, egs_forward, egs_forward_enqueue, egs_backward_adam and egs_backward_lossgrad
+ * points to an egs_object_motion instead: the preprocess kernels place the moved rows, p' = A p + b (see egs_object_move_points below for the
+ * arithmetic and for why `moved` is not `rot.selected`), every later stage sees the placed position, and the backward
+ *   - writes dL_dmeans3D -- and steps EGS_SINK_MEANS3D -- with the gradient of the CANONICAL position, A^T dL/dp' for a moved row;
+ *   - with `grad`, writes dL/dA12 (12 floats in A12's layout) and dL/dM9 (9 floats; zeros without rot.M9) as a deterministic reduction:
+ *     per-workgroup lines in `scratch`, one finish launch, no float atomics.  dL/dM9 is k_cov3d_backward's gM operation for operation,
+ *     the row-0 multiplier included.  Without `grad` (a constant pose) the backward makes no shuffle and no extra launch.
+ * The motion of the positions works with every covariance input (cov3D_precomp too); rot.M9 under egs_object_rotation's conditions.
+ * Bit set with A12 == NULL, or grad without scratch: EGS_ERR_ARG before any device work; bit set with rot == NULL: EGS_ERR_MODE.  egs_backward (no `rot` argument)
+ * does not take the bit.  Pass the same flags and struct to the forward and to the backward.  Callers that do not set the bit are untouched. */
+#define EGS_ACT_OBJECT_MOTION 8
+typedef struct egs_object_motion {
+    egs_object_rotation rot;      /* first member; rot.M9 == NULL: covariances are not turned */
+    const float*   A12;           /* device float[12], row-major 3x4 [A | b]; required */
+    const uint8_t* moved;         /* device uint8[P] or NULL = every row */
+    float*         grad;          /* device float[21] out (dL/dA12 [12] in A12's layout, dL/dM9 [9]) or NULL */
+    void*          scratch;       /* egs_object_motion_scratch_bytes(P), needed with grad */
+} egs_object_motion;
 int egs_forward_geometry(
     int P, int sh_degree, int sh_coeffs /* M: coefficients per channel in `shs` */,
     const float* means3D /*[P,3]*/, const float* shs /*[P,M,3] or NULL*/, const float* shs_rest /*see below; normally NULL*/,
@@ -387,6 +408,33 @@ int egs_cov3d_backward(int N, const float* scaling, int scaling_is_log, float sc
                        float* dL_dscaling /*[N,3] out*/, float* dL_drotation /*[N,4] out*/, float* dL_dM9, float* dM_scratch,
                        const float* opacity /*[N] forward output or NULL*/, const float* dL_dopacity /*[N]*/,
                        float* dL_dopacity_raw /*[N] out*/, void* stream);
+
+/* ---- rigid object motion of the positions (ABI 6 addition; additions only).  Every EgoGaussian stage after the static one poses the
+ *      object's Gaussians per frame: gaussians.apply_trans_rot_new(...) rebuilds _xyz out of place before the render
+ *      (/root/reference/scene/gaussian_model.py:939-986: torch.where(is_object == which, apply_T_xyz(T, xyz), xyz), with the trainable
+ *      ObjectMove on top during training, /root/reference/utils/geometry_utils.py:14-33,188-193) and reverse_trans_rot_new(...) undoes
+ *      it through a matrix inverse afterwards (gaussian_model.py:1037-1060).  Here the pose is an INPUT: for a moved row
+ *          p'_i = A p_i + b          A12 = [A | b], device float[12], row-major 3x4; three fused multiply-adds per component
+ *      and nothing is mutated, so there is nothing to reverse.  Backward, with g_i = dL/dp'_i:
+ *          dL/dp_i = A^T g_i  (moved rows; g_i for the others)      dL/dA12 = sum over the moved rows of [g_i p_i^T | g_i]
+ *      `moved` (device uint8[P], NULL = every row) is the EXACT mask of the reference's torch.where -- it is NOT the `selected` of
+ *      egs_object_rotation, which carries the reference's [N,1]-index quirk (row 0).  Rows at or beyond *active_count
+ *      (capacity-sized models) are never moved and never summed.  How A12 is composed from the accumulated and the trainable pose
+ *      (A = R_t A_f, b = R_t b_f + t, the 6-D -> matrix map) is 3x3 algebra the caller does; autograd carries dL/dA12 on from there.
+ *      The pose gradient is a deterministic reduction: per-workgroup lines (six __shfl_xor levels, four waves through LDS: an eight-deep
+ *      float32 tree) in `scratch`, then one finish workgroup that adds the lines in index order in float64.  No float atomics: the same
+ *      inputs give the same bits.  (egs_object_motion_scratch_bytes also covers the rasterizer's backward, whose lines come one per
+ *      64 rows when the spherical-harmonics launch finishes the positions' gradient, plus the rotation lines.)
+ *      egs_object_move_points           the placed positions as an array [P,3] (evaluation, export of a posed frame, a comparison path);
+ *                                       rows that are not moved are copied bit for bit.  `out` must not alias means3D.
+ *      egs_object_move_points_backward  dmeans3D [P,3] (may be NULL) and grad12 (device float[12] in A12's layout, may be NULL; needs
+ *                                       means3D and `scratch`) from g [P,3]; dmeans3D must not alias g. */
+size_t egs_object_motion_scratch_bytes(int P);
+int egs_object_move_points(int P, const float* means3D /*[P,3]*/, const float* A12 /*device [12]*/, const uint8_t* moved /*[P] or NULL*/,
+                           const int32_t* active_count /*device int32[1] or NULL*/, float* out /*[P,3] out*/, void* stream);
+int egs_object_move_points_backward(int P, const float* means3D /*[P,3]*/, const float* A12, const uint8_t* moved, const int32_t* active_count,
+                                    const float* g /*[P,3]: dL/dp'*/, float* dmeans3D /*[P,3] out or NULL*/, float* grad12 /*device [12] out or NULL*/,
+                                    void* scratch /*egs_object_motion_scratch_bytes(P), needed with grad12*/, void* stream);
 
 /* ---- f-3: fused image loss (1 - lambda) * L1 + lambda * (1 - SSIM), 11x11 Gaussian window sigma 1.5, zero padding.
  *      Replaces l1_loss + ssim (/root/reference/utils/loss_utils.py:57-107) as combined at

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.common import flip_pixels, check_grads_isolating_flips, check_images_isolating_flips, make_inputs, seeded_grads, rel_err, outlier_fraction, tile_culling, check_culled_lists   # noqa: E402
+from tests.common import FarRowOverBar, NEAR_SHARE, gaussians_contributing_to, flip_pixels, check_grads_isolating_flips, check_images_isolating_flips, make_inputs, seeded_grads, rel_err, outlier_fraction, tile_culling, check_culled_lists   # noqa: E402
 from tests.test_gpu_parity import hip_forward, hip_backward, oracle_forward, TOL                                     # noqa: E402
 from egogaussian_amd import _C                                                                                       # noqa: E402
 
@@ -104,57 +104,71 @@ def _one_draw(d, N, H, W, cull, split, active, tag, dev, worst, keep_going, n_ca
             e = rel_err(hh, ora)
             worst[name] = max(worst.get(name, 0.0), e)
             strict = strict and e <= TOL
-        # Gaussians away from every flipped pixel: the north star's 1e-4, whatever the frame; the ones in a flipped pixel's tile list: a
-        # flipped pair moves the gradients of ITS splat by that pair's whole share -- for a faint splat that reaches three or four pixels a
-        # few per cent of its dL/dopacity (seed 4242, draw 3215: one flipped pixel, 2.3 %; tests/dev/fuzz_repro.py replays a draw)
-        if np.isfinite(st["color"]).all() and all(np.isfinite(v).all() for v in gb.values() if v is not None):
-            try:
-                _, far, _ = check_grads_isolating_flips(names, hb, gb, st, flip_px, TOL, share=5e-2, what=tag)
-            except AssertionError as first:
-                # The float32 oracle adds a splat's thousands of pixel terms in whatever order its OpenMP threads reach them: on a splat that
-                # covers the whole frame its own sum moves by 1-4e-4 of the array's maximum from run to run (seed 20260930, draw 227: Gaussian
-                # 67346, radius 377 px on a 222x82 image -- oracle32 1548.96 / 1548.40 in two runs, oracle64 1548.242, HIP 1548.242), and the HIP
-                # path's float32 sums (wave reductions + atomics) carry the same kind of noise.  The rows that missed the bar against the float32
-                # oracle -- and only those -- are arbitrated by the float64 oracle of the same draw: within the bar, or within 3 x the bar
-                # (far_cap) for a splat of 36 px radius or more (>= 4 000 pixel terms).  Any row that misses THAT fails the draw.
-                from oracle.oracle import Oracle
-                from tests.common import gaussians_near_flips
-                o64 = Oracle(np.float64, nthreads=8)
-                d64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in d.items()}
-                st64 = o64.forward(**d64)
-                gb64 = o64.backward(st64, *[x.double() for x in grads])
-                near = gaussians_near_flips(st, flip_px, 0)
-                far = 0.0
-                for name, h in zip(names, hb):
-                    o32, o64g = gb.get(name), gb64.get(name)
-                    if o32 is None or h is None or h.numel() == 0:
-                        continue
-                    hh = h.detach().cpu().numpy().reshape(o32.shape).astype(np.float64)
-                    a32, a64 = np.asarray(o32, dtype=np.float64), np.asarray(o64g, dtype=np.float64).reshape(o32.shape)
-                    sc = float(np.abs(a32).max()) + 1e-30
-                    e32 = np.abs(hh - a32).reshape(a32.shape[0], -1).max(1) / sc
-                    e64 = np.abs(hh - a64).reshape(a32.shape[0], -1).max(1) / sc
-                    e32[near[near < a32.shape[0]]] = 0.0                 # (rows near a flipped pixel have their own bound, checked above)
-                    rows = np.nonzero(e32 >= TOL)[0]
-                    # frame-filling splats: 3 x the bar, or -- when the float32 ORACLE itself is further than that from the float64 one (seed 777123,
-                    # draw 129: radius 300 px on 412x270, 111 k pixel terms: oracle32 18145.8, HIP 18149.1, oracle64 18155.9) -- no worse than
-                    # 1.5 x the float32 oracle's own distance from the float64 result
-                    o_err = np.abs(a32 - a64).reshape(a32.shape[0], -1).max(1) / sc
-                    # ... and, whatever the radius, where the float32 ORACLE is itself further than the bar from the float64 one the row is held to
-                    # 1.5 x that distance (seed 9001, draw 10962: ONE Gaussian of 15 px radius, symmetric footprint -- sum |gd dx| is 7 000 x the
-                    # sum: oracle32 0.55225 with one thread, 0.55207 with eight, HIP 0.55220, the float32 terms summed in float64 0.55215,
-                    # oracle64 0.55254: every float32 evaluation is 5-8e-4 off; tests/test_gpu_offscreen.py holds that draw with all three distances)
-                    bar = np.where(np.asarray(st["radii"])[rows] >= 36, np.maximum(3.0 * TOL, 1.5 * o_err[rows]), np.maximum(TOL, 1.5 * o_err[rows]))
-                    if (e64[rows] >= bar).any():
-                        if not keep_going:
-                            raise first
-                        worst.setdefault("_failed_draws", []).append(f"draw {n_cases}: {str(first)[:420]}")     # (a long run reports them all; pytest's slice stops here)
-                        break
-                    far = max(far, float(np.where(e32 >= TOL, 0.0, e32).max()))
-                else:
-                    worst["_arbitrated_by_f64_oracle"] = worst.get("_arbitrated_by_f64_oracle", 0) + 1
-            worst["_far_from_flips"] = max(worst.get("_far_from_flips", 0.0), far)
+        check_draw_gradients(names, hb, gb, st, flip_px, d, grads, tag, worst, keep_going, n_cases)
         return strict
+
+
+def check_draw_gradients(names, hb, gb, st, flip_px, d, grads, tag, worst, keep_going=False, n_cases=0):
+    """The gradients of one draw (hb: the subject's, torch tensors; gb / st: the float32 oracle's) under the rule of the parity tests.
+    Gaussians that contribute to no flipped pixel: the north star's 1e-4, whatever the frame; the contributors of a flipped pixel's chain
+    (tests/common.py gaussians_contributing_to): the flipped pair's share, 2e-3 of the array's maximum, and no more of them than the caps
+    allow.  (The largest such row on record with the suite's seeds is 6.2e-4; a long randomised run has seen one flipped pair move the
+    dL/dopacity of a faint splat that reaches three or four pixels by 2.3 % -- seed 4242, draw 3215; tests/dev/fuzz_repro.py replays a
+    draw -- which fails this bound and is reported with the pixel's cause.)
+    ONLY a row far from every flip that misses the bar goes to arbitration by the float64 oracle (FarRowOverBar); the share of the
+    set-aside rows and the caps on their number are not arbitrated: those failures propagate, and the set-aside rows of the arrays the
+    first call did not reach are held to the share here."""
+    if not (np.isfinite(st["color"]).all() and all(np.isfinite(v).all() for v in gb.values() if v is not None)):
+        return
+    try:
+        _, far, _ = check_grads_isolating_flips(names, hb, gb, st, flip_px, TOL, what=tag)
+    except FarRowOverBar as first:
+        # The float32 oracle adds a splat's thousands of pixel terms in whatever order its OpenMP threads reach them: on a splat that
+        # covers the whole frame its own sum moves by 1-4e-4 of the array's maximum from run to run (seed 20260930, draw 227: Gaussian
+        # 67346, radius 377 px on a 222x82 image -- oracle32 1548.96 / 1548.40 in two runs, oracle64 1548.242, HIP 1548.242), and the HIP
+        # path's float32 sums (wave reductions + atomics) carry the same kind of noise.  The rows that missed the bar against the float32
+        # oracle -- and only those -- are arbitrated by the float64 oracle of the same draw: within the bar, or within 3 x the bar
+        # (far_cap) for a splat of 36 px radius or more (>= 4 000 pixel terms).  Any row that misses THAT fails the draw.
+        from oracle.oracle import Oracle
+        o64 = Oracle(np.float64, nthreads=8)
+        d64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in d.items()}
+        st64 = o64.forward(**d64)
+        gb64 = o64.backward(st64, *[x.double() for x in grads])
+        near = gaussians_contributing_to(st, flip_px, 0)          # (the caps on their number were asserted before the first array was looked at)
+        far = 0.0
+        for name, h in zip(names, hb):
+            o32, o64g = gb.get(name), gb64.get(name)
+            if o32 is None or h is None or h.numel() == 0:
+                continue
+            hh = h.detach().cpu().numpy().reshape(o32.shape).astype(np.float64)
+            a32, a64 = np.asarray(o32, dtype=np.float64), np.asarray(o64g, dtype=np.float64).reshape(o32.shape)
+            sc = float(np.abs(a32).max()) + 1e-30
+            e32 = np.abs(hh - a32).reshape(a32.shape[0], -1).max(1) / sc
+            e64 = np.abs(hh - a64).reshape(a32.shape[0], -1).max(1) / sc
+            near_rows = near[near < a32.shape[0]]
+            e_near = float(e32[near_rows].max()) if near_rows.size else 0.0
+            assert e_near < NEAR_SHARE, (f"{tag} {name}: max rel err {e_near} (bound {NEAR_SHARE:g}) on Gaussian {int(near_rows[np.argmax(e32[near_rows])])}, "
+                                         f"a contributor to a flipped pixel's chain")
+            e32[near_rows] = 0.0                                  # (held to the share just above, against the float32 oracle)
+            rows = np.nonzero(e32 >= TOL)[0]
+            # frame-filling splats: 3 x the bar, or -- when the float32 ORACLE itself is further than that from the float64 one (seed 777123,
+            # draw 129: radius 300 px on 412x270, 111 k pixel terms: oracle32 18145.8, HIP 18149.1, oracle64 18155.9) -- no worse than
+            # 1.5 x the float32 oracle's own distance from the float64 result
+            o_err = np.abs(a32 - a64).reshape(a32.shape[0], -1).max(1) / sc
+            # ... and, whatever the radius, where the float32 ORACLE is itself further than the bar from the float64 one the row is held to
+            # 1.5 x that distance (seed 9001, draw 10962: ONE Gaussian of 15 px radius, symmetric footprint -- sum |gd dx| is 7 000 x the
+            # sum: oracle32 0.55225 with one thread, 0.55207 with eight, HIP 0.55220, the float32 terms summed in float64 0.55215,
+            # oracle64 0.55254: every float32 evaluation is 5-8e-4 off; tests/test_gpu_offscreen.py holds that draw with all three distances)
+            bar = np.where(np.asarray(st["radii"])[rows] >= 36, np.maximum(3.0 * TOL, 1.5 * o_err[rows]), np.maximum(TOL, 1.5 * o_err[rows]))
+            if (e64[rows] >= bar).any():
+                if not keep_going:
+                    raise first
+                worst.setdefault("_failed_draws", []).append(f"draw {n_cases}: {str(first)[:420]}")     # (a long run reports them all; pytest's slice stops here)
+                break
+            far = max(far, float(np.where(e32 >= TOL, 0.0, e32).max()))
+        else:
+            worst["_arbitrated_by_f64_oracle"] = worst.get("_arbitrated_by_f64_oracle", 0) + 1
+    worst["_far_from_flips"] = max(worst.get("_far_from_flips", 0.0), far)
 
 
 if __name__ == "__main__":

@@ -93,7 +93,7 @@ def test_config_C_bench_mode_vs_oracle():
     # float noise, the two sides' images (equal to ~1e-7) give OPPOSITE signs, and that pixel's upstream gradient differs by 2 x 0.8 / n --
     # in round 5 these rows were put down to "fp32 accumulation order", which the repeated replays below disprove (spread 1e-8).  Such a
     # pixel is found directly (the signs differ), has to prove it (both sides within 1e-6 of the ground truth there), and then counts as
-    # a flipped pixel: its tile's Gaussians get the flipped pair's bound, everything else the bar.
+    # a flipped pixel: the contributors of its chain (and of the pixels within the SSIM halo) get the flipped pair's bound, everything else the bar.
     gt = gts[1].cpu().numpy().astype(np.float64)
     s_hip, s_or = np.sign(img_hip.astype(np.float64) - gt), np.sign(st["color"].astype(np.float64) - gt)
     tie = s_hip != s_or                                               # per pixel-channel

@@ -5,12 +5,12 @@ summing instead of per pixel shows it here first.
 
 Every gradient row of every draw is held to the float64 oracle: within 1e-4 (max-norm relative: of the largest |entry| of the array), or --
 where the float32 ORACLE itself is further than that from the float64 one -- within twice the float32 oracle's own distance.  Rows in the
-tile list of a proven threshold flip are set aside as everywhere else (tests/common.py).  The three distances are printed per draw."""
+chain of a proven threshold flip (its contributors) are set aside as everywhere else (tests/common.py).  The three distances are printed per draw."""
 import numpy as np
 import pytest
 import torch
 
-from tests.common import make_inputs, seeded_grads, tile_culling, flip_pixels, gaussians_near_flips, check_images_isolating_flips
+from tests.common import make_inputs, seeded_grads, tile_culling, flip_pixels, gaussians_contributing_to, check_images_isolating_flips
 from tests.test_gpu_parity import hip_forward, hip_backward, oracle_forward, TOL
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +57,7 @@ def test_large_offscreen_centred_splats_vs_float64_oracle(N, H, W, seed, deg, mo
     flip_px = flip_pixels(out[1].cpu().numpy(), iv["final_T"].cpu().numpy(), st, iv["n_contrib"].cpu().numpy().view(np.uint32))
     check_images_isolating_flips((("color", out[1].cpu().numpy(), st["color"]), ("depth", out[2].cpu().numpy(), st["depth"]), ("alpha", out[3].cpu().numpy(), st["alpha"])),
                                  st, flip_px, TOL)
-    near = gaussians_near_flips(st, flip_px, 0)
+    near = gaussians_contributing_to(st, flip_px, 0)
     rep, bad = [], []
     for name, h in zip(NAMES, hb):
         o32 = gb.get(name)

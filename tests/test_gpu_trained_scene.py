@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.common import flip_pixels, check_images_isolating_flips, make_inputs, seeded_grads, rel_err, outlier_fraction, tile_culling
+from tests.common import flip_pixels, check_images_isolating_flips, check_grads_isolating_flips, make_inputs, seeded_grads, rel_err, outlier_fraction, tile_culling
 from tests.test_gpu_parity import hip_forward, hip_backward, oracle_forward, _dev, TOL
 
 pytestmark = pytest.mark.gpu
@@ -31,10 +31,17 @@ def _hot_codes(geom, N, radii):
     return np.where(radii.cpu().numpy() > 0, ((bx >> 15) & 1) | ((bx >> 30) & 2) | ((by >> 13) & 4), 0)
 
 
-def _check_grads(hb, gb, st, flip_px, what):
-    """Gaussians away from every threshold flip at 1e-4, the ones in a flipped pixel's tile list by a pair's share (tests/common.py)."""
+def _check_grads(hb, gb, st, flip_px, what, rows_of=None):
+    """Gaussians that contribute to no flipped pixel at 1e-4 of the array maximum, the contributors by a pair's share (tests/common.py).
+    rows_of = (inputs, upstream gradients): every row against its own magnitude as well (float64 oracle) -- the replica-line path
+    exists for the hot rows only, and the cold rows next to them are what a bar relative to the hot rows' maximum cannot see."""
     from tests.common import check_grads_isolating_flips
-    return check_grads_isolating_flips(NAMES, hb, gb, st, flip_px, TOL, what=what)[0]
+    from tests.test_gpu_parity import check_rows
+    near = []
+    rep = check_grads_isolating_flips(NAMES, hb, gb, st, flip_px, TOL, what=what, near_out=near)[0]
+    if rows_of is not None:
+        rep += "\n   " + check_rows(rows_of[0], rows_of[1], NAMES, hb, st, gb, near[0], what)
+    return rep
 
 
 @pytest.mark.parametrize("cull", [False, True], ids=["reference-lists", "tile-culling"])
@@ -67,7 +74,7 @@ def test_hot_gaussians_accumulate_through_replica_lines(cull):
     flip_px = flip_pixels(out[1].cpu().numpy(), iv["final_T"].cpu().numpy(), st, None if cull else iv["n_contrib"].cpu().numpy().view(np.uint32))
     check_images_isolating_flips((("color", out[1].cpu().numpy(), st["color"]), ("depth", out[2].cpu().numpy(), st["depth"]), ("alpha", out[3].cpu().numpy(), st["alpha"])), st, flip_px, TOL)
     gb = o.backward(st, *grads)
-    print("\n   hot replica lines: " + _check_grads(hb, gb, st, flip_px, "hot"))
+    print("\n   hot replica lines: " + _check_grads(hb, gb, st, flip_px, "hot", rows_of=(d, grads)))
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3, 4, 5])
@@ -108,7 +115,7 @@ def test_random_hot_layouts_vs_oracle(seed):
     flip_px = flip_pixels(out[1].cpu().numpy(), iv["final_T"].cpu().numpy(), st, None if cull else iv["n_contrib"].cpu().numpy().view(np.uint32))
     check_images_isolating_flips((("color", out[1].cpu().numpy(), st["color"]), ("depth", out[2].cpu().numpy(), st["depth"]), ("alpha", out[3].cpu().numpy(), st["alpha"])), st, flip_px, TOL)
     gb = o.backward(st, *grads)
-    print(f"\n   [{N}@{W}x{H} {mode} cull={cull}] {len(big)} large splats, {int((code != 0).sum())} hot: " + _check_grads(hb, gb, st, flip_px, "random hot"))
+    print(f"\n   [{N}@{W}x{H} {mode} cull={cull}] {len(big)} large splats, {int((code != 0).sum())} hot: " + _check_grads(hb, gb, st, flip_px, "random hot", rows_of=(d, grads)))
 
 
 def _trained_inputs():
@@ -155,4 +162,14 @@ def test_trained_scene_vs_oracle():
     check_images_isolating_flips((("color", out[1].cpu().numpy(), st["color"]), ("depth", out[2].cpu().numpy(), st["depth"]), ("alpha", out[3].cpu().numpy(), st["alpha"])), st, flip_px, TOL)
     gb = o.backward(st, *grads)
     n_list = int((iv["ranges"][:, 1] - iv["ranges"][:, 0]).sum())
-    print(f"\n   trained scene: R {out[0]}, kept {n_list}, hot Gaussians {n_hot}; " + _check_grads(hb, gb, st, flip_px, "trained"))
+    # Screen-filling splats are in every tile's list: the tile-list rule set them aside wherever a pixel flipped; now they answer to the bar,
+    # and where the float32 oracle's own half-million-term sum is further than the bar from the float64 one, to the float64 oracle (on this
+    # scene Gaussian 119933 is, at every thread count, so the float64 oracle runs on practically every execution: profiles/parity_rows.md).
+    # The per-row measure (check_grad_rows_vs_float64) is NOT run here although the float64 gradients are at hand: the float32 and the
+    # float64 oracle take different branches at 1 567 pixels of this scene, the contributors of those pixels are 3 776 of the 174 051
+    # visible rows (2.17 %), and the measure's own condition is that at most 2 % of the visible rows are excluded -- no subject can meet it.
+    import functools
+    from tests.test_gpu_parity import float64_oracle
+    arbiter = functools.lru_cache(None)(lambda: float64_oracle(d, grads)[1])
+    rep = check_grads_isolating_flips(NAMES, hb, gb, st, flip_px, TOL, what="trained", arbiter=arbiter)[0]
+    print(f"\n   trained scene: R {out[0]}, kept {n_list}, hot Gaussians {n_hot}; " + rep)

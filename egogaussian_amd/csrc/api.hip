@@ -5,6 +5,7 @@
 #include "egs_common.h"
 #include "object_motion.h"
 #include "backward_prologue.h"
+#include "loss_window.h"
 #include <string.h>
 #include <vector>
 #include <mutex>
@@ -487,6 +488,19 @@ static void sink_to_kernel_args(const egs_adam_sink* sink, const uint32_t* skip_
     tick.coef = sink->coef; tick.skip = skip_flag; tick.b1 = sink->beta1; tick.b2 = sink->beta2;
 }
 
+// egs_object_loss (HOST struct) -> what the kernels read (loss_window.h)
+static int obj_loss_args(const egs_object_loss* o, int channels, int height, int width, float lambda_dssim, EgsObjLossK& k) {
+    if (!o || !o->alpha || !o->obj_mask || channels <= 0 || height <= 0 || width <= 0) return EGS_ERR_ARG;
+    const float hw = (float)height * (float)width, n = (float)channels * hw;
+    k = EgsObjLossK{};
+    k.alpha = o->alpha; k.mask = o->obj_mask; k.apartial = o->alpha_partial_sums; k.terms = o->terms;
+    k.w_l1a = o->lambda_l1_alpha / hw; k.w_l2a2 = (2.f * o->lambda_l2_alpha) / hw;
+    k.l_img = o->lambda_image; k.l_l1a = o->lambda_l1_alpha; k.l_l2a = o->lambda_l2_alpha; k.inv_hw = 1.f / hw;
+    k.fin_w_l1 = (1.f - lambda_dssim) / n; k.fin_w_ssim = lambda_dssim / n;
+    k.n_astrips = (unsigned)(egs_l1_ssim_partial_count(1, height, width) / 2);
+    return 0;
+}
+
 static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
                  const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
                  const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
@@ -496,11 +510,12 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
                  float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
                  float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
                  const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
-                 void* stream, int debug, const egs_loss_grad* loss_grad = nullptr) {
+                 void* stream, int debug, const egs_loss_grad* loss_grad = nullptr, const egs_object_loss* obj_loss = nullptr) {
     int rc = check_dims(P, width, height); if (rc) return rc;
     EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     // the image loss's gradient computed by the blend itself (egs_backward_lossgrad): colour gradients only, three channels
-    EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr;
+    EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr; EgsObjLossK olk = {};
+    if (obj_loss && !loss_grad) return EGS_ERR_ARG;
     if (loss_grad) {
         const egs_loss_grad& q = *loss_grad;
         if (!q.image || !q.gt || !q.dm_dmu1 || !q.dm_dexx || !q.dm_dexy || !q.upstream_grad) return EGS_ERR_ARG;
@@ -510,6 +525,13 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
                                q.deferred_loss, q.deferred_partial_sums ? q.loss_running_sum : nullptr };
         lgp = &lgh;
         if (!dL_dout_color) dL_dout_color = q.image;                 // (never read: the checks below want a pointer)
+        if (obj_loss) {
+            // the object stages' loss: the image weights carry lambda_image, the blend also forms dL/dalpha (k_render_backward<2, true>)
+            if (q.deferred_partial_sums && !obj_loss->alpha_partial_sums) return EGS_ERR_ARG;
+            rc = obj_loss_args(obj_loss, 3, height, width, q.lambda_dssim, olk); if (rc) return rc;
+            lgh.w_l1_n = obj_loss->lambda_image * (1.f - q.lambda_dssim); lgh.w_ssim_n = obj_loss->lambda_image * q.lambda_dssim;
+            lgh.obj = &olk;
+        }
     }
     if (P == 0) {
         if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, (hipStream_t)stream));
@@ -716,6 +738,56 @@ int egs_l1_ssim_forward_ex(int channels, int height, int width, const float* img
     if (side) { int rc = prologue_args(side, pa); if (rc) return rc; }
     return egs_launch_l1_ssim_forward(channels, height, width, img, gt, lambda_dssim, partial_sums, dm_dmu1, dm_dexx, dm_dexy, loss, loss_running_sum,
                                       side ? &pa : nullptr, (hipStream_t)stream);
+}
+
+int egs_object_loss_forward_ex(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
+                               float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss, float* loss_running_sum,
+                               const egs_object_loss* obj, const egs_backward_prologue* side, void* stream) {
+    EgsObjLossK ok; int rc = obj_loss_args(obj, channels, height, width, lambda_dssim, ok); if (rc) return rc;
+    if (!obj->alpha_partial_sums) return EGS_ERR_ARG;
+    EgsPrologueArgs pa = {};
+    if (side) { rc = prologue_args(side, pa); if (rc) return rc; }
+    return egs_launch_l1_ssim_forward(channels, height, width, img, gt, lambda_dssim, partial_sums, dm_dmu1, dm_dexx, dm_dexy, loss, loss_running_sum,
+                                      side ? &pa : nullptr, (hipStream_t)stream, &ok);
+}
+
+int egs_object_loss_forward(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
+                            float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss, float* loss_running_sum,
+                            const egs_object_loss* obj, void* stream) {
+    return egs_object_loss_forward_ex(channels, height, width, img, gt, lambda_dssim, partial_sums, dm_dmu1, dm_dexx, dm_dexy, loss, loss_running_sum, obj,
+                                      nullptr, stream);
+}
+
+int egs_object_loss_backward_ex(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
+                                const float* upstream_grad, const float* gate, const float* dm_dmu1, const float* dm_dexx,
+                                const float* dm_dexy, float* dL_dimg, float* dL_dalpha, const float* deferred_partial_sums, float* deferred_loss,
+                                float* loss_running_sum, const egs_object_loss* obj, const egs_backward_prologue* side, void* stream) {
+    EgsObjLossK ok; int rc = obj_loss_args(obj, channels, height, width, lambda_dssim, ok); if (rc) return rc;
+    if (!dL_dalpha || (deferred_partial_sums && !obj->alpha_partial_sums)) return EGS_ERR_ARG;
+    EgsPrologueArgs pa = {};
+    if (side) { rc = prologue_args(side, pa); if (rc) return rc; }
+    // the image weights carry lambda_image; the value's own weights travel in `ok`
+    return egs_launch_l1_ssim_backward_w(channels, height, width, img, gt, obj->lambda_image * (1.f - lambda_dssim), obj->lambda_image * lambda_dssim, lambda_dssim,
+                                         upstream_grad, nullptr, gate, dm_dmu1, dm_dexx, dm_dexy, dL_dimg, deferred_partial_sums, deferred_loss,
+                                         loss_running_sum, side ? &pa : nullptr, (hipStream_t)stream, &ok, dL_dalpha);
+}
+
+int egs_backward_object_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
+                          const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, int width, int height, float tan_fovx, float tan_fovy, const int32_t* radii,
+                          const void* geom_buffer, const void* binning_buffer, const void* image_buffer, const egs_loss_grad* loss_grad,
+                          const egs_object_loss* obj,
+                          float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
+                          float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
+                          const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
+                          void* stream, int debug) {
+    if (!loss_grad || !obj) return EGS_ERR_ARG;
+    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
+                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
+                         binning_buffer, image_buffer, nullptr, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
+                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
+                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad, obj);
 }
 
 int egs_l1_ssim_pair_backward(int channels, int height, int width, const float* img, const float* gt, const float* upstream_l1,

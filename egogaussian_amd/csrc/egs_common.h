@@ -224,7 +224,8 @@ hipError_t egs_launch_backward_prologue(int P, int W, int H, EgsImgPtrs im, floa
 // fin_*: the loss VALUE the forward deferred (egs_l1_ssim_forward with loss == NULL) is assembled by one wave of the blend launch.
 struct EgsLossGradHost { const float* img; const float* gt; const float* dm_dmu1; const float* dm_dexx; const float* dm_dexy; const float* gate;
                          const float* upstream; const float* upstream_ssim; float w_l1_n, w_ssim_n;
-                         const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running; };
+                         const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
+                         const struct EgsObjLossK* obj; };      // obj (may be NULL; loss_window.h): the object stages' loss -- the blend also forms dL/dalpha (k_render_backward<2, true>)
 #ifdef EGS_LG_CHECK
 extern EgsLossGradHost egs_debug_lossgrad;
 #endif

@@ -163,12 +163,14 @@ __device__ __forceinline__ unsigned loss_logical_block(unsigned b, unsigned main
 // grid: 8 * ceil(C * ceil(strips_x * strips_y / WPB) / 8) (1-D, see loss_logical_block); a wave = one strip
 // SIDE: the last `side_jobs` workgroups carry the preparation of the rasterizer's backward blend of the same frame (as k_l1_ssim_backward<true>
 // does) -- for a training step whose blend computes the loss gradient itself (render_bwd.hip, LG) and therefore has no loss-backward launch.
-template <bool SIDE>
+// OBJ (the object stages' loss, loss_window.h EgsObjLossK): the strips of plane 0 also add up |m - alpha| and (m - alpha)^2 over their own
+// pixels -- per lane down the rows, then across the lanes, one float2 per strip: a fixed order -- into the alpha terms' own partial array.
+template <bool SIDE, bool OBJ = false>
 __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_forward(int H, int W, int strips_x, int strips_y, const float* __restrict__ img,
                                                                const float* __restrict__ gt, float* __restrict__ partial,
                                                                float* __restrict__ dm_dmu1, float* __restrict__ dm_dexx,
                                                                float* __restrict__ dm_dexy, unsigned per_plane, unsigned main_wgs,
-                                                               unsigned side_jobs, EgsPrologueArgs side) {
+                                                               unsigned side_jobs, EgsPrologueArgs side, EgsObjLossK obj) {
     __shared__ v2f lds[WPB][2 * 80];
     if (SIDE) {
         __shared__ EgsOrderLds order_lds;
@@ -225,6 +227,22 @@ __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_forward(int H, int W, int 
     if (lane == 0) {
         const size_t b = (size_t)plane_z * strips_x * strips_y + strip;
         partial[2 * b] = l1; partial[2 * b + 1] = sm;
+    }
+    if (OBJ && plane_z == 0) {                                          // (wave-uniform)
+        // the strip's own SR x SW pixels of the alpha plane and the mask: every load issued before the first use (one memory latency)
+        float av[SR], mv[SR];
+#pragma unroll
+        for (int k = 0; k < SR; k++) {
+            const bool ok = c.col_out && c.y_first + k < c.y_end;
+            const unsigned p = ok ? (unsigned)(c.y_first + k) * (unsigned)W + (unsigned)c.gx : 0u;
+            av[k] = ok ? obj.alpha[p] : 0.f; mv[k] = ok ? obj.mask[p] : 0.f;
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < SR; k++) { const float dd = mv[k] - av[k]; s1 += fabsf(dd); s2 += dd * dd; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_xor(s1, d, 64); s2 += __shfl_xor(s2, d, 64); }
+        if (lane == 0) { obj.apartial[2 * strip] = s1; obj.apartial[2 * strip + 1] = s2; }
     }
 }
 
@@ -303,7 +321,9 @@ __device__ __forceinline__ void bwd_step(BwdCtx& c, Window<3>& w, int y_in, floa
 // dozen stores of its own instead was slower still, 23.3 us: the stores sit in front of the strip's first loads.)  They have nothing to do with the loss; they ride here because this launch sits between the two blends of a training
 // step and leaves most of the machine's issue slots and all of its HBM bandwidth unused, while a launch of their own costs 12 us.
 // grid: 1-D = per channel plane ceil(strips / WPB) strip workgroups (+ 1 for the deferred loss value), then the side jobs
-template <bool SIDE>
+// OBJ (the object stages' loss): the strips of plane 0 also write dL/dalpha of their own pixels (loss_window.h egs_alpha_grad); the deferred
+// value is the one with the alpha terms.
+template <bool SIDE, bool OBJ = false>
 __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_backward(int H, int W, int strips_x, int strips_y, const float* __restrict__ img,
                                                                 const float* __restrict__ gt, float w_l1, float w_ssim,
                                                                 const float* __restrict__ upstream, const float* __restrict__ upstream_ssim,
@@ -312,7 +332,8 @@ __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_backward(int H, int W, int
                                                                 const float* __restrict__ dm_dexy, float* __restrict__ dimg,
                                                                 const float* __restrict__ fin_partial, size_t fin_n, float fin_lambda,
                                                                 float* __restrict__ fin_loss, float* __restrict__ fin_running,
-                                                                unsigned per_plane, unsigned main_wgs, unsigned side_jobs, EgsPrologueArgs side) {
+                                                                unsigned per_plane, unsigned main_wgs, unsigned side_jobs, EgsPrologueArgs side,
+                                                                EgsObjLossK obj, float* __restrict__ dalpha) {
     __shared__ __attribute__((aligned(8))) float lds[WPB][3 * 80];      // per wave: [80] pairs (two maps), then [80] floats (the third)
     if (SIDE) {
         __shared__ EgsOrderLds order_lds;
@@ -324,7 +345,10 @@ __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_backward(int H, int W, int
     const unsigned plane_z = rel / per_plane, bx = rel - plane_z * per_plane;
     const int strip = (int)bx * WPB + (int)wv;
     if (fin_partial && bx == per_plane - 1) {                          // deferred loss value: one extra workgroup per channel plane, no strip
-        if (plane_z == 0 && wv == 0) wave_finish_loss(fin_n, fin_partial, w_l1, w_ssim, fin_lambda, fin_loss, fin_running, lane);
+        if (plane_z == 0 && wv == 0) {
+            if (OBJ) wave_finish_obj_loss(fin_n, fin_partial, fin_lambda, obj, fin_loss, fin_running, lane);
+            else wave_finish_loss(fin_n, fin_partial, w_l1, w_ssim, fin_lambda, fin_loss, fin_running, lane);
+        }
         return;                                                        // (every resident wave ends with the kernel: a wave with a strip has no slack)
     }
     if (strip >= strips_x * strips_y) return;
@@ -367,6 +391,20 @@ __global__ __launch_bounds__(64 * WPB) void k_l1_ssim_backward(int H, int W, int
 #undef BSTEP
         cur = nxt;
     }
+    if (OBJ && plane_z == 0) {                                          // (wave-uniform)
+        float av[SR], mv[SR], gv[SR];
+#pragma unroll
+        for (int k = 0; k < SR; k++) {
+            const bool ok = c.col_out && c.y_first + k < c.y_end;
+            const unsigned p = ok ? (unsigned)(c.y_first + k) * (unsigned)W + (unsigned)c.gx : 0u;
+            av[k] = ok ? obj.alpha[p] : 0.f; mv[k] = ok ? obj.mask[p] : 0.f; gv[k] = (ok && gate) ? gate[p] : 1.f;
+        }
+        const float up0 = upstream[0];                                  // (c.up is 1 when the two image terms carry an upstream scalar each)
+#pragma unroll
+        for (int k = 0; k < SR; k++)
+            if (c.col_out && c.y_first + k < c.y_end)
+                dalpha[(unsigned)(c.y_first + k) * (unsigned)W + (unsigned)c.gx] = egs_alpha_grad(av[k], mv[k], obj.w_l1a, obj.w_l2a2, up0, gate != nullptr, gv[k]);
+    }
 }
 
 // Adds up the per-block partial sums and assembles the scalar loss (one workgroup; deterministic order).
@@ -383,6 +421,29 @@ __global__ __launch_bounds__(1024) void k_l1_ssim_finish(size_t nblocks, const f
         float ta = 0.f, tb = 0.f;
         for (int k = 0; k < 16; k++) { ta += red[0][k]; tb += red[1][k]; }
         const float v = w_l1 * ta + lambda - w_ssim * tb;                     // (1-l) mean|x-y| + l (1 - mean SSIM)
+        loss[0] = v;
+        if (running_sum) running_sum[0] += v;
+    }
+}
+
+// k_l1_ssim_finish with the alpha terms of the object stages' loss: the image sums are added in k_l1_ssim_finish's order
+__global__ __launch_bounds__(1024) void k_obj_loss_finish(size_t nblocks, const float* __restrict__ partial, float lambda, EgsObjLossK o,
+                                                          float* __restrict__ loss, float* __restrict__ running_sum) {
+    __shared__ float red[4][16];
+    float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+    for (size_t i = threadIdx.x; i < nblocks; i += 1024) { const float2 v = reinterpret_cast<const float2*>(partial)[i]; a += v.x; b += v.y; }
+    for (unsigned i = threadIdx.x; i < o.n_astrips; i += 1024) { const float2 v = reinterpret_cast<const float2*>(o.apartial)[i]; c += v.x; d += v.y; }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) { a += __shfl_xor(a, s, 64); b += __shfl_xor(b, s, 64); c += __shfl_xor(c, s, 64); d += __shfl_xor(d, s, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; red[2][threadIdx.x >> 6] = c; red[3][threadIdx.x >> 6] = d; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ta = 0.f, tb = 0.f, tc = 0.f, td = 0.f;
+        for (int k = 0; k < 16; k++) { ta += red[0][k]; tb += red[1][k]; tc += red[2][k]; td += red[3][k]; }
+        const float img = o.fin_w_l1 * ta + lambda - o.fin_w_ssim * tb;
+        const float t1 = o.inv_hw * tc, t2 = o.inv_hw * td;
+        const float v = __fmaf_rn(o.l_l2a, t2, __fmaf_rn(o.l_l1a, t1, o.l_img * img));
+        if (o.terms) { o.terms[0] = img; o.terms[1] = t1; o.terms[2] = t2; }
         loss[0] = v;
         if (running_sum) running_sum[0] += v;
     }
@@ -410,10 +471,7 @@ __global__ __launch_bounds__(1024) void k_l1_ssim_finish_pair(size_t nblocks, co
 int egs_launch_l1_ssim_backward_w(int channels, int height, int width, const float* img, const float* gt, float w_l1_n, float w_ssim_n, float lambda_dssim,
                                 const float* upstream_grad, const float* upstream_ssim, const float* gate, const float* dm_dmu1, const float* dm_dexx,
                                 const float* dm_dexy, float* dL_dimg, const float* deferred_partial_sums, float* deferred_loss,
-                                float* loss_running_sum, const EgsPrologueArgs* side, hipStream_t stream);
-int egs_launch_l1_ssim_forward(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
-                               float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss, float* loss_running_sum,
-                               const EgsPrologueArgs* side, hipStream_t stream);
+                                float* loss_running_sum, const EgsPrologueArgs* side, hipStream_t stream, const EgsObjLossK* obj, float* dalpha);
 int egs_launch_l1_ssim_backward(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
                                 const float* upstream_grad, const float* gate, const float* dm_dmu1, const float* dm_dexx,
                                 const float* dm_dexy, float* dL_dimg, const float* deferred_partial_sums, float* deferred_loss,
@@ -425,9 +483,10 @@ int egs_launch_l1_ssim_backward(int channels, int height, int width, const float
 int egs_launch_l1_ssim_backward_w(int channels, int height, int width, const float* img, const float* gt, float w_l1_n, float w_ssim_n, float lambda_dssim,
                                 const float* upstream_grad, const float* upstream_ssim, const float* gate, const float* dm_dmu1, const float* dm_dexx,
                                 const float* dm_dexy, float* dL_dimg, const float* deferred_partial_sums, float* deferred_loss,
-                                float* loss_running_sum, const EgsPrologueArgs* side, hipStream_t stream) {
+                                float* loss_running_sum, const EgsPrologueArgs* side, hipStream_t stream, const EgsObjLossK* obj, float* dalpha) {
     if (channels <= 0 || height <= 0 || width <= 0 || !img || !gt || !upstream_grad || !dm_dmu1 || !dm_dexx || !dm_dexy || !dL_dimg)
         return EGS_ERR_ARG;
+    if (obj && (!dalpha || !obj->alpha || !obj->mask || upstream_ssim)) return EGS_ERR_ARG;
     const float n = (float)channels * (float)height * (float)width;
     const int strips_x = (width + SW - 1) / SW, strips_y = (height + SR - 1) / SR;
     const unsigned per_plane = (unsigned)((strips_x * strips_y + WPB - 1) / WPB + (deferred_partial_sums ? 1 : 0));
@@ -442,8 +501,11 @@ int egs_launch_l1_ssim_backward_w(int channels, int height, int width, const flo
 #define LB_ARGS height, width, strips_x, strips_y, img, gt, w_l1_n / n, w_ssim_n / n, upstream_grad, upstream_ssim, gate, dm_dmu1, dm_dexx, \
                 dm_dexy, dL_dimg, deferred_partial_sums, (size_t)strips_x * strips_y * channels, lambda_dssim, deferred_loss,            \
                 deferred_partial_sums ? loss_running_sum : nullptr, per_plane, main_wgs, side_jobs
-    if (side) hipLaunchKernelGGL(k_l1_ssim_backward<true>, dim3(side_jobs + main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, *side);
-    else hipLaunchKernelGGL(k_l1_ssim_backward<false>, dim3(main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, none);
+    const EgsObjLossK no_obj = {};
+    if (obj && side) hipLaunchKernelGGL((k_l1_ssim_backward<true, true>), dim3(side_jobs + main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, *side, *obj, dalpha);
+    else if (obj) hipLaunchKernelGGL((k_l1_ssim_backward<false, true>), dim3(main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, none, *obj, dalpha);
+    else if (side) hipLaunchKernelGGL(k_l1_ssim_backward<true>, dim3(side_jobs + main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, *side, no_obj, nullptr);
+    else hipLaunchKernelGGL(k_l1_ssim_backward<false>, dim3(main_pad), dim3(64 * WPB), 0, stream, LB_ARGS, none, no_obj, nullptr);
 #undef LB_ARGS
     return (int)hipGetLastError();
 }
@@ -469,9 +531,11 @@ int egs_l1_ssim_forward(int channels, int height, int width, const float* img, c
 
 int egs_launch_l1_ssim_forward(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
                                float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss, float* loss_running_sum,
-                               const EgsPrologueArgs* side, hipStream_t stream) {
+                               const EgsPrologueArgs* side, hipStream_t stream, const EgsObjLossK* obj) {
     if (channels <= 0 || height <= 0 || width <= 0 || !img || !gt || !partial_sums || !dm_dmu1 || !dm_dexx || !dm_dexy)
         return EGS_ERR_ARG;
+    if (obj && (!obj->alpha || !obj->mask || !obj->apartial)) return EGS_ERR_ARG;
+    const EgsObjLossK no_obj = {};
     const int strips_x = (width + SW - 1) / SW, strips_y = (height + SR - 1) / SR;
     const unsigned per_plane = (unsigned)((strips_x * strips_y + WPB - 1) / WPB), main_wgs = per_plane * (unsigned)channels;
     const unsigned main_pad = ((main_wgs + 7u) / 8u) * 8u;
@@ -480,13 +544,22 @@ int egs_launch_l1_ssim_forward(int channels, int height, int width, const float*
         // 124 VGPRs: eight 2-wave workgroups per CU, 2 048 resident slots; the zeroing workgroups take what the strips leave, 32 at least
         const unsigned spare = main_pad + EGS_XCDS + 1 + 32 <= 2048 ? 2048 - main_pad - EGS_XCDS - 1 : 32;
         const unsigned side_jobs = egs_prologue_jobs(side->n4, side->has_tick, 64 * WPB, spare);
+        if (obj) hipLaunchKernelGGL((k_l1_ssim_forward<true, true>), dim3(main_pad + side_jobs), dim3(64 * WPB), 0, stream, height, width, strips_x, strips_y, img, gt,
+                                    partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, side_jobs, *side, *obj);
+        else
         hipLaunchKernelGGL(k_l1_ssim_forward<true>, dim3(main_pad + side_jobs), dim3(64 * WPB), 0, stream, height, width, strips_x, strips_y, img, gt,
-                           partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, side_jobs, *side);
-    } else
+                           partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, side_jobs, *side, no_obj);
+    } else if (obj)
+    hipLaunchKernelGGL((k_l1_ssim_forward<false, true>), dim3(main_pad), dim3(64 * WPB), 0, stream, height, width, strips_x, strips_y, img, gt,
+                       partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, 0u, none, *obj);
+    else
     hipLaunchKernelGGL(k_l1_ssim_forward<false>, dim3(main_pad), dim3(64 * WPB), 0, stream, height, width, strips_x, strips_y, img, gt,
-                       partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, 0u, none);
+                       partial_sums, dm_dmu1, dm_dexx, dm_dexy, per_plane, main_wgs, 0u, none, no_obj);
     const float n = (float)channels * (float)height * (float)width;
-    if (loss)                                       // loss == NULL: the value is assembled by egs_l1_ssim_backward (deferred)
+    if (loss && obj)
+        hipLaunchKernelGGL(k_obj_loss_finish, dim3(1), dim3(1024), 0, stream, (size_t)strips_x * strips_y * channels, partial_sums, lambda_dssim, *obj, loss,
+                           loss_running_sum);
+    else if (loss)                                  // loss == NULL: the value is assembled by egs_l1_ssim_backward (deferred)
         hipLaunchKernelGGL(k_l1_ssim_finish, dim3(1), dim3(1024), 0, stream, (size_t)strips_x * strips_y * channels, partial_sums,
                            (1.f - lambda_dssim) / n, lambda_dssim / n, lambda_dssim, loss, loss_running_sum);
     return (int)hipGetLastError();

@@ -70,12 +70,16 @@ __global__ __launch_bounds__(1024) void k_backward_prologue(EgsPrologueArgs a) {
 // so that the training step needs no loss-backward launch at all.  Threads 0..233 = (channel, map, window column): each loads its column of
 // the tile's 26-row window and leaves 16 vertically blurred values in LDS ([channel][map][16][27] floats, 15.2 KiB, in the space the loop
 // below uses for the staged records and the reduction); after ONE barrier every lane blurs horizontally at its own pixel.
+// <2, true> (the object stages' loss, image + alpha against the object mask): the prologue also forms dL/dalpha of the lane's pixel from the alpha
+// plane the forward wrote and the mask -- loss_window.h egs_alpha_grad, the function the loss-backward launch uses: bit-identical -- and dL/ddepth
+// stays 0; the blend is MODE 2's.
 #ifdef EGS_LG_CHECK
 __device__ unsigned egs_lg_mismatch;
 #endif
 struct EgsLossGrad { const float* img; const float* gt; const float* m0; const float* m1; const float* m2; const float* gate;
                      const float* up; const float* up_ssim; float w_l1, w_ssim;
-                     const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running; };
+                     const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
+                     EgsObjLossK obj; };              // (read by <2, true> only) the object stages' loss: the alpha plane the forward wrote, the mask, the alpha weights
 #define LG_COLS 27
 template <int MODE, bool LG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_render_backward(
@@ -124,7 +128,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     float lg_r = 0.f, lg_g = 0.f, lg_b = 0.f;
     if (LG) {
         // the loss value the forward deferred: one wave of the launch adds up the per-strip partial sums (loss_window.h), as k_l1_ssim_backward did
-        if (lg.fin_partial && blockIdx.x == 0 && wv == 0) wave_finish_loss(lg.fin_n, lg.fin_partial, lg.w_l1, lg.w_ssim, lg.fin_lambda, lg.fin_loss, lg.fin_running, lane);
+        if (lg.fin_partial && blockIdx.x == 0 && wv == 0) {
+            if (HAS_DA) wave_finish_obj_loss(lg.fin_n, lg.fin_partial, lg.fin_lambda, lg.obj, lg.fin_loss, lg.fin_running, lane);
+            else wave_finish_loss(lg.fin_n, lg.fin_partial, lg.w_l1, lg.w_ssim, lg.fin_lambda, lg.fin_loss, lg.fin_running, lane);
+        }
         const int tx0 = (tile % gx) * EGS_TILE, ty0 = (tile / gx) * EGS_TILE;
         float* vb = reinterpret_cast<float*>(smem);                  // [9][16][LG_COLS]
         const size_t HWp = (size_t)H * W;
@@ -202,8 +209,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (LG && (__float_as_uint(lg_r) != __float_as_uint(dL_dcolor[pix]) || __float_as_uint(lg_g) != __float_as_uint(dL_dcolor[HW + pix]) ||
                    __float_as_uint(lg_b) != __float_as_uint(dL_dcolor[2 * HW + pix]))) atomicAdd(&egs_lg_mismatch, 1u);
 #endif
-        if (HAS_DA && dL_ddepth) g_d = dL_ddepth[pix];
-        if (HAS_DA && dL_dalpha) g_a = dL_dalpha[pix];
+        if (HAS_DA && !LG && dL_ddepth) g_d = dL_ddepth[pix];
+        if (HAS_DA && !LG && dL_dalpha) g_a = dL_dalpha[pix];
+        // (formed here, not in the prologue above: one more value alive across its 26-row window spilled four registers)
+        if (HAS_DA && LG) g_a = egs_alpha_grad(lg.obj.alpha[pix], lg.obj.mask[pix], lg.obj.w_l1a, lg.obj.w_l2a2, lg.up[0], lg.gate != nullptr,
+                                               lg.gate ? lg.gate[pix] : 1.f);
     }
     const float bg_term = MODE == 0 ? 0.f : -T_final * (bg[0] * g_r + bg[1] * g_g + bg[2] * g_b);
     uint32_t wmax = last;
@@ -345,10 +355,15 @@ namespace {
 __global__ __launch_bounds__(64) void k_loss_finish(size_t n, const float* __restrict__ partial, float w_l1, float w_ssim, float lambda, float* loss, float* running) {
     wave_finish_loss(n, partial, w_l1, w_ssim, lambda, loss, running, threadIdx.x);
 }
+__global__ __launch_bounds__(64) void k_obj_loss_finish_wave(size_t n, const float* __restrict__ partial, float lambda, EgsObjLossK o, float* loss, float* running) {
+    wave_finish_obj_loss(n, partial, lambda, o, loss, running, threadIdx.x);
+}
 }  // namespace
 hipError_t egs_launch_loss_finish(const EgsLossGradHost& lg, int W, int H, hipStream_t s) {
     if (!lg.fin_partial) return hipSuccess;
     const float n = (float)W * (float)H * 3.f;
+    if (lg.obj) hipLaunchKernelGGL(k_obj_loss_finish_wave, dim3(1), dim3(64), 0, s, lg.fin_n, lg.fin_partial, lg.fin_lambda, *lg.obj, lg.fin_loss, lg.fin_running);
+    else
     hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, s, lg.fin_n, lg.fin_partial, lg.w_l1_n / n, lg.w_ssim_n / n, lg.fin_lambda, lg.fin_loss, lg.fin_running);
     return hipGetLastError();
 }
@@ -383,11 +398,13 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
     EgsLossGrad lgk = {};
     if (lg) { lgk.img = lg->img; lgk.gt = lg->gt; lgk.m0 = lg->dm_dmu1; lgk.m1 = lg->dm_dexx; lgk.m2 = lg->dm_dexy; lgk.gate = lg->gate;
               lgk.up = lg->upstream; lgk.up_ssim = lg->upstream_ssim; lgk.w_l1 = lg->w_l1_n / ((float)W * (float)H * 3.f); lgk.w_ssim = lg->w_ssim_n / ((float)W * (float)H * 3.f);
-              lgk.fin_partial = lg->fin_partial; lgk.fin_n = lg->fin_n; lgk.fin_lambda = lg->fin_lambda; lgk.fin_loss = lg->fin_loss; lgk.fin_running = lg->fin_running; }
+              lgk.fin_partial = lg->fin_partial; lgk.fin_n = lg->fin_n; lgk.fin_lambda = lg->fin_lambda; lgk.fin_loss = lg->fin_loss; lgk.fin_running = lg->fin_running;
+              if (lg->obj) lgk.obj = *lg->obj; }
 #define EGS_BWD_LAUNCH(MODE, LGF) hipLaunchKernelGGL((k_render_backward<MODE, LGF>), dim3(egs_blocks_for_tiles(n_tiles)), dim3(256), 0, s, W, H, gx, n_tiles, \
                            im.ranges, point_list, g.rec, bg, im.final_T, im.n_contrib, dL_dcolor, dL_ddepth, dL_dalpha, \
                            im.tile_order, grad_acc, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * EGS_GRAD_STRIDE), (uint32_t)egs_hot_slots((size_t)P), lgk)
     if (colors_only) EGS_BWD_LAUNCH(0, false);
+    else if (lg && lg->obj) EGS_BWD_LAUNCH(2, true);                 // (dL_ddepth, dL_dalpha are not read: the prologue forms dL/dalpha, dL/ddepth is 0)
     else if (dL_ddepth || dL_dalpha) EGS_BWD_LAUNCH(2, false);
     else if (lg) EGS_BWD_LAUNCH(1, true);
     else EGS_BWD_LAUNCH(1, false);

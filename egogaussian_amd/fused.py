@@ -328,3 +328,114 @@ def l1_ssim_loss(image, gt, lambda_dssim=0.2, grad_gate=None, running_sum=None, 
         if fn is not None and getattr(fn, "egs_raster_node", False):
             node = fn
     return _L1SSIM.apply(image, gt, lambda_dssim, grad_gate, running_sum, defer_value, node, bool(raster_lossgrad and node is not None))
+
+
+class _ObjectLoss(torch.autograd.Function):
+    """The object stages' loss on (image, alpha): include/egs_raster.h egs_object_loss_forward[_ex] / egs_object_loss_backward_ex /
+    egs_backward_object_lossgrad.  Two differentiable inputs, one forward launch, at most one backward launch."""
+
+    @staticmethod
+    def forward(ctx, img, alpha, gtm, mask, lambda_dssim, weights, gate, running_sum, terms, defer_value, raster_node, lossgrad):
+        L = _lib.load()
+        img, gtm = _need_hip(img, "image"), _need_hip(gtm, "gt")
+        a, mask = _need_hip(alpha, "alpha"), _need_hip(mask, "obj_mask")
+        assert img.dim() == 3 and img.shape == gtm.shape
+        Cc, H, W = img.shape
+        if a.numel() != H * W or mask.numel() != H * W:
+            raise RuntimeError("object_stage_loss: alpha and obj_mask hold one value per pixel of the image ([1,H,W] or [H,W])")
+        dev = img.device
+        partial = torch.empty(L.egs_l1_ssim_partial_count(Cc, H, W) + L.egs_l1_ssim_partial_count(1, H, W), device=dev)
+        apartial = partial[L.egs_l1_ssim_partial_count(Cc, H, W):]
+        maps = torch.empty((3, Cc, H, W), device=dev)
+        loss = torch.empty((), device=dev)
+        ob = _lib.ObjectLoss()
+        ob.alpha, ob.obj_mask, ob.alpha_partial_sums = a.data_ptr(), mask.data_ptr(), apartial.data_ptr()
+        ob.lambda_image, ob.lambda_l1_alpha, ob.lambda_l2_alpha = float(weights[0]), float(weights[1]), float(weights[2])
+        ob.terms = None if terms is None else terms.data_ptr()
+        side = None
+        if lossgrad and raster_node is not None and Cc == 3:
+            # as _L1SSIM: the blend will compute BOTH gradients itself; what the loss backward launch carried for it rides in this forward
+            from .rasterizer import backward_prologue_of
+            side = backward_prologue_of(raster_node)
+        with _hip.device_ctx(dev):
+            _lib.check(L.egs_object_loss_forward_ex(Cc, H, W, _p(img), _p(gtm), float(lambda_dssim), _p(partial), _p(maps[0]), _p(maps[1]), _p(maps[2]),
+                                                    None if defer_value else _p(loss), None if defer_value else _p(running_sum), C.byref(ob),
+                                                    C.byref(side) if side is not None else None, _stream(dev)))
+        ctx.lossgrad = side is not None
+        ctx.save_for_backward(img, gtm, maps, a, mask, gate if gate is not None else torch.empty(0))
+        ctx.lam, ctx.has_gate, ctx.ob, ctx.alpha_shape = float(lambda_dssim), gate is not None, ob, alpha.shape
+        ctx.keep = (partial, terms)
+        ctx.deferred = (partial, loss, running_sum) if defer_value else None
+        ctx.raster_node = raster_node
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.load()
+        img, gtm, maps, a, mask, gate = ctx.saved_tensors
+        gate = gate.float().contiguous() if ctx.has_gate else None
+        Cc, H, W = img.shape
+        g = g.reshape(1)
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        dimg = torch.empty_like(img)
+        dalpha = torch.empty(ctx.alpha_shape, device=img.device, dtype=torch.float32)
+        d = ctx.deferred
+        none = (None,) * 10
+        if ctx.lossgrad:
+            # no launch: the rasterizer backward that follows forms dL/dimage AND dL/dalpha inside its blend kernel (bit-identical to the
+            # launch below).  Both tensors go back uninitialised and unread; the rasterizer recognises each by address and version.
+            lg = _lib.LossGrad()
+            lg.image, lg.gt, lg.dm_dmu1, lg.dm_dexx, lg.dm_dexy = img.data_ptr(), gtm.data_ptr(), maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr()
+            lg.gate = gate.data_ptr() if gate is not None else None
+            lg.upstream_grad, lg.lambda_dssim = g.data_ptr(), ctx.lam
+            if d:
+                lg.deferred_partial_sums, lg.deferred_loss = d[0].data_ptr(), d[1].data_ptr()
+                lg.loss_running_sum = d[2].data_ptr() if d[2] is not None else None
+            ctx.raster_node.loss_grad = (lg, (img, gtm, maps, gate, g, d, a, mask, ctx.keep), (dimg.data_ptr(), dimg._version), ctx.ob,
+                                         (dalpha.data_ptr(), dalpha._version))
+            return (dimg, dalpha) + none
+        side = None
+        if ctx.raster_node is not None:
+            from .rasterizer import backward_prologue_of
+            side = backward_prologue_of(ctx.raster_node)
+        with _hip.device_ctx(img.device):
+            _lib.check(L.egs_object_loss_backward_ex(Cc, H, W, _p(img), _p(gtm), ctx.lam, _p(g), _p(gate), _p(maps[0]), _p(maps[1]), _p(maps[2]),
+                                                     _p(dimg), _p(dalpha), _p(d[0]) if d else None, _p(d[1]) if d else None, _p(d[2]) if d else None,
+                                                     C.byref(ctx.ob), C.byref(side) if side is not None else None, _stream(img.device)))
+        return (dimg, dalpha) + none
+
+
+def object_stage_loss(image, alpha, gt, obj_mask, lambda_dssim=0.2, lambda_image=1.0, lambda_l1_alpha=0.0, lambda_l2_alpha=0.5, grad_gate=None,
+                      running_sum=None, terms=None, defer_value=False, raster_prologue=False, raster_lossgrad=False, gt_premasked=False):
+    """The loss of the stages that recover the object's motion (losses.object_stage_loss is its torch mirror;
+    /root/reference/trainers/coarse_obj_pose.py:239-260, trainers/fine_obj.py:128-151):
+        lambda_image * [(1 - lambda) L1 + lambda (1 - SSIM)](image, gt * obj_mask) + lambda_l1_alpha * mean|obj_mask - alpha|
+            + lambda_l2_alpha * mean (obj_mask - alpha)^2
+    One autograd node with two differentiable inputs, `image` [3,H,W] and `alpha` ([1,H,W] as the rasterizer returns it, or [H,W]): one
+    HIP launch forward, one backward -- instead of the image loss plus five torch launches each way for the alpha terms.
+    grad_gate [H,W] multiplies BOTH gradients per pixel: it replaces the reference's two hooks, `grad * (1 - hand_mask)` on the image and
+    on alpha.  gt_premasked=True: `gt` already is gt * obj_mask (graph.pack_frame stores it so) -- no multiply here.
+    terms: optional device float32[3] that receives (image loss, mean|m - alpha|, mean (m - alpha)^2), unweighted, whenever the value
+    is assembled -- what the trainers log.  running_sum / defer_value / raster_prologue: as l1_ssim_loss.
+    raster_lossgrad=True (image AND alpha straight from one rasterizer call, three channels, a backward that is sure to follow): no
+    backward launch; the rasterizer's backward blend forms both gradients itself, bit-identical to that launch.  Both gradient tensors
+    autograd hands on are uninitialised memory; the rasterizer's backward recognises each and refuses (RuntimeError) when the image
+    or alpha has a second consumer or a hook that replaced the gradient, or when the depth output received a gradient.
+    With both alpha weights 0 and lambda_image 1 the value and the image gradient are l1_ssim_loss's, bit for bit."""
+    if running_sum is not None:
+        running_sum = _need_hip(running_sum, "running_sum")
+    if terms is not None and not (terms.is_cuda and terms.dtype == torch.float32 and terms.numel() == 3 and terms.is_contiguous()):
+        raise RuntimeError("object_stage_loss: `terms` is a contiguous float32[3] tensor on the image's device")
+    mask = obj_mask.detach()
+    if mask.dtype != torch.float32:
+        mask = mask.float()
+    gtm = gt if gt_premasked else gt * mask
+    node = None
+    if raster_prologue:
+        fn = image.grad_fn
+        if fn is not None and getattr(fn, "egs_raster_node", False):
+            node = fn
+    lossgrad = bool(raster_lossgrad and node is not None and alpha.grad_fn is node)
+    return _ObjectLoss.apply(image, alpha, gtm, mask, lambda_dssim, (lambda_image, lambda_l1_alpha, lambda_l2_alpha), grad_gate, running_sum, terms,
+                             defer_value, node, lossgrad)

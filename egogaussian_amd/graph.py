@@ -19,13 +19,14 @@ What is baked into the captured launches and therefore needs `recapture()` when 
 (densification and pruning of a plain model replace them; a capacity.CapacityGaussians model keeps them, and its live row
 count is a device word the kernels read), the image size, `pc.active_sh_degree` (the reference raises it every 1000
 iterations, scene/gaussian_model.py:176-178), the background tensor's address, `lambda_dssim`.  What does not: camera,
-ground truth, accum_R and gate contents (copied in per call) and the learning rates (device scalars; `__call__` pushes
+ground truth, accum_R / accum_T, gate and object-mask contents (copied in per call), the VALUES of a trainable pose's two parameters
+(pose=: they are tensors of the captured step like the model's) and the learning rates (device scalars; `__call__` pushes
 host-side edits of `param_groups[i]["lr"]` -- the reference's per-iteration `update_learning_rate` -- before each replay).
 """
 import torch
 
 from . import _C
-from .fused import l1_ssim_loss
+from .fused import l1_ssim_loss, object_stage_loss
 from .renderer import render
 from .scene_synth import Pipe
 
@@ -35,8 +36,9 @@ def pack_camera(cam):
     return torch.cat([cam.world_view_transform.reshape(-1), cam.full_proj_transform.reshape(-1), cam.camera_center.reshape(-1)]).float()
 
 
-def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False):
-    """Float offsets of the segments of a packed frame (each starts on a 16-byte boundary): -> ({name: (begin, end)}, size)."""
+def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_loss=False):
+    """Float offsets of the segments of a packed frame (each starts on a 16-byte boundary): -> ({name: (begin, end)}, size).
+    object_loss: an `obj_mask` segment of n_pix floats follows everything else (the other segments keep their offsets)."""
     up4 = lambda x: (x + 3) & ~3
     off = {"gt": (0, n_img)}
     end = up4(n_img)
@@ -47,16 +49,24 @@ def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False):
         off["accum_T"] = (end, end + 12); end = up4(end + 12)      # the object's accumulated pose as A12 = [A | b], row-major 3x4
     if gated:
         off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
+    if object_loss:
+        off["obj_mask"] = (end, end + n_pix); end = up4(end + n_pix)
     return off, end
 
 
-def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None):
+def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
     """One resident tensor per training frame: the ground-truth image, the camera block and -- for a step captured with
     dynamic=True / gated=True -- the object's accumulated rotation (3x3) and the per-pixel gradient gate (1 - hand mask, [H,W]).
     accum_T (a step captured with motion=True): the object's accumulated pose, 4x4 or 3x4 -- its first three rows travel as 12 floats.
+    obj_mask (a step captured with object_loss=): the object mask [H,W] or [1,H,W]; the frame then stores gt * obj_mask -- the image the object
+    stages compare against -- and the mask.
     GraphedTrainStep(frame) then refreshes every static input of the captured step with ONE device copy."""
-    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None)
+    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None, obj_mask is not None)
     f = torch.zeros(size, device=gt.device, dtype=torch.float32)
+    if obj_mask is not None:
+        m = obj_mask.to(gt.device, torch.float32).reshape(gt.shape[-2], gt.shape[-1])
+        f[off["obj_mask"][0]:off["obj_mask"][1]] = m.reshape(-1)
+        gt = gt * m
     f[off["gt"][0]:off["gt"][1]] = gt.reshape(-1)
     f[off["cam"][0]:off["cam"][1]] = pack_camera(cam).to(gt.device)
     if accum_R is not None:
@@ -99,7 +109,7 @@ class _StaticCamera:
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
-                 motion=False):
+                 motion=False, object_loss=None, pose=None):
         """densify_stats: the captured step also keeps the per-iteration densification statistics (trainers/train_static.py:125-127:
                        max_radii2D, xyz_gradient_accum, denom) -- updated by the rasterizer's backward itself, no launch of their own.
         dynamic:       the `fine_all` call shape (/root/reference/trainers/fine_all.py:88-93): render(..., rot_cov=True,
@@ -107,8 +117,18 @@ class GraphedTrainStep:
         motion:        (with dynamic) the real `fine_all` step: the object's Gaussians are also PLACED by the frame's accumulated pose
                        (<static 3x4 accum_T, refreshed per call like accum_R>) inside the rasterizer -- render(..., object_motion=) --
                        instead of by apply_trans_rot_new / reverse_trans_rot_new around the render (fine_all.py:88-116), which would
-                       re-seat `_xyz` every iteration and could not be captured.  The pose is a constant of the captured step; a
-                       trainable pose inside a captured step is not supported.
+                       re-seat `_xyz` every iteration and could not be captured.  Without `pose` the pose is a constant of the captured step.
+        pose:          (with motion) the trainable pose of the object stages ON TOP of the frame's accumulated one: a module with
+                       `obj_translation`, `obj_rotation_6d` and `rot_L` (the reference's ObjectMove, utils/geometry_utils.py:14-33;
+                       coarse_obj_pose.py, fine_obj.py).  The captured step composes motion.ObjectMotion(accum_T, pose, accum_R) from the
+                       static buffers (a few tiny torch launches), the rasterizer returns dL/dA12 and dL/dM9, autograd carries them to the
+                       two parameters, and `optimizer.step()` inside the capture steps them: they must be ordinary groups of the SAME
+                       FusedAdam(capturable=True).  Their learning rates are device scalars like every other group's: zeroing or restoring
+                       groups' "lr" (the stages' zero_gaussians_lr / zero_pose_lr / load_lrs) needs no re-capture.
+        object_loss:   dict(lambda_image=, lambda_l1_alpha=, lambda_l2_alpha=): the object stages' loss (fused.object_stage_loss) instead of
+                       the image loss -- the render composites alpha, the frame carries an `obj_mask` segment and stores gt * obj_mask
+                       (pack_frame(obj_mask=)), the gate (gated=True) applies to the image's AND alpha's gradient.  `self.loss_terms`
+                       (device float32[3]) holds the last step's image loss, mean|m - alpha| and mean (m - alpha)^2.
         gated:         the image gradient is multiplied by a per-pixel gate refreshed per call -- the reference's
                        `render_image.register_hook(lambda grad: grad * (1 - hand_mask))` (train_static.py:91, fine_all.py:94).
         check_every:   K > 0: every K calls read the overflow maximum (one host synchronisation) and re-capture with a larger
@@ -141,6 +161,18 @@ class GraphedTrainStep:
         self.motion = bool(motion)
         if self.motion and not self.dynamic:
             raise ValueError("GraphedTrainStep(motion=True) goes with dynamic=True (the pose's rotation turns the covariances)")
+        self.pose = pose
+        if pose is not None:
+            if not self.motion:
+                raise ValueError("GraphedTrainStep(pose=) goes with dynamic=True, motion=True (the trainable pose sits on top of the frame's)")
+            owned = {id(p) for g in optimizer.param_groups for p in g["params"]}
+            if id(pose.obj_translation) not in owned or id(pose.obj_rotation_6d) not in owned:
+                raise ValueError("GraphedTrainStep(pose=): obj_translation and obj_rotation_6d must be parameter groups of the optimizer "
+                                 "given (its step() inside the capture is what moves them)")
+        self.object_loss = None if object_loss is None else dict(object_loss)
+        if self.object_loss is not None and set(self.object_loss) - {"lambda_image", "lambda_l1_alpha", "lambda_l2_alpha"}:
+            raise ValueError("GraphedTrainStep(object_loss=): a dict of lambda_image, lambda_l1_alpha, lambda_l2_alpha")
+        self.loss_terms = None
         self.render_kwargs = dict(render_kwargs or {})
         self.check_every = int(check_every)
         self.steps_per_replay = max(1, int(steps_per_replay))
@@ -155,8 +187,12 @@ class GraphedTrainStep:
     def _dynamic_kwargs(self, f):
         kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=self.which_object, during_training=False)
         if self.motion:
-            from .motion import ComposedMotion
-            kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
+            from .motion import ComposedMotion, ObjectMotion
+            if self.pose is not None:
+                # composed INSIDE the capture from the static buffers and the two parameters: autograd carries dL/dA12, dL/dM9 back to them
+                kw["object_motion"] = ObjectMotion(f["accum_T"], self.pose, f["accum_R"])
+            else:
+                kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
         return kw
 
     def _body(self, k=0):
@@ -166,23 +202,33 @@ class GraphedTrainStep:
         if self.dynamic:
             kw.update(self._dynamic_kwargs(f))
         out = render(f["cam"], self.pc, self.pipe, self.bg, fused_densify_stats=self.densify_stats, guard=self.guard,
-                     optimizer=self.opt if self.fuse_optimizer else None, color_only=True, **kw)      # (the loss reads the colour image only)
+                     optimizer=self.opt if self.fuse_optimizer else None, color_only=self.object_loss is None, **kw)      # (the image loss reads the colour image only)
         # the loss value and the running sum are produced by the loss BACKWARD kernel (nothing reads them before): two launches less
-        loss = l1_ssim_loss(out["render"], f["gt"], self.lam, grad_gate=f["gate"] if self.gated else None, running_sum=self.loss_sum,
-                            defer_value=True, raster_prologue=True, raster_lossgrad=self.loss_grad_in_blend)
+        if self.object_loss is not None:
+            loss = object_stage_loss(out["render"], out["alpha"], f["gt"], f["obj_mask"], self.lam, grad_gate=f["gate"] if self.gated else None,
+                                     running_sum=self.loss_sum, terms=self.loss_terms, defer_value=True, raster_prologue=True,
+                                     raster_lossgrad=self.loss_grad_in_blend, gt_premasked=True, **self.object_loss)
+        else:
+            loss = l1_ssim_loss(out["render"], f["gt"], self.lam, grad_gate=f["gate"] if self.gated else None, running_sum=self.loss_sum,
+                                defer_value=True, raster_prologue=True, raster_lossgrad=self.loss_grad_in_blend)
         loss.backward(gradient=self._one)                            # a resident 1.0: no fill kernel per iteration
         self.opt.step()                                              # whatever the backward did not step itself (fuse_optimizer)
         return loss.detach(), out
 
     def _frame_layout(self, gt):
-        return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion)
+        return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion, self.object_loss is not None)
 
-    def capture(self, cam, gt, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None):
+    def capture(self, cam, gt, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
+                obj_mask=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
         more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
-        capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow)."""
+        capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow).
+        obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask."""
         dev = gt.device
+        if self.object_loss is not None and obj_mask is not None:
+            obj_mask = obj_mask.to(dev, torch.float32).reshape(gt.shape[-2], gt.shape[-1])
+            gt = gt * obj_mask
         if isinstance(cam, _StaticCamera):                           # recapture: keep the static buffers
             if gt is not self.gt:
                 self.gt.copy_(gt)
@@ -193,8 +239,11 @@ class GraphedTrainStep:
             self._slots = []
             for k in range(self.steps_per_replay):
                 fr = self._frames[k]
-                slot = {"gt": fr[off["gt"][0]:off["gt"][1]].view(gt.shape), "accum_R": None, "gate": None, "accum_T": None}
+                slot = {"gt": fr[off["gt"][0]:off["gt"][1]].view(gt.shape), "accum_R": None, "gate": None, "accum_T": None, "obj_mask": None}
                 slot["gt"].copy_(gt)
+                if self.object_loss is not None:
+                    slot["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(gt.shape[-2], gt.shape[-1])
+                    slot["obj_mask"].copy_(torch.ones(gt.shape[-2:], device=dev) if obj_mask is None else obj_mask)
                 slot["cam"] = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
                 if self.dynamic:
                     slot["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
@@ -210,9 +259,12 @@ class GraphedTrainStep:
             first = self._slots[0]                                   # (the single-iteration names)
             self.gt, self.cam, self.accum_R, self.gate = first["gt"], first["cam"], first["accum_R"], first["gate"]
             self.accum_T = first["accum_T"]
+            self.obj_mask = first["obj_mask"]
         self._one = torch.ones((), device=dev)
         if getattr(self, "loss_sum", None) is None:
             self.loss_sum = torch.zeros((), device=dev)                  # sum of the losses of every iteration run through this object
+        if self.object_loss is not None and self.loss_terms is None:
+            self.loss_terms = torch.zeros(3, device=dev)
         self.guard = _C.StepGuard(dev)
         self.opt.guard = self.guard                                  # the Adam launch of an overflowed frame does nothing
         side = torch.cuda.Stream(device=dev)
@@ -273,7 +325,9 @@ class GraphedTrainStep:
             slots2 = []
             for k in range(self.steps_per_replay):
                 fr, src = frames2[k], self._slots[k]
-                sl = {"gt": fr[off["gt"][0]:off["gt"][1]].view(src["gt"].shape), "accum_R": None, "gate": None, "accum_T": None}
+                sl = {"gt": fr[off["gt"][0]:off["gt"][1]].view(src["gt"].shape), "accum_R": None, "gate": None, "accum_T": None, "obj_mask": None}
+                if self.object_loss is not None:
+                    sl["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(src["gt"].shape[-2], src["gt"].shape[-1])
                 sl["cam"] = _StaticCamera(src["cam"], storage=fr[off["cam"][0]:off["cam"][1]])
                 if self.dynamic:
                     sl["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
@@ -319,7 +373,7 @@ class GraphedTrainStep:
         self._sets = None
         return self.capture(cam, gt, warmup=warmup, capacity_margin=capacity_margin, capacity_cams=capacity_cams)
 
-    def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None, accum_T=None):
+    def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None):
         """One training iteration (steps_per_replay of them): copy inputs in, replay.  Returns the (device, static) loss tensor of
         the last iteration (`self.losses` has all).  Either (camera, ground-truth image[, accum_R][, gate]) or packed frames from
         pack_frame(): one for a single-iteration step, a [S, frame] tensor (one copy) or a list of S for steps_per_replay = S.
@@ -338,7 +392,11 @@ class GraphedTrainStep:
             if self.steps_per_replay != 1:
                 raise ValueError("steps_per_replay > 1 takes packed frames")
             self.cam.load(cam)
-            self.gt.copy_(gt, non_blocking=True)
+            if self.object_loss is not None and obj_mask is not None:
+                self.obj_mask.copy_(obj_mask.reshape(self.obj_mask.shape), non_blocking=True)
+                torch.mul(gt, self.obj_mask, out=self.gt)                # (object_loss=: the static image is gt * obj_mask)
+            else:
+                self.gt.copy_(gt, non_blocking=True)
             if self.dynamic and accum_R is not None:
                 self.accum_R.copy_(accum_R, non_blocking=True)
             if self.motion and accum_T is not None:

@@ -67,6 +67,11 @@ class LossGrad(C.Structure):                     # egs_loss_grad
                 ("deferred_loss", C.c_void_p), ("loss_running_sum", C.c_void_p)]
 
 
+class ObjectLoss(C.Structure):                   # egs_object_loss
+    _fields_ = [("alpha", C.c_void_p), ("obj_mask", C.c_void_p), ("lambda_image", C.c_float), ("lambda_l1_alpha", C.c_float),
+                ("lambda_l2_alpha", C.c_float), ("alpha_partial_sums", C.c_void_p), ("terms", C.c_void_p)]
+
+
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
 # name -> (restype, argtypes); every symbol include/egs_raster.h declares
@@ -115,6 +120,13 @@ SIGNATURES = {
     "egs_backward_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
                                         vp, vp, vp, vp, C.POINTER(LossGrad), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                         C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_object_loss_forward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss), vp]),
+    "egs_object_loss_forward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss), C.POINTER(BackwardPrologue), vp]),
+    "egs_object_loss_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss),
+                                              C.POINTER(BackwardPrologue), vp]),
+    "egs_backward_object_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
+                                               vp, vp, vp, vp, C.POINTER(LossGrad), C.POINTER(ObjectLoss), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
     "egs_adam_step": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "egs_adam_workgroups": (C.c_int64, [i64]),
     "egs_adam_step_capturable": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]),

@@ -54,3 +54,18 @@ def psnr(img1, img2):
 def training_loss(image, gt, lambda_dssim=0.2):
     """(1 - lambda) L1 + lambda (1 - SSIM), /root/reference/trainers/train_static.py:92-95, arguments/__init__.py:83."""
     return (1.0 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1.0 - ssim(image, gt))
+
+
+def object_stage_loss(image, alpha, gt, obj_mask, lambda_dssim, lambda_image=1.0, lambda_l1_alpha=0.0, lambda_l2_alpha=0.5):
+    """The loss of the stages that recover the object's motion (/root/reference/trainers/coarse_obj_pose.py:239-260,
+    trainers/fine_obj.py:128-151):
+        lambda_image * [(1 - lambda) L1 + lambda (1 - SSIM)](gt * obj_mask, image) + lambda_l1_alpha * L1(obj_mask, alpha)
+            + lambda_l2_alpha * L2(obj_mask, alpha)
+    `gt` is the frame as loaded: it is multiplied by the mask HERE.  alpha, obj_mask: [1,H,W] or [H,W].  The hand-mask hooks of the
+    reference (grad * (1 - hand_mask) on the image and on alpha) are the caller's; fused.object_stage_loss takes them as grad_gate.
+    The oracle of the HIP kernels behind fused.object_stage_loss, on any device and in any float type."""
+    m = obj_mask.to(image.dtype)
+    gtm = gt * m
+    img = (1.0 - lambda_dssim) * l1_loss(gtm, image) + lambda_dssim * (1.0 - ssim(gtm, image))
+    a = alpha.reshape(m.shape)
+    return lambda_image * img + lambda_l1_alpha * l1_loss(m, a) + lambda_l2_alpha * l2_loss(m, a)

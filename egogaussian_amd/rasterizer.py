@@ -120,6 +120,18 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise RuntimeError("l1_ssim_loss(raster_lossgrad=True): the rendered image has another gradient contribution (a second consumer, or a "
                                    "hook that changed the gradient) -- the in-blend loss gradient would drop it.  Use raster_lossgrad=False "
                                    "(GraphedTrainStep(loss_grad_in_blend=False)), or express a per-pixel mask as grad_gate=")
+            if len(ctx.loss_grad) > 3:
+                # fused.object_stage_loss(raster_lossgrad=True): the blend forms dL/dalpha as well and dL/ddepth is 0 -- the same rule for alpha,
+                # and nothing at all may have reached the depth output
+                ptr, version = ctx.loss_grad[4]
+                if grad_depth.numel() != 0 or grad_alpha.numel() == 0 or grad_alpha.data_ptr() != ptr or grad_alpha._version != version:
+                    what = "the depth output received a gradient" if grad_depth.numel() != 0 else \
+                        "the alpha output has another gradient contribution (a second consumer, or a hook that changed the gradient)"
+                    ctx.loss_grad = None
+                    raise RuntimeError(f"object_stage_loss(raster_lossgrad=True): {what} -- another gradient contribution the in-blend loss gradient "
+                                       "would drop.  Use raster_lossgrad=False (GraphedTrainStep(loss_grad_in_blend=False)), or express a "
+                                       "per-pixel mask as grad_gate=")
+                grad_alpha = torch.empty(0, device=dev)                 # (uninitialised and unread: the blend forms it)
         split = sh_rest.numel() != 0
         # autograd's view of who reads which gradient, for the library (include/egs_raster.h EGS_GRAD_*): inputs order of forward()
         need = ctx.needs_input_grad
@@ -131,7 +143,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos, geom,
             ctx.num_rendered, binning, img, alpha, rs.debug, ctx.activation_flags, sh_rest if split else None, ctx.densify_stats, ctx.guard,
             ctx.sink, ctx.prologue_scratch, ctx.object_rotation, grad_mask, loss_grad=None if ctx.loss_grad is None else ctx.loss_grad[0],
-            object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]))
+            object_loss=None if (ctx.loss_grad is None or len(ctx.loss_grad) <= 3) else ctx.loss_grad[3], object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]))
         g_A12 = g_M = None
         if ctx.object_motion is not None:
             pose = grads[-1]

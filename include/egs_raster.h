@@ -523,6 +523,46 @@ int egs_backward_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const 
                           const uint32_t* skip_flag, const egs_adam_sink* sink /*HOST or NULL*/, int prologue_done, const egs_object_rotation* rot /*HOST or NULL*/,
                           int grad_mask, void* scratch, void* stream, int debug);
 
+/* ---- The object stages' loss (additions to ABI 6; nothing above changes).  The stages that recover the object's motion train on
+ *      lambda_image * [(1 - lambda) L1 + lambda (1 - SSIM)](image, gt * obj_mask)
+ *          + lambda_l1_alpha * mean|obj_mask - alpha| + lambda_l2_alpha * mean (obj_mask - alpha)^2
+ * with the hand-mask gate on the gradient of the image AND of alpha (/root/reference/trainers/coarse_obj_pose.py:239-260,
+ * trainers/fine_obj.py:128-151).  `gt` arrives already multiplied by the mask.  The entry points are the image loss's with an
+ * egs_object_loss beside them: the forward launch also adds up the two alpha sums (a fixed order: per strip, then over the strips),
+ * the finishing code assembles the weighted value and, with `terms`, the three terms apart; the backward launch also writes
+ *      dL/dalpha = gate * upstream * (lambda_l1_alpha * sign(alpha - m) + 2 lambda_l2_alpha * (alpha - m)) / (H W),   sign(0) = 0,
+ * and egs_backward_object_lossgrad is egs_backward_lossgrad whose blend forms that value itself as well (bit-identical to the launch's;
+ * dL/ddepth is 0): the forward it belongs to composited depth and alpha (out_alpha != NULL), `alpha` is that plane. */
+typedef struct egs_object_loss {     /* HOST struct */
+    const float* alpha;              /* [H,W] the alpha plane of the render the loss is taken on */
+    const float* obj_mask;           /* [H,W] */
+    float lambda_image, lambda_l1_alpha, lambda_l2_alpha;
+    float* alpha_partial_sums;       /* scratch: egs_l1_ssim_partial_count(1, H, W) floats, beside the image loss's partial_sums */
+    float* terms;                    /* device float[3] out or NULL: image loss, mean|m - alpha|, mean (m - alpha)^2 (unweighted), written with the value */
+} egs_object_loss;
+int egs_object_loss_forward(int channels, int height, int width, const float* img, const float* gt /*already gt * obj_mask*/, float lambda_dssim,
+                            float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss /*or NULL: deferred*/,
+                            float* loss_running_sum, const egs_object_loss* obj /*HOST*/, void* stream);
+int egs_object_loss_forward_ex(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
+                               float* partial_sums, float* dm_dmu1, float* dm_dexx, float* dm_dexy, float* loss /*or NULL: deferred*/,
+                               float* loss_running_sum, const egs_object_loss* obj /*HOST*/, const egs_backward_prologue* side /*HOST or NULL*/,
+                               void* stream);
+int egs_object_loss_backward_ex(int channels, int height, int width, const float* img, const float* gt, float lambda_dssim,
+                                const float* upstream_grad, const float* gate, const float* dm_dmu1, const float* dm_dexx,
+                                const float* dm_dexy, float* dL_dimg /*[C,H,W] out*/, float* dL_dalpha /*[H,W] out*/,
+                                const float* deferred_partial_sums, float* deferred_loss, float* loss_running_sum,
+                                const egs_object_loss* obj /*HOST*/, const egs_backward_prologue* side /*HOST or NULL*/, void* stream);
+int egs_backward_object_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
+                          const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, int width, int height, float tan_fovx, float tan_fovy, const int32_t* radii,
+                          const void* geom_buffer, const void* binning_buffer, const void* image_buffer, const egs_loss_grad* loss_grad /*HOST*/,
+                          const egs_object_loss* obj /*HOST*/,
+                          float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
+                          float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
+                          const uint32_t* skip_flag, const egs_adam_sink* sink /*HOST or NULL*/, int prologue_done, const egs_object_rotation* rot /*HOST or NULL*/,
+                          int grad_mask, void* scratch, void* stream, int debug);
+
 /* ---- f-4 (optimizer part): multi-tensor Adam step in one launch.  Same update as torch.optim.Adam(weight_decay=0,
  *      amsgrad=False), which the reference builds at /root/reference/scene/gaussian_model.py:198 and steps at
  *      /root/reference/trainers/train_static.py:137.  All array arguments are HOST arrays of length n_tensors holding

@@ -565,6 +565,77 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots) + tail
 
 
+# ---- the label phase (include/egs_raster.h: egs_label_bce_*, egs_backward_label) -----------------------------------------------
+ACT_SCALAR_COLOR = _lib.ACT_SCALAR_COLOR           # colors_precomp is float[P]: one value per Gaussian
+
+
+def label_bce_partial_count(H, W):
+    return int(_lib.load().egs_label_bce_partial_count(int(H), int(W)))
+
+
+def label_bce_forward(img, obj_mask, partial=None, loss=None, running_sum=None, defer_value=False):
+    """BCE-with-logits of the channel mean of `img` [3,H,W] against `obj_mask` [H,W] -> (loss float32[1] or None when deferred, partial sums).
+    defer_value: only the per-quadrant partial sums are written; label_bce_backward (or backward_label) assembles the value."""
+    L = _lib.load()
+    img, obj_mask = _f32c(img, "img"), _f32c(obj_mask, "obj_mask")
+    H, W = img.shape[-2], img.shape[-1]
+    dev = img.device
+    with _hip.device_ctx(dev):
+        if partial is None:
+            partial = torch.empty((label_bce_partial_count(H, W),), device=dev, dtype=torch.float32)
+        if loss is None and not defer_value:
+            loss = torch.empty((1,), device=dev, dtype=torch.float32)
+        _lib.check(L.egs_label_bce_forward(H, W, _ptr(img), _ptr(obj_mask), _ptr(partial), None if defer_value else _ptr(loss),
+                                           None if defer_value else _ptr(running_sum), _stream(dev)))
+    return (None if defer_value else loss), partial
+
+
+def label_bce_backward(img, obj_mask, upstream, gate=None, deferred_partial=None, deferred_loss=None, running_sum=None):
+    """dL/dimg [3,H,W] of the label loss (dL/dx / 3 in each plane); with deferred_partial the launch also assembles the value."""
+    L = _lib.load()
+    img, obj_mask, upstream, gate = _f32c(img, "img"), _f32c(obj_mask, "obj_mask"), _f32c(upstream, "upstream"), _opt(_f32c(gate, "gate"))
+    H, W = img.shape[-2], img.shape[-1]
+    dev = img.device
+    with _hip.device_ctx(dev):
+        dimg = torch.empty((3, H, W), device=dev, dtype=torch.float32)
+        _lib.check(L.egs_label_bce_backward(H, W, _ptr(img), _ptr(obj_mask), _ptr(gate), _ptr(upstream), _ptr(dimg), _ptr(deferred_partial),
+                                            _ptr(deferred_loss), _ptr(running_sum), _stream(dev)))
+    return dimg
+
+
+def label_loss_struct(img, obj_mask, upstream, gate=None, partial=None, loss=None, running_sum=None):
+    """(lib.LabelLoss, tensors it points to) for backward_label(label_loss=): the blend forms the loss gradient itself."""
+    H, W = img.shape[-2], img.shape[-1]
+    if partial is None:
+        partial = torch.empty((label_bce_partial_count(H, W),), device=img.device, dtype=torch.float32)
+    st = _lib.LabelLoss()
+    st.img, st.mask, st.gate, st.upstream = img.data_ptr(), obj_mask.data_ptr(), _ptr(gate), upstream.data_ptr()
+    st.partial, st.n_partial, st.loss, st.running = partial.data_ptr(), partial.numel(), _ptr(loss), _ptr(running_sum)
+    return st, (img, obj_mask, gate, upstream, partial, loss, running_sum)
+
+
+def backward_label(radii, geomBuffer, R, binningBuffer, imageBuffer, H, W, dL_dout_color=None, label_loss=None, want_grad=True, dlabel=None,
+                   adam=None, active_rows=None, guard=None, scratch=None, debug=0):
+    """The backward of a render whose colour is one value per Gaussian -> dL/dlabel float32[P] (None with want_grad=False).
+    Exactly one of dL_dout_color [3,H,W] and label_loss (a lib.LabelLoss: the blend forms the gradient of the label loss itself).
+    adam: (lib.AdamLeaf of the label, beta1, beta2, eps, coef float32[12]) -- the label's Adam step is taken by the last launch."""
+    L = _lib.load()
+    P = radii.shape[0]
+    dev = radii.device
+    with _hip.device_ctx(dev):
+        if want_grad and dlabel is None:
+            dlabel = torch.empty((P,), device=dev, dtype=torch.float32)
+        if scratch is None:
+            scratch = torch.empty((max(int(L.egs_backward_scratch_bytes(P)), 16),), device=dev, dtype=torch.uint8)
+        g_color = None if dL_dout_color is None else _f32c(dL_dout_color, "dL_dout_color")
+        leaf, b1, b2, eps, coef = adam if adam is not None else (None, 0.0, 0.0, 0.0, None)
+        _lib.check(L.egs_backward_label(P, int(R), int(W), int(H), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g_color),
+                                        None if label_loss is None else C.byref(label_loss), _ptr(dlabel) if want_grad else None,
+                                        None if leaf is None else C.byref(leaf), float(b1), float(b2), float(eps), _ptr(coef), _ptr(active_rows),
+                                        _ptr(None if guard is None else guard.overflow), _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+    return dlabel if want_grad else None
+
+
 def _stat_ptrs(stats_tensors, P, dev):
     if stats_tensors is None:
         return None, None, None

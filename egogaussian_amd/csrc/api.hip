@@ -6,6 +6,7 @@
 #include "object_motion.h"
 #include "backward_prologue.h"
 #include "loss_window.h"
+#include "label_bce.h"
 #include <string.h>
 #include <vector>
 #include <mutex>
@@ -95,7 +96,8 @@ static inline bool misaligned(const void* a, const void* b = nullptr, const void
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 255u) != 0;
 }
 int check_modes(const float* shs, const float* colors, const float* scales, const float* rots, const float* cov, int act) {
-    if (act & ~(EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS | EGS_ACT_LOGIT_OPACITY | EGS_ACT_OBJECT_MOTION)) return EGS_ERR_MODE;
+    if (act & ~(EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS | EGS_ACT_LOGIT_OPACITY | EGS_ACT_OBJECT_MOTION | EGS_ACT_SCALAR_COLOR)) return EGS_ERR_MODE;
+    if ((act & EGS_ACT_SCALAR_COLOR) && !colors) return EGS_ERR_MODE;                               // one value per Gaussian: of colors_precomp
     if ((act & (EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS)) && cov != nullptr) return EGS_ERR_MODE;   // nothing to activate: the covariance is given
     if ((shs != nullptr) == (colors != nullptr)) return EGS_ERR_MODE;
     const bool sr = scales != nullptr && rots != nullptr;
@@ -512,6 +514,7 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
                  const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
                  void* stream, int debug, const egs_loss_grad* loss_grad = nullptr, const egs_object_loss* obj_loss = nullptr) {
     int rc = check_dims(P, width, height); if (rc) return rc;
+    if (activation_flags & EGS_ACT_SCALAR_COLOR) return EGS_ERR_MODE;  // a scalar colour's gradient is egs_backward_label's: dL_dcolors here is [P,3]
     EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     // the image loss's gradient computed by the blend itself (egs_backward_lossgrad): colour gradients only, three channels
     EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr; EgsObjLossK olk = {};
@@ -788,6 +791,76 @@ int egs_backward_object_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R,
                          binning_buffer, image_buffer, nullptr, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
                          dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
                          skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad, obj);
+}
+
+// ---- the label phase (include/egs_raster.h; label_loss.hip, render_bwd.hip k_render_backward<3>) ----
+size_t egs_label_bce_partial_count(int height, int width) {
+    if (height <= 0 || width <= 0) return 0;
+    return (size_t)4 * (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+}
+int egs_label_bce_forward(int height, int width, const float* img, const float* obj_mask, float* partial_sums, float* loss, float* loss_running_sum,
+                          void* stream) {
+    int rc = check_dims(0, width, height); if (rc) return rc;
+    if (!img || !obj_mask || !partial_sums) return EGS_ERR_ARG;
+    EGS_TRY(egs_launch_label_bce_forward(height, width, img, obj_mask, partial_sums, loss, loss_running_sum, loss != nullptr, (hipStream_t)stream));
+    return 0;
+}
+int egs_label_bce_backward(int height, int width, const float* img, const float* obj_mask, const float* gate, const float* upstream_grad, float* dL_dimg,
+                           const float* deferred_partial_sums, float* deferred_loss, float* loss_running_sum, void* stream) {
+    int rc = check_dims(0, width, height); if (rc) return rc;
+    if (!img || !obj_mask || !upstream_grad || !dL_dimg) return EGS_ERR_ARG;
+    EGS_TRY(egs_launch_label_bce_backward(height, width, img, obj_mask, gate, upstream_grad, dL_dimg, deferred_partial_sums, deferred_loss,
+                                          deferred_partial_sums ? loss_running_sum : nullptr, (hipStream_t)stream));
+    return 0;
+}
+int egs_backward_label(int P, int64_t R, int width, int height, const int32_t* radii, const void* geom_buffer, const void* binning_buffer,
+                       const void* image_buffer, const float* dL_dout_color, const egs_label_loss* loss, float* dL_dlabel, const egs_adam_leaf* adam,
+                       float beta1, float beta2, float eps, float* coef, const int32_t* active_rows, const uint32_t* skip_flag, void* scratch,
+                       void* stream, int flags) {
+    const int debug = flags;
+    int rc = check_dims(P, width, height); if (rc) return rc;
+    if ((dL_dout_color != nullptr) == (loss != nullptr)) return EGS_ERR_MODE;
+    if (R < 0 || R >= (1ll << 31)) return EGS_ERR_RANGE;
+    const size_t n_partial = egs_label_bce_partial_count(height, width);
+    if (loss && (!loss->img || !loss->mask || !loss->upstream || !loss->partial || loss->n_partial < n_partial)) return EGS_ERR_ARG;
+    if (adam && (!adam->param || !adam->exp_avg || !adam->exp_avg_sq || !adam->lr || !adam->step || !coef)) return EGS_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const float inv_hw = 1.f / ((float)height * (float)width);
+    EgsAdamTick tick = {}; EgsLabelAdam la = {};
+    if (adam) {
+        tick.step[0] = adam->step; tick.lr[0] = adam->lr; tick.coef = coef; tick.skip = skip_flag; tick.b1 = beta1; tick.b2 = beta2;
+        la = EgsLabelAdam{ adam->param, adam->exp_avg, adam->exp_avg_sq, coef, active_rows, skip_flag, beta1, beta2, eps };
+    }
+    if (P == 0) {                                                     // nothing to blend: the value of the background image, no step
+        if (loss) EGS_TRY(egs_launch_label_bce_forward(height, width, loss->img, loss->mask, loss->partial, loss->loss, loss->running,
+                                                       (loss->loss || loss->running) ? 1 : 0, s));
+        return 0;
+    }
+    if (!radii || !geom_buffer || !image_buffer || !scratch || (R > 0 && !binning_buffer)) return EGS_ERR_ARG;
+    if (misaligned(geom_buffer, binning_buffer, image_buffer) || ((uintptr_t)scratch & 15u)) return EGS_ERR_ARG;
+    EgsGeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    EgsImgPtrs im = img_ptrs(const_cast<void*>(image_buffer), width, height);
+    float* grad_acc = (float*)scratch;
+    if (R == 0) {                                                     // no instance: every gradient is 0 (radii <= 0 everywhere); the step is still taken
+        EGS_TRY(egs_launch_zero_f4((float4*)grad_acc, egs_acc_floats((size_t)P) / 4, s));
+        if (adam) EGS_TRY(egs_launch_adam_tick(tick, s));
+        if (loss) EGS_TRY(egs_launch_label_bce_forward(height, width, loss->img, loss->mask, loss->partial, nullptr, nullptr, 0, s));
+    } else {
+        EgsBinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), P, R, width, height);
+        EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, adam ? &tick : nullptr, s));
+        EgsLabelLossK lk = {}; EgsLossGradHost lgh = {};
+        if (loss) { lk = EgsLabelLossK{ loss->img, loss->mask, loss->gate, loss->upstream, loss->partial, inv_hw }; lgh.lab = &lk; }
+        egs_prof_start(EGS_K_RENDER_BWD, s);
+        EGS_TRY(egs_launch_render_backward(P, width, height, nullptr, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 2, loss ? &lgh : nullptr, s));
+        egs_prof_stop(EGS_K_RENDER_BWD, s);
+        EGS_SYNC_IF_DEBUG(s);
+    }
+    egs_prof_start(EGS_K_PREPROCESS_BWD, s);
+    EGS_TRY(egs_launch_label_finish(P, grad_acc, g.clamped, radii, dL_dlabel, adam ? &la : nullptr, skip_flag, loss ? loss->partial : nullptr, n_partial, inv_hw,
+                                    loss ? loss->loss : nullptr, loss ? loss->running : nullptr, s));
+    egs_prof_stop(EGS_K_PREPROCESS_BWD, s);
+    EGS_SYNC_IF_DEBUG(s);
+    return 0;
 }
 
 int egs_l1_ssim_pair_backward(int channels, int height, int width, const float* img, const float* gt, const float* upstream_l1,

@@ -225,7 +225,7 @@ hipError_t egs_launch_backward_prologue(int P, int W, int H, EgsImgPtrs im, floa
 struct EgsLossGradHost { const float* img; const float* gt; const float* dm_dmu1; const float* dm_dexx; const float* dm_dexy; const float* gate;
                          const float* upstream; const float* upstream_ssim; float w_l1_n, w_ssim_n;
                          const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
-                         const struct EgsObjLossK* obj; };      // obj (may be NULL; loss_window.h): the object stages' loss -- the blend also forms dL/dalpha (k_render_backward<2, true>)
+                         const struct EgsObjLossK* obj; const struct EgsLabelLossK* lab; };      // lab (may be NULL; label_bce.h): the label loss, formed by k_render_backward<3, true>; obj (may be NULL; loss_window.h): the object stages' loss -- the blend also forms dL/dalpha (k_render_backward<2, true>)
 #ifdef EGS_LG_CHECK
 extern EgsLossGradHost egs_debug_lossgrad;
 #endif
@@ -233,9 +233,18 @@ hipError_t egs_launch_loss_finish(const EgsLossGradHost& lg, int W, int H, hipSt
 // lg (may be NULL): the blend computes dL/dcolour itself (k_render_backward<1, true>); dL_dcolor, dL_ddepth, dL_dalpha are then not read
 hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsGeomPtrs g, const uint32_t* point_list,
                                       EgsImgPtrs im, const float* dL_dcolor, const float* dL_ddepth,
-                                      const float* dL_dalpha, float* grad_acc, int colors_only, const EgsLossGradHost* lg, hipStream_t s);
+                                      const float* dL_dalpha, float* grad_acc, int colors_only /*2: one scalar colour (k_render_backward<3>)*/, const EgsLossGradHost* lg, hipStream_t s);
 // colors_only: the blend left only the colour sums (k_render_backward<0>); this turns them into dL/dcolors_precomp [P,3]
 hipError_t egs_launch_colors_from_acc(int P, const float* grad_acc, const uint8_t* clamped, const int32_t* radii, float* dcolors, hipStream_t s);
+// The label step's last launch (label_loss.hip k_label_finish): dL/dlabel[i] = slot 6 of Gaussian i's line (+ its replica lines), 0 when radii[i] <= 0;
+// with `leaf` the label's Adam step for every live row (coef[0], coef[1] as the tick left them); with `lab` one wave assembles the loss value.
+struct EgsLabelAdam { float* p; float* m; float* v; const float* coef; const int32_t* active_rows; const uint32_t* skip; float b1, b2, eps; };
+hipError_t egs_launch_label_finish(int P, const float* grad_acc, const uint8_t* clamped, const int32_t* radii, float* dlabel, const EgsLabelAdam* leaf,
+                                   const uint32_t* skip, const float* partial, size_t n_partial, float inv_hw, float* loss, float* running, hipStream_t s);
+// the label loss alone (label_loss.hip): the quadrant partials (+ the value unless loss == NULL and running == NULL ... see egs_label_bce_forward)
+hipError_t egs_launch_label_bce_forward(int H, int W, const float* img, const float* mask, float* partial, float* loss, float* running, int finish, hipStream_t s);
+hipError_t egs_launch_label_bce_backward(int H, int W, const float* img, const float* mask, const float* gate, const float* up, float* dL_dimg,
+                                         const float* fin_partial, float* fin_loss, float* fin_running, hipStream_t s);
 hipError_t egs_launch_adam_tick(const EgsAdamTick& tick, hipStream_t s);       // the same bookkeeping as a launch of its own (frames with no instance)
 
 // Zero-fill by a kernel.  hipMemsetAsync is avoided inside the per-step chain: captured into a hipGraph it becomes a memset

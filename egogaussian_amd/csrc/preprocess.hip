@@ -192,7 +192,10 @@ __device__ __forceinline__ uint32_t preprocess_one(
 
     float rgb[3]; uint32_t cl = 0;
     if (colors) {
-        rgb[0] = colors[3 * i]; rgb[1] = colors[3 * i + 1]; rgb[2] = colors[3 * i + 2];
+        // EGS_ACT_SCALAR_COLOR: one value per Gaussian fills the three slots -- no [P,3] copy of the label exists.  A branch on the uniform flag: the
+        // strided form (colors[cs * i + k * ck]) moved the register allocation of every instantiation (profiles/label_phase_resources.txt)
+        if (act & EGS_ACT_SCALAR_COLOR) rgb[0] = rgb[1] = rgb[2] = colors[i];
+        else { rgb[0] = colors[3 * i]; rgb[1] = colors[3 * i + 1]; rgb[2] = colors[3 * i + 2]; }
     } else if (!shs) {
         rgb[0] = rgb[1] = rgb[2] = 0.f;                            // k_sh_forward fills the colour (and the clamp flags) in afterwards
     } else {

@@ -24,6 +24,7 @@
 #include "backward_prologue.h"
 #include "blend_instrument.h"      // measurement / ablation hooks: all empty in the product build
 #include "loss_window.h"
+#include "label_bce.h"
 #include <algorithm>
 
 namespace {
@@ -52,6 +53,14 @@ __device__ __forceinline__ float row_sum(float v) {
     v = dpp_add<0x140>(v);      // row_mirror
     return v;
 }
+// the 64-lane sum of v, valid in row 3 (lanes 48-63): the row sums, then row_bcast:15 adds row 0 into row 1 and row 2 into row 3, and
+// row_bcast:31 adds rows 0-1 into rows 2 and 3 (rows the row mask leaves out add the 0 of `old`)
+__device__ __forceinline__ float wave_sum_row3(float v) {
+    v = row_sum(v);
+    v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x142, 0xa, 0xf, false));
+    v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x143, 0xc, 0xf, false));
+    return v;
+}
 
 __global__ __launch_bounds__(1024) void k_backward_prologue(EgsPrologueArgs a) {
     __shared__ EgsOrderLds L;
@@ -64,6 +73,13 @@ __global__ __launch_bounds__(1024) void k_backward_prologue(EgsPrologueArgs a) {
 // MODE 0 (ABI 4, egs_backward grad_mask == EGS_GRAD_COLORS): only dL/dcolors_precomp is wanted -- the reference's label call
 // (/root/reference/gaussian_renderer/render_helper.py:38-54 detaches every geometric input).  dL/dcolour_c = sum over pixels of
 // w dL/dC_c with w = alpha T: no dL/dalpha recurrence, no background term, no moments -- three sums per (wave, splat) instead of ten.
+// MODE 3 (egs_backward_label): MODE 0 for a SCALAR colour -- the label, which the forward broadcast into the record's three colour slots: dL/dlabel =
+// sum over pixels of w g with g = dL/dC0 + dL/dC1 + dL/dC2, ONE sum per (wave, splat).  Its 64-lane reduction is six DPP adds (wave_sum_row3: four in-row,
+// then row_bcast:15 and row_bcast:31; 6 x 6.8 = 41 cycles by the prices above, against 50 for permlane32 + permlane16 swaps + four in-row DPP adds and
+// 42 + an LDS round trip and its waits for the swap / LDS / quad-DPP chain of the ten-value path, which has nothing to amortise over with one value;
+// v_readlane cannot add floats on the scalar side).  Lane 63 issues the one global_atomic_add_f32 into slot 6 of the line (hot replicas as ever).
+// <3, true>: g is the label loss's dL/dx (label_bce.h), formed per lane from the image, the mask and the gate -- no 26-row window, no extra barrier --
+// and lane 0 of every quadrant-wave stores its sum of the loss value (plain store, before any early return).  A wave whose 64 g are all 0 leaves.
 // LG (loss gradient inside the blend): dL/dC of the tile's 256 pixels is not loaded but computed here from what the image loss's FORWARD
 // left -- its three derivative maps, the image and the ground truth -- with k_l1_ssim_backward's arithmetic, operation for operation
 // (loss.hip bwd_step / vblur_s / hblur_s: vertical 11-tap blur of the maps first, then the horizontal one, zero padding outside the image),
@@ -79,7 +95,7 @@ __device__ unsigned egs_lg_mismatch;
 struct EgsLossGrad { const float* img; const float* gt; const float* m0; const float* m1; const float* m2; const float* gate;
                      const float* up; const float* up_ssim; float w_l1, w_ssim;
                      const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
-                     EgsObjLossK obj; };              // (read by <2, true> only) the object stages' loss: the alpha plane the forward wrote, the mask, the alpha weights
+                     EgsObjLossK obj; EgsLabelLossK lab; };      // obj (read by <2, true> only); lab (read by <3, true> only, label_bce.h); obj: the object stages' loss: the alpha plane the forward wrote, the mask, the alpha weights
 #define LG_COLS 27
 template <int MODE, bool LG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_render_backward(
@@ -90,7 +106,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const uint32_t* __restrict__ quad_visits, const uint32_t hot_base /* first float of the hot replica lines inside grad_acc */,
     const uint32_t hot_slots /* lines per replica = ceil(P / 256) * EGS_HOT_PER_BLOCK */, const EgsLossGrad lg) {
     constexpr bool HAS_DA = MODE == 2;
-    constexpr int NV = MODE == 0 ? 3 : 10;                            // sums per (wave, splat)
+    constexpr int NV = MODE == 0 ? 3 : MODE == 3 ? 1 : 10;             // sums per (wave, splat)
+    constexpr bool COLOR_SUMS = MODE == 0 || MODE == 3;                // no dL/dalpha recurrence, no background term, no moments
     __shared__ float4 smem[4 * 64 * EGS_SPLAT_REC_F4 + 4 * 5 * 16];      // the staged records of four waves, then their reduction slices
     float4 (*lds)[64 * EGS_SPLAT_REC_F4] = reinterpret_cast<float4 (*)[64 * EGS_SPLAT_REC_F4]>(smem);
     float (*red)[5 * 64] = reinterpret_cast<float (*)[5 * 64]>(smem + 4 * 64 * EGS_SPLAT_REC_F4);
@@ -126,7 +143,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const int px = qx0 + (int)(lane & 7), py = qy0 + (int)(lane >> 3);
     const bool inside = px < W && py < H;
     float lg_r = 0.f, lg_g = 0.f, lg_b = 0.f;
-    if (LG) {
+    if (LG && MODE != 3) {
         // the loss value the forward deferred: one wave of the launch adds up the per-strip partial sums (loss_window.h), as k_l1_ssim_backward did
         if (lg.fin_partial && blockIdx.x == 0 && wv == 0) {
             if (HAS_DA) wave_finish_obj_loss(lg.fin_n, lg.fin_partial, lg.fin_lambda, lg.obj, lg.fin_loss, lg.fin_running, lane);
@@ -190,6 +207,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
         __syncthreads();                                              // the loop below reuses this LDS for its staged records
     }
+    // <3, true>: the label loss's dL/dx of the lane's pixel from the image the forward left, the mask and the gate (label_bce.h; no window,
+    // no barrier), and the quadrant's sum of the loss value -- stored BEFORE any early return: a quadrant no splat reaches still counts
+    if (LG && MODE == 3) {
+        float l = 0.f;
+        if (inside) {
+            const size_t pix = (size_t)py * W + px, HWp = (size_t)H * W;
+            const float x = egs_label_logit(lg.lab.img[pix], lg.lab.img[HWp + pix], lg.lab.img[2 * HWp + pix]);
+            const float m = lg.lab.mask[pix];
+            l = egs_label_bce_value(x, m);
+            lg_r = egs_label_bce_grad(x, m, lg.lab.inv_hw, lg.lab.up[0], lg.lab.gate != nullptr, lg.lab.gate ? lg.lab.gate[pix] : 1.f);
+        }
+        l = egs_label_wave_sum(l);
+        if (lane == 0) lg.lab.partial[(size_t)tile * 4 + q] = l;
+    }
     if (qx0 >= W || qy0 >= H) return;
 
     const float pxf = (float)px, pyf = (float)py;
@@ -203,10 +234,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (inside) {
         const size_t pix = (size_t)py * W + px, HW = (size_t)H * W;
         T_final = final_T[pix]; last = n_contrib[pix];
-        if (LG) { g_r = lg_r; g_g = lg_g; g_b = lg_b; }
+        if (MODE == 3) g_r = LG ? lg_r : __fadd_rn(__fadd_rn(dL_dcolor[pix], dL_dcolor[HW + pix]), dL_dcolor[2 * HW + pix]);      // one colour: one upstream value
+        else if (LG) { g_r = lg_r; g_g = lg_g; g_b = lg_b; }
         else { g_r = dL_dcolor[pix]; g_g = dL_dcolor[HW + pix]; g_b = dL_dcolor[2 * HW + pix]; }
 #ifdef EGS_LG_CHECK                     // debug build: the computed gradient against the one k_l1_ssim_backward wrote (bit for bit)
-        if (LG && (__float_as_uint(lg_r) != __float_as_uint(dL_dcolor[pix]) || __float_as_uint(lg_g) != __float_as_uint(dL_dcolor[HW + pix]) ||
+        if (LG && MODE != 3 && (__float_as_uint(lg_r) != __float_as_uint(dL_dcolor[pix]) || __float_as_uint(lg_g) != __float_as_uint(dL_dcolor[HW + pix]) ||
                    __float_as_uint(lg_b) != __float_as_uint(dL_dcolor[2 * HW + pix]))) atomicAdd(&egs_lg_mismatch, 1u);
 #endif
         if (HAS_DA && !LG && dL_ddepth) g_d = dL_ddepth[pix];
@@ -215,17 +247,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (HAS_DA && LG) g_a = egs_alpha_grad(lg.obj.alpha[pix], lg.obj.mask[pix], lg.obj.w_l1a, lg.obj.w_l2a2, lg.up[0], lg.gate != nullptr,
                                                lg.gate ? lg.gate[pix] : 1.f);
     }
-    const float bg_term = MODE == 0 ? 0.f : -T_final * (bg[0] * g_r + bg[1] * g_g + bg[2] * g_b);
+    const float bg_term = COLOR_SUMS ? 0.f : -T_final * (bg[0] * g_r + bg[1] * g_g + bg[2] * g_b);
     uint32_t wmax = last;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, d, 64));
     if (wmax == 0) return;
+    if (MODE == 3 && __ballot(g_r != 0.f) == 0ull) return;          // (e.g. a quadrant entirely under the hand mask: every sum would be 0)
 
     // stage 2/3 of the reduction: lane 4v+g (v < 10) sums partials [8g, 8g+8) of value v; lane 4v publishes it.
     // After the permlane32 fold, value v lives in register row v/2, lanes (v%2)*32 .. +31.
     const unsigned rv = lane >> 2, rg = lane & 3;
     const float4* red_src = reinterpret_cast<const float4*>(myred + (rv < (unsigned)NV ? (rv >> 1) * 64 + (rv & 1) * 32 + rg * 8 : 0));
-    const int slot = (rg == 0 && rv < (unsigned)NV) ? (int)rv + (MODE == 0 ? 6 : 0) : -1;      // (MODE 0: the three colour slots of the line)
+    int slot = MODE == 3 ? (lane == 63 ? 6 : -1)                      // (MODE 3: lane 63 holds the one sum; slot 6, the first colour slot)
+                         : (rg == 0 && rv < (unsigned)NV) ? (int)rv + (MODE == 0 ? 6 : 0) : -1;      // (MODE 0: the three colour slots of the line)
+    // (MODE 3: kept opaque -- with a provably uniform address the compiler wraps the one-lane atomic into its own cross-lane reduction loop)
+    if (MODE == 3) asm volatile("" : "+v"(slot));
 
     // S = the blended colour-gradient term of everything BEHIND the splat being processed (U of the header), kept "ready for the
     // next contributor": after a splat with (a, u) it becomes a u + (1 - a) S -- one state word and one select instead of three
@@ -299,6 +335,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const float rcp = __builtin_amdgcn_rcpf(1.f - a);
             const float Tn = T * rcp;                                   // transmittance in front of this splat
             const float w = a * Tn;
+            float out;
+            if (MODE == 3) {
+                T = Tn;
+                (void)S; (void)bg_term; (void)red_src; (void)myred;
+                out = wave_sum_row3(w * g_r);
+            } else {
             if (MODE == 0) {
                 T = Tn;
                 const float v6 = w * g_r, v7 = w * g_g, v8 = w * g_b;
@@ -327,9 +369,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             myred[3 * 64 + lane] = fold32(v6, v7); myred[4 * 64 + lane] = fold32(v8, v9);
             }
             const float4 pa = red_src[0], pb = red_src[1];
-            float out = ((pa.x + pa.y) + (pa.z + pa.w)) + ((pb.x + pb.y) + (pb.z + pb.w));
+            out = ((pa.x + pa.y) + (pa.z + pa.w)) + ((pb.x + pb.y) + (pb.z + pb.w));
             out = dpp_add<0xB1>(out);       // quad_perm [1,0,3,2]
             out = dpp_add<0x4E>(out);       // quad_perm [2,3,0,1]
+            }
             const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)my_id, j);
             EGS_BWD_ABL7(my[j * 3 + 2])
             uint32_t line = gid * (uint32_t)EGS_GRAD_STRIDE;            // first float of the accumulator line (48 P < 2^32 bytes: P < 89 M)
@@ -399,11 +442,14 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
     if (lg) { lgk.img = lg->img; lgk.gt = lg->gt; lgk.m0 = lg->dm_dmu1; lgk.m1 = lg->dm_dexx; lgk.m2 = lg->dm_dexy; lgk.gate = lg->gate;
               lgk.up = lg->upstream; lgk.up_ssim = lg->upstream_ssim; lgk.w_l1 = lg->w_l1_n / ((float)W * (float)H * 3.f); lgk.w_ssim = lg->w_ssim_n / ((float)W * (float)H * 3.f);
               lgk.fin_partial = lg->fin_partial; lgk.fin_n = lg->fin_n; lgk.fin_lambda = lg->fin_lambda; lgk.fin_loss = lg->fin_loss; lgk.fin_running = lg->fin_running;
-              if (lg->obj) lgk.obj = *lg->obj; }
+              if (lg->obj) lgk.obj = *lg->obj;
+              if (lg->lab) lgk.lab = *lg->lab; }
 #define EGS_BWD_LAUNCH(MODE, LGF) hipLaunchKernelGGL((k_render_backward<MODE, LGF>), dim3(egs_blocks_for_tiles(n_tiles)), dim3(256), 0, s, W, H, gx, n_tiles, \
                            im.ranges, point_list, g.rec, bg, im.final_T, im.n_contrib, dL_dcolor, dL_ddepth, dL_dalpha, \
                            im.tile_order, grad_acc, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * EGS_GRAD_STRIDE), (uint32_t)egs_hot_slots((size_t)P), lgk)
-    if (colors_only) EGS_BWD_LAUNCH(0, false);
+    if (colors_only == 2 && lg && lg->lab) EGS_BWD_LAUNCH(3, true);  // scalar colour, the label loss formed by the blend (dL_dcolor is not read)
+    else if (colors_only == 2) EGS_BWD_LAUNCH(3, false);             // scalar colour, any loss: the three upstream planes added up
+    else if (colors_only) EGS_BWD_LAUNCH(0, false);
     else if (lg && lg->obj) EGS_BWD_LAUNCH(2, true);                 // (dL_ddepth, dL_dalpha are not read: the prologue forms dL/dalpha, dL/ddepth is 0)
     else if (dL_ddepth || dL_dalpha) EGS_BWD_LAUNCH(2, false);
     else if (lg) EGS_BWD_LAUNCH(1, true);

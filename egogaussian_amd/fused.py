@@ -439,3 +439,60 @@ def object_stage_loss(image, alpha, gt, obj_mask, lambda_dssim=0.2, lambda_image
     lossgrad = bool(raster_lossgrad and node is not None and alpha.grad_fn is node)
     return _ObjectLoss.apply(image, alpha, gtm, mask, lambda_dssim, (lambda_image, lambda_l1_alpha, lambda_l2_alpha), grad_gate, running_sum, terms,
                              defer_value, node, lossgrad)
+
+
+class _LabelBCE(torch.autograd.Function):
+    """The label phase's loss (losses.label_bce_loss) as one node: the HIP forward (per-quadrant partial sums in a fixed order + a finishing
+    launch, or deferred), and either the HIP backward launch or -- lossgrad -- no launch at all: the scalar colours-only blend of the label
+    render in front forms the gradient itself (include/egs_raster.h egs_backward_label)."""
+
+    @staticmethod
+    def forward(ctx, img, mask, gate, running_sum, defer_value, raster_node, lossgrad):
+        from . import _C
+        img, mask = _need_hip(img, "image"), _need_hip(mask, "obj_mask")
+        assert img.dim() == 3 and img.shape[0] == 3 and mask.numel() == img.shape[1] * img.shape[2]
+        loss = torch.empty((), device=img.device)
+        _, partial = _C.label_bce_forward(img, mask, loss=loss.view(1), running_sum=running_sum, defer_value=defer_value)
+        ctx.save_for_backward(img, mask, gate if gate is not None else torch.empty(0))
+        ctx.has_gate = gate is not None
+        ctx.deferred = (partial, loss, running_sum) if defer_value else None
+        ctx.partial = partial
+        ctx.raster_node, ctx.lossgrad = raster_node, bool(lossgrad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _C
+        img, mask, gate = ctx.saved_tensors
+        gate = gate.float().contiguous() if ctx.has_gate else None
+        g = g.reshape(1)
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        d = ctx.deferred
+        if ctx.lossgrad:
+            # no launch here: the label render's backward blend forms dL/dx per pixel itself, and its last launch assembles a deferred value.
+            # `dimg` goes back uninitialised and unread; the rasterizer's node refuses any other tensor in its place.
+            dimg = torch.empty_like(img)
+            st, keep = _C.label_loss_struct(img, mask, g, gate, ctx.partial, d[1].view(1) if d else None, d[2] if d else None)
+            ctx.raster_node.label_loss = (st, keep, (dimg.data_ptr(), dimg._version))
+            return dimg, None, None, None, None, None, None
+        dimg = _C.label_bce_backward(img, mask, g, gate, d[0] if d else None, d[1].view(1) if d else None, d[2] if d else None)
+        return dimg, None, None, None, None, None, None
+
+
+def label_bce_loss(image, obj_mask, grad_gate=None, running_sum=None, defer_value=False, raster_lossgrad=False):
+    """BCEWithLogitsLoss()(image.mean(0, keepdim=True), obj_mask) for the label render `image` [3,H,W] (losses.label_bce_loss is the torch mirror;
+    /root/reference/trainers/train_static.py:104-109).  `grad_gate` [H,W] multiplies d loss / d mean per pixel -- the reference's
+    `render_label.register_hook(lambda g: g * (1 - hand_mask))`.  running_sum / defer_value: as l1_ssim_loss.
+    raster_lossgrad=True (when `image` is get_render_label(..., scalar=True)'s output itself and loss.backward() is sure to follow): this loss has
+    no backward launch; the label render's backward blend forms the gradient from the image, the mask and the gate.  The gradient tensor handed
+    to the rasterizer is uninitialised memory, and the rasterizer's node refuses any other gradient contribution to the image."""
+    if running_sum is not None:
+        running_sum = _need_hip(running_sum, "running_sum")
+    node = None
+    if raster_lossgrad:
+        fn = image.grad_fn
+        if fn is not None and getattr(fn, "egs_label_node", False):
+            node = fn
+    m = obj_mask.reshape(image.shape[-2], image.shape[-1])
+    return _LabelBCE.apply(image, m, grad_gate, running_sum, defer_value, node, node is not None)

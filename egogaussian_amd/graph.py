@@ -36,10 +36,18 @@ def pack_camera(cam):
     return torch.cat([cam.world_view_transform.reshape(-1), cam.full_proj_transform.reshape(-1), cam.camera_center.reshape(-1)]).float()
 
 
-def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_loss=False):
+def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_loss=False, label_phase=False):
     """Float offsets of the segments of a packed frame (each starts on a 16-byte boundary): -> ({name: (begin, end)}, size).
-    object_loss: an `obj_mask` segment of n_pix floats follows everything else (the other segments keep their offsets)."""
+    object_loss: an `obj_mask` segment of n_pix floats follows everything else (the other segments keep their offsets).
+    label_phase: the frame of a label step -- no image segment (n_img is not read): camera[, gate], obj_mask."""
     up4 = lambda x: (x + 3) & ~3
+    if label_phase:
+        off = {"cam": (0, 35)}
+        end = up4(35)
+        if gated:
+            off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
+        off["obj_mask"] = (end, end + n_pix); end = up4(end + n_pix)
+        return off, end
     off = {"gt": (0, n_img)}
     end = up4(n_img)
     off["cam"] = (end, end + 35); end = up4(end + 35)
@@ -78,6 +86,19 @@ def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
     return f
 
 
+def pack_label_frame(cam, obj_mask, gate=None):
+    """One resident tensor per frame of the label phase (GraphedTrainStep(label_phase=True)): the camera block, the gate (1 - hand mask,
+    [H,W]; a step captured with gated=True) and the object mask ([H,W] or [1,H,W]).  No image: the label loss reads none."""
+    H, W = obj_mask.shape[-2], obj_mask.shape[-1]
+    off, size = frame_layout(0, H * W, gated=gate is not None, label_phase=True)
+    f = torch.zeros(size, device=obj_mask.device, dtype=torch.float32)
+    f[off["cam"][0]:off["cam"][1]] = pack_camera(cam).to(obj_mask.device)
+    if gate is not None:
+        f[off["gate"][0]:off["gate"][1]] = gate.reshape(-1).to(obj_mask.device)
+    f[off["obj_mask"][0]:off["obj_mask"][1]] = obj_mask.to(torch.float32).reshape(-1)
+    return f
+
+
 class _StaticCamera:
     """Camera whose tensors are fixed device buffers; `load(cam)` copies another camera of the same intrinsics in."""
 
@@ -109,8 +130,16 @@ class _StaticCamera:
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
-                 motion=False, object_loss=None, pose=None):
-        """densify_stats: the captured step also keeps the per-iteration densification statistics (trainers/train_static.py:125-127:
+                 motion=False, object_loss=None, pose=None, label_phase=False):
+        """label_phase:   the label phase of the static stage (/root/reference/trainers/train_static.py:104-109) instead of the image step:
+                       the label render with the label as one value per Gaussian, BCE-with-logits of its channel mean against the frame's
+                       object mask (gated: the hand-mask hook), Adam on the label ALONE -- forward chain, backward prologue, the scalar
+                       colours-only blend that forms the loss gradient itself, and one launch that reads dL/dlabel out, takes the step and
+                       assembles the value (include/egs_raster.h egs_backward_label).  No colour render() runs: in that phase its image
+                       reaches no loss.  The optimizer must have a "label" group; no other group is touched (their .grad is None in the
+                       reference too).  capture(cam, obj_mask=, gate=) / __call__(cam, obj_mask=, gate=) or pack_label_frame() frames.
+                       `self.image` is the label render, `self.label_grad` the dL/dlabel [P] of the last replay.
+        densify_stats: the captured step also keeps the per-iteration densification statistics (trainers/train_static.py:125-127:
                        max_radii2D, xyz_gradient_accum, denom) -- updated by the rasterizer's backward itself, no launch of their own.
         dynamic:       the `fine_all` call shape (/root/reference/trainers/fine_all.py:88-93): render(..., rot_cov=True,
                        accum_R=<static 3x3, refreshed per call>, which_object=which_object, during_training=False).
@@ -149,6 +178,18 @@ class GraphedTrainStep:
                        (renderer.render, optimizer=): no gradient arrays, no optimizer launch for them; the step's loss must then
                        depend on the model through that one render only -- which is the step this class captures.  Results are
                        bit-identical either way."""
+        self.label_phase = bool(label_phase)
+        if self.label_phase:
+            for name, on in (("dynamic", dynamic), ("motion", motion), ("pose", pose is not None), ("object_loss", object_loss is not None),
+                             ("densify_stats", densify_stats), ("double_buffer", double_buffer)):
+                if on:
+                    raise ValueError(f"GraphedTrainStep(label_phase=True) does not go with {name}: the label step renders the static model, "
+                                     "trains the label alone and keeps one set of frame buffers")
+            groups = [g for g in optimizer.param_groups if g.get("name") == "label"]
+            if len(groups) != 1 or len(groups[0]["params"]) != 1:
+                raise ValueError('GraphedTrainStep(label_phase=True) needs a "label" parameter group (one tensor) in the optimizer given')
+            self._label_group = groups[0]
+        self.label_grad = None
         self.fuse_optimizer = bool(fuse_optimizer)
         import os
         self.loss_grad_in_blend = bool(loss_grad_in_blend) and not os.environ.get("EGS_NO_LOSS_GRAD_IN_BLEND")      # (A/B switch for bench.py)
@@ -195,6 +236,112 @@ class GraphedTrainStep:
                 kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
         return kw
 
+    def _label_body(self, k=0):
+        """One iteration of the label phase on static frame k: no autograd, the library's calls in order."""
+        import math
+        from . import lib as _lib
+        from .optim import _touched
+        f, pc, opt, group = self._slots[k], self.pc, self.opt, self._label_group
+        p = group["params"][0]
+        cam = f["cam"]
+        dev = p.device
+        capturing = torch.cuda.is_current_stream_capturing()
+        with torch.no_grad():
+            raw = pc.get_raw_parameters() if getattr(pc, "get_raw_parameters", None) is not None else None
+            if raw is not None:
+                scales, rotations, opacity = raw
+                act = _C.ACT_RAW_PARAMETERS | _C.ACT_SCALAR_COLOR
+            else:
+                scales, rotations, opacity = pc.get_scaling, pc.get_rotation, pc.get_opacity
+                act = _C.ACT_SCALAR_COLOR
+            e = torch.empty(0, device=dev)
+            H, W = int(cam.image_height), int(cam.image_width)
+            R, color, _, _, radii, geom, binning, img = _C.rasterize_gaussians(
+                self.bg, pc.get_xyz.detach(), p.detach().view(-1), opacity.detach(), scales.detach(), rotations.detach(), 1.0, e,
+                cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), H, W, e,
+                pc.active_sh_degree, cam.camera_center, False, False, act, None, getattr(pc, "active_count", None), self.guard, None, True, None)
+            m, v, step, lr_t = opt._capturable_state(p, group)
+            coef = opt._coef.get(dev)
+            if coef is None:
+                coef = opt._coef[dev] = torch.zeros(12, device=dev)
+            leaf = _lib.AdamLeaf()
+            leaf.param, leaf.exp_avg, leaf.exp_avg_sq, leaf.lr, leaf.step = p.data_ptr(), m.data_ptr(), v.data_ptr(), lr_t.data_ptr(), step.data_ptr()
+            rows = None
+            if opt.active_rows is not None and p.shape[0] == opt.active_rows[1]:
+                rows = opt.active_rows[0]
+            loss = torch.empty((), device=dev)
+            st, keep = _C.label_loss_struct(color, f["obj_mask"], self._one.view(1), f["gate"] if self.gated else None, None, loss.view(1), self.loss_sum.view(1))
+            # (the overflow word is written by CAPTURED forwards only: an eager warm-up step follows a complete render)
+            dl = _C.backward_label(radii, geom, R, binning, img, H, W, label_loss=st, adam=(leaf, float(group["betas"][0]), float(group["betas"][1]),
+                                   float(group["eps"]), coef), active_rows=rows, guard=self.guard if capturing else None)
+            opt._aux_of(p)["counter_stale"] = True        # k_adam's own step counters do not follow a step taken here (optim.AdamSink.mark_stepped)
+            _touched(p)
+        self._label_keep = (keep, m, v, step, lr_t, coef, geom, binning, img)
+        return loss, {"render": color, "radii": radii, "label_grad": dl}
+
+    def _capture_label(self, cam, obj_mask, gate, warmup, capacity_margin, capacity):
+        """capture() of a label step: the static frame holds camera[, gate], obj_mask (frame_layout(label_phase=True))."""
+        dev = self._label_group["params"][0].device
+        if not isinstance(cam, _StaticCamera):
+            H, W = int(cam.image_height), int(cam.image_width)
+            off, size = frame_layout(0, H * W, gated=self.gated, label_phase=True)
+            self._frames = torch.zeros((self.steps_per_replay, size), device=dev, dtype=torch.float32)
+            self._slots = []
+            for k in range(self.steps_per_replay):
+                fr = self._frames[k]
+                slot = {"gt": None, "accum_R": None, "accum_T": None, "gate": None}
+                slot["cam"] = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
+                slot["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(H, W)
+                if obj_mask is not None:
+                    slot["obj_mask"].copy_(obj_mask.to(dev, torch.float32).reshape(H, W))
+                if self.gated:
+                    slot["gate"] = fr[off["gate"][0]:off["gate"][1]].view(H, W)
+                    slot["gate"].copy_(torch.ones((H, W), device=dev) if gate is None else gate.reshape(H, W))
+                self._slots.append(slot)
+            self._frame = self._frames[0]
+            first = self._slots[0]
+            self.gt, self.cam, self.accum_R, self.accum_T, self.gate, self.obj_mask = None, first["cam"], None, None, first["gate"], first["obj_mask"]
+        self._one = torch.ones((), device=dev)
+        if getattr(self, "loss_sum", None) is None:
+            self.loss_sum = torch.zeros((), device=dev)
+        self.guard = _C.StepGuard(dev)
+        self.opt.guard = self.guard
+        self.opt.sync_lr()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        r_seen = 0
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):                          # eager: real label steps; they set the capacity hint and the lazy state
+                self._label_body()
+                r_seen = max(r_seen, _C.stats["num_rendered"])
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.capacity = max(int(r_seen * capacity_margin), _C.stats["capacity"], getattr(self, "_min_capacity", 0))
+        if capacity is not None:
+            self.capacity = max(int(capacity), 1)
+        _C.set_capacity_hint(self.capacity, dev)
+        self.P = self.pc.get_xyz.shape[0]
+        self._model_version = getattr(self.pc, "model_version", 0)
+        self.graph = torch.cuda.CUDAGraph()
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self.graph.capture_begin(capture_error_mode="thread_local")
+            try:
+                self.losses, self.label_grads, keeps = [], [], []
+                for k in range(self.steps_per_replay):
+                    self.loss, out = self._label_body(k)
+                    self.losses.append(self.loss); self.label_grads.append(out["label_grad"]); keeps.append(self._label_keep)
+                self._label_keeps = keeps
+                self.image, self.radii, self.label_grad = out["render"], out["radii"], out["label_grad"]
+                self.visibility_filter = self.viewspace_grad = None
+            finally:
+                self.graph.capture_end()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self._sets = None
+        self.guard.running_max.zero_(); self.guard.overflow.zero_()
+        return self
+
     def _body(self, k=0):
         """One training iteration on static frame k."""
         f = self._slots[k]
@@ -218,13 +365,17 @@ class GraphedTrainStep:
     def _frame_layout(self, gt):
         return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion, self.object_loss is not None)
 
-    def capture(self, cam, gt, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
+    def capture(self, cam, gt=None, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
                 obj_mask=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
         more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
         capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow).
         obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask."""
+        if self.label_phase:
+            if obj_mask is None and not isinstance(cam, _StaticCamera):
+                raise ValueError("GraphedTrainStep(label_phase=True).capture(cam, obj_mask=...): the label step's frame is camera[, gate], obj_mask")
+            return self._capture_label(cam, obj_mask, gate, warmup, capacity_margin, capacity)
         dev = gt.device
         if self.object_loss is not None and obj_mask is not None:
             obj_mask = obj_mask.to(dev, torch.float32).reshape(gt.shape[-2], gt.shape[-1])
@@ -371,6 +522,8 @@ class GraphedTrainStep:
         gt = self.gt if gt is None else gt
         self.graph = None                                            # drop the old graph and its private memory pool first
         self._sets = None
+        if self.label_phase:
+            return self.capture(cam, None, warmup=warmup, capacity_margin=capacity_margin, obj_mask=self.obj_mask, gate=self.gate)
         return self.capture(cam, gt, warmup=warmup, capacity_margin=capacity_margin, capacity_cams=capacity_cams)
 
     def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None):
@@ -382,7 +535,14 @@ class GraphedTrainStep:
         produced on the current stream right before the call then serialise behind the replay that is still running."""
         if gt is None and self._sets is not None:
             return self._call_double_buffered(cam, ready)
-        if gt is None:
+        if self.label_phase and obj_mask is not None:
+            if self.steps_per_replay != 1:
+                raise ValueError("steps_per_replay > 1 takes packed frames")
+            self.cam.load(cam)
+            self.obj_mask.copy_(obj_mask.reshape(self.obj_mask.shape), non_blocking=True)
+            if self.gated and gate is not None:
+                self.gate.copy_(gate.reshape(self.gate.shape), non_blocking=True)
+        elif gt is None:
             if isinstance(cam, (list, tuple)):
                 for k, fr in enumerate(cam):
                     self._frames[k].copy_(fr, non_blocking=True)

@@ -72,6 +72,12 @@ class ObjectLoss(C.Structure):                   # egs_object_loss
                 ("lambda_l2_alpha", C.c_float), ("alpha_partial_sums", C.c_void_p), ("terms", C.c_void_p)]
 
 
+class LabelLoss(C.Structure):                    # egs_label_loss
+    _fields_ = [("img", C.c_void_p), ("mask", C.c_void_p), ("gate", C.c_void_p), ("upstream", C.c_void_p), ("partial", C.c_void_p),
+                ("n_partial", C.c_size_t), ("loss", C.c_void_p), ("running", C.c_void_p)]
+
+
+ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
 # name -> (restype, argtypes); every symbol include/egs_raster.h declares
@@ -127,6 +133,11 @@ SIGNATURES = {
     "egs_backward_object_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
                                                vp, vp, vp, vp, C.POINTER(LossGrad), C.POINTER(ObjectLoss), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_label_bce_partial_count": (C.c_size_t, [i32, i32]),
+    "egs_label_bce_forward": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp]),
+    "egs_label_bce_backward": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_backward_label": (C.c_int, [i32, i64, i32, i32, vp, vp, vp, vp, vp, C.POINTER(LabelLoss), vp, C.POINTER(AdamLeaf), f32, f32, f32, vp, vp, vp,
+                                     vp, vp, i32]),
     "egs_adam_step": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "egs_adam_workgroups": (C.c_int64, [i64]),
     "egs_adam_step_capturable": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]),

@@ -69,3 +69,11 @@ def object_stage_loss(image, alpha, gt, obj_mask, lambda_dssim, lambda_image=1.0
     img = (1.0 - lambda_dssim) * l1_loss(gtm, image) + lambda_dssim * (1.0 - ssim(gtm, image))
     a = alpha.reshape(m.shape)
     return lambda_image * img + lambda_l1_alpha * l1_loss(m, a) + lambda_l2_alpha * l2_loss(m, a)
+
+
+def label_bce_loss(render_label, obj_mask):
+    """The label phase's loss (/root/reference/trainers/train_static.py:104-109): BCE-with-logits of the channel mean of the label render
+    [3,H,W] against the object mask ([H,W] or [1,H,W]).  The reference's hand-mask hook (grad * (1 - hand_mask) on the mean) is the caller's;
+    fused.label_bce_loss takes it as grad_gate.  The oracle of the HIP kernels behind fused.label_bce_loss, on any device and in any float type."""
+    x = render_label.mean(0, keepdim=True)
+    return torch.nn.functional.binary_cross_entropy_with_logits(x, obj_mask.to(x.dtype).reshape(x.shape))

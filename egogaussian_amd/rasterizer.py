@@ -162,6 +162,54 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grads[8] if split else None, None, None, None, None, None, None, None, g_A12, g_M)
 
 
+class _RasterizeLabel(torch.autograd.Function):
+    """The label render with the label as ONE value per Gaussian (include/egs_raster.h EGS_ACT_SCALAR_COLOR, egs_backward_label): the preprocess
+    kernel fills the record's three colour slots from it -- no [P,3] copy --, the backward is the scalar colours-only blend and returns dL/dlabel.
+    Geometry is a constant of the loss, as in the reference's label call (/root/reference/gaussian_renderer/render_helper.py:38-54)."""
+
+    @staticmethod
+    def forward(ctx, label, means3D, opacities, scales, rotations, raster_settings, active_count=None, guard=None):
+        rs = raster_settings
+        empty = torch.empty(0, device=means3D.device, dtype=torch.float32)
+        flat = label.detach().reshape(-1).float().contiguous()
+        if flat.numel() != means3D.shape[0]:
+            raise RuntimeError("get_render_label(scalar=True): the label holds one value per Gaussian")
+        num_rendered, color, _, _, radii, geom, binning, img = _C.rasterize_gaussians(
+            rs.bg, means3D, flat, opacities, scales, rotations, rs.scale_modifier, empty, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+            rs.image_height, rs.image_width, empty, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, _C.ACT_SCALAR_COLOR, None, active_count, guard,
+            None, True, None)
+        ctx.raster_settings, ctx.num_rendered, ctx.guard, ctx.label_shape = rs, num_rendered, guard, tuple(label.shape)
+        ctx.egs_label_node = True                   # fused.label_bce_loss(raster_lossgrad=True) recognises its input's grad_fn by this
+        ctx.label_loss = None                       # (lib.LabelLoss, tensors it points to, (address, version) of the gradient tensor handed over)
+        ctx.save_for_backward(radii, geom, binning, img)
+        ctx.mark_non_differentiable(radii)
+        return color, radii
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii=None):
+        rs = ctx.raster_settings
+        radii, geom, binning, img = ctx.saved_tensors
+        H, W = int(rs.image_height), int(rs.image_width)
+        ll, ctx.label_loss = ctx.label_loss, None
+        if ll is not None:
+            ptr, version = ll[2]
+            if grad_color is None or grad_color.data_ptr() != ptr or grad_color._version != version:
+                raise RuntimeError("label_bce_loss(raster_lossgrad=True): the label render has another gradient contribution (a second consumer, or a "
+                                   "hook that changed the gradient) -- the in-blend loss gradient would drop it.  Use raster_lossgrad=False, or "
+                                   "express a per-pixel mask as grad_gate=")
+            g = _C.backward_label(radii, geom, ctx.num_rendered, binning, img, H, W, label_loss=ll[0], guard=ctx.guard, debug=rs.debug)
+        else:
+            if grad_color is None:
+                grad_color = torch.zeros((3, H, W), device=radii.device)
+            g = _C.backward_label(radii, geom, ctx.num_rendered, binning, img, H, W, dL_dout_color=grad_color, guard=ctx.guard, debug=rs.debug)
+        return g.view(ctx.label_shape), None, None, None, None, None, None, None
+
+
+def rasterize_label(label, means3D, opacities, scales, rotations, raster_settings, active_count=None, guard=None):
+    """-> (label image [3,H,W]: three equal planes, radii); only `label` ([P] or [P,1]) receives a gradient, of its own shape."""
+    return _RasterizeLabel.apply(label, means3D, opacities, scales, rotations, raster_settings, active_count, guard)
+
+
 def backward_prologue_of(node):
     """For the backward node of a rasterizer call that has not run yet: the egs_backward_prologue describing what that backward needs
     prepared (include/egs_raster.h), or None.  The scratch buffer it names is allocated here and handed to the node, whose backward

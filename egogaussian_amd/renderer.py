@@ -175,8 +175,17 @@ def gaussians_to_label_rendervar(gaussians):
             "scales": gaussians.get_scaling.detach(), "means2D": _screenspace_leaf(xyz).detach()}      # (the reference: zeros_like(xyz) + 0, two launches; nothing reads the values)
 
 
-def get_render_label(viewpoint_camera, pc, bg_color):
-    """Per-Gaussian scalar label rendered as a grey colour through a fresh rasterizer (object segmentation)."""
+def get_render_label(viewpoint_camera, pc, bg_color, scalar=False):
+    """Per-Gaussian scalar label rendered as a grey colour through a fresh rasterizer (object segmentation).
+    scalar (extension; default: the reference's call): `pc.get_label` goes to the rasterizer as ONE value per Gaussian -- no [P,3] expansion,
+    and the backward is the scalar colours-only blend, which returns dL/dlabel as [P,1] (include/egs_raster.h egs_backward_label).  The image is
+    the same, bit for bit; depth and alpha are not composited."""
+    if scalar:
+        from .rasterizer import rasterize_label
+        label, _ = rasterize_label(pc.get_label, pc.get_xyz.detach(), pc.get_opacity.detach(), pc.get_scaling.detach(), pc.get_rotation.detach(),
+                                   get_raster_settings(viewpoint_camera, pc, bg_color),
+                                   active_count=getattr(pc, "active_count", None))
+        return label
     renderer = GaussianRasterizer(get_raster_settings(viewpoint_camera, pc, bg_color))
     label, _, _, _ = renderer(**gaussians_to_label_rendervar(pc))
     return label

@@ -563,6 +563,60 @@ int egs_backward_object_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R,
                           const uint32_t* skip_flag, const egs_adam_sink* sink /*HOST or NULL*/, int prologue_done, const egs_object_rotation* rot /*HOST or NULL*/,
                           int grad_mask, void* scratch, void* stream, int debug);
 
+/* ---- The label phase of the static stage (additions to ABI 6; nothing above changes).  30 000 iterations of
+ *          render_label = mean_c(get_render_label(cam, gaussians, bg));  hook: grad *= 1 - hand_mask
+ *          loss = BCEWithLogitsLoss()(render_label, obj_mask);  loss.backward();  optimizer.step()      (only the label has a gradient)
+ *      (/root/reference/trainers/train_static.py:104-109; the label render detaches the geometry, gaussian_renderer/render_helper.py:38-54).
+ *      Per pixel, with the three planes C0, C1, C2 of the label render, the mask m, the gate k (1 when absent) and the upstream scalar up:
+ *          x = (C0 + C1 + C2) / 3     l = max(x, 0) - x m + log1p(exp(-|x|))     dL/dx = up k (sigmoid(x) - m) / (H W)
+ *      and the loss is the mean of l over the H W pixels; a pixel no splat reaches counts with x = mean(bg).
+ *   egs_label_bce_forward   writes one partial sum per (16x16 tile, 8x8 quadrant) into `partial_sums` (egs_label_bce_partial_count floats:
+ *                           a fixed partition and a fixed order inside it) and, unless loss == NULL, a finishing launch adds them up in index
+ *                           order in float64: deterministic, the same bits on every run.  loss == NULL defers the value (as egs_l1_ssim_forward
+ *                           does): pass the partial sums to egs_label_bce_backward as `deferred_partial_sums`, one wave of which assembles it.
+ *   egs_label_bce_backward  dL/dC [3,H,W]: dL/dx / 3 in each plane.
+ *   egs_backward_label      the backward of a render whose colour is ONE value per Gaussian, the label (the forward got it as colors_precomp with
+ *                           EGS_ACT_SCALAR_COLOR... or as that value repeated three times: the backward does not read the colours).  Only dL/dlabel
+ *                           exists: one sum per (wave, splat) in the blend, sum over pixels of w (dL/dC0 + dL/dC1 + dL/dC2), then one launch that
+ *                           reads it out of the accumulator (exactly 0 where radii <= 0) into dL_dlabel [P] (may be NULL).
+ *                           Exactly one of dL_dout_color and `loss` must be given (else EGS_ERR_MODE): with `loss` the blend forms dL/dx above
+ *                           itself from the image the forward left -- no loss-backward launch, dL/dC never reaches memory -- and writes the quadrant
+ *                           partial sums of the value (the partition and bits of egs_label_bce_forward), which the last launch adds up into
+ *                           loss->loss / loss->running (either may be NULL).  loss->partial_sums: egs_label_bce_partial_count floats, n_partial
+ *                           says how many the caller provides (fewer: EGS_ERR_ARG).
+ *                           `adam` (may be NULL): the label's Adam step taken by the last launch for EVERY row below *active_rows (all rows if NULL),
+ *                           rows with a zero gradient included -- torch's Adam is dense -- with the arithmetic, the step count and the bias
+ *                           corrections of egs_backward_adam: bit-identical to egs_adam_step_capturable fed the same gradient.  adam->param is
+ *                           the label [P], exp_avg / exp_avg_sq have its shape, lr / step are device float[1]; coef: device float[12] scratch.
+ *                           skip_flag set (overflowed frame): no gradient is written, no step is taken and none is counted (the value is still
+ *                           assembled, of the clipped image).  scratch: egs_backward_scratch_bytes(P).  The chain is prologue (tile order, cleared
+ *                           accumulator, step bookkeeping), blend, finish: three launches on `stream`, capturable.
+ *                           CALLER-CHECKED PRECONDITION: with `adam`, this call is the label's ONLY consumer in the optimizer step -- the gradient it
+ *                           forms is the label's whole gradient (see egs_backward_adam). */
+#define EGS_ACT_SCALAR_COLOR 16     /* colors_precomp is float[P], one value per Gaussian, broadcast into the record's three colour slots */
+size_t egs_label_bce_partial_count(int height, int width);
+int egs_label_bce_forward(int height, int width, const float* img /*[3,H,W]*/, const float* obj_mask /*[H,W]*/, float* partial_sums /*scratch*/,
+                          float* loss /*device [1] out, or NULL: deferred*/, float* loss_running_sum /*device [1] in/out or NULL*/, void* stream);
+int egs_label_bce_backward(int height, int width, const float* img, const float* obj_mask, const float* gate /*[H,W] or NULL*/,
+                           const float* upstream_grad /*device [1]*/, float* dL_dimg /*[3,H,W] out*/,
+                           const float* deferred_partial_sums /*NULL unless the forward deferred the value*/, float* deferred_loss /*device [1] out or NULL*/,
+                           float* loss_running_sum /*device [1] in/out or NULL*/, void* stream);
+typedef struct egs_label_loss {      /* HOST struct */
+    const float* img;                /* [3,H,W] the label render the loss is taken on */
+    const float* mask;               /* [H,W] the object mask */
+    const float* gate;               /* [H,W] or NULL: per-pixel factor on the gradient (1 - hand_mask) */
+    const float* upstream;           /* device float[1]: dL/d(loss) */
+    float* partial;                  /* scratch: egs_label_bce_partial_count(H, W) floats */
+    size_t n_partial;                /* floats `partial` holds */
+    float* loss;                     /* device float[1] out, or NULL */
+    float* running;                  /* device float[1] in/out, or NULL */
+} egs_label_loss;
+int egs_backward_label(int P, int64_t R, int width, int height, const int32_t* radii, const void* geom_buffer, const void* binning_buffer,
+                       const void* image_buffer, const float* dL_dout_color /*[3,H,W] or NULL*/, const egs_label_loss* loss /*HOST or NULL*/,
+                       float* dL_dlabel /*[P] out or NULL*/, const egs_adam_leaf* adam /*HOST or NULL*/, float beta1, float beta2, float eps,
+                       float* coef /*device float[12] scratch; needed with adam*/, const int32_t* active_rows /*device int32[1] or NULL*/,
+                       const uint32_t* skip_flag /*device uint32[1] or NULL*/, void* scratch, void* stream, int flags);
+
 /* ---- f-4 (optimizer part): multi-tensor Adam step in one launch.  Same update as torch.optim.Adam(weight_decay=0,
  *      amsgrad=False), which the reference builds at /root/reference/scene/gaussian_model.py:198 and steps at
  *      /root/reference/trainers/train_static.py:137.  All array arguments are HOST arrays of length n_tensors holding

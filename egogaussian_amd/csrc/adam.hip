@@ -92,11 +92,12 @@ static int adam_impl(int n_tensors, float* const* params, const float* const* gr
     const bool dev = step_dev != nullptr;
     if (n_tensors && (!params || !grads || !exp_avg || !exp_avg_sq || !numels)) return EGS_ERR_ARG;
     if (n_tensors && (dev ? (!lr_dev || !counters) : (!lrs || !steps))) return EGS_ERR_ARG;
-    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MAX_TENSORS) {
+    for (int t = 0; t < n_tensors;) {                                // one launch per ADAM_MAX_TENSORS non-empty tensors
         AdamArgs a; a.n = 0; a.b1 = beta1; a.b2 = beta2; a.eps = eps;
         a.skip = skip_flag; a.active_rows = (active_rows && row_floats) ? active_rows : nullptr;
         unsigned blocks = 0;
-        for (int t = t0; t < n_tensors && a.n < ADAM_MAX_TENSORS; t++) {
+        // an empty tensor takes no slot, so a chunk may reach past 16 indices: the next chunk starts where this one stopped
+        for (; t < n_tensors && a.n < ADAM_MAX_TENSORS; t++) {
             if (numels[t] <= 0) continue;
             if (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t]) return EGS_ERR_ARG;
             if (dev ? (!step_dev[t] || !lr_dev[t] || !counters[t]) : steps[t] < 1) return EGS_ERR_ARG;

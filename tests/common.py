@@ -470,6 +470,26 @@ def row_errors(a, ref64, rows):
     return np.abs(a - b).max(1) / np.abs(b).max(1)
 
 
+def row_rule(e_s, evals):
+    """The state-free core of check_grad_rows_vs_float64 (tests/anchors.py holds kernels without a rasterizer state to it): the per-row
+    errors of the subject (e_s) against those of one or more float32 yardstick evaluations (evals, same rows, same float64 reference).
+    -> (subject q50/q90, yardstick q50/q90, subject tail counts, yardstick tail counts, the list of violated conditions):
+      * q50 and q90: subject <= ROW_Q_FACTOR x yardstick (the larger of the evaluations);
+      * for tau in ROW_TAUS: #{e > tau}: subject <= ROW_TAIL_FACTOR x yardstick + ROW_TAIL_SLACK rows."""
+    q_s = np.quantile(e_s, [0.5, 0.9])
+    q_o = np.max([np.quantile(e, [0.5, 0.9]) for e in evals], axis=0)
+    c_s = [int((e_s > tau).sum()) for tau in ROW_TAUS]
+    c_o = [max(int((e > tau).sum()) for e in evals) for tau in ROW_TAUS]
+    bad = []
+    for q, a, b in (("q50", q_s[0], q_o[0]), ("q90", q_s[1], q_o[1])):
+        if not a <= ROW_Q_FACTOR * b:
+            bad.append(f"{q} {a:.2e} > {ROW_Q_FACTOR:g} x {b:.2e}")
+    for tau, cs, co in zip(ROW_TAUS, c_s, c_o):
+        if cs > ROW_TAIL_FACTOR * co + ROW_TAIL_SLACK:
+            bad.append(f"{cs} rows over {tau:g} > {ROW_TAIL_FACTOR:g} x {co} + {ROW_TAIL_SLACK}")
+    return q_s, q_o, c_s, c_o, bad
+
+
 def check_grad_rows_vs_float64(names, subject_grads, st32, g32, st64, g64, near_ids, what="", g32_alt=None, record=None):
     """Max-norm bars divide by the largest entry of the array; a splatting backward has rows decades below it, which such a bar does
     not see.  Here every row answers to ITS OWN magnitude, with the float64 oracle as the reference and the float32 oracle's distance
@@ -514,23 +534,13 @@ def check_grad_rows_vs_float64(names, subject_grads, st32, g32, st64, g64, near_
             continue
         e_s = row_errors(ss, a64, rows)
         evals = [row_errors(o32, a64, rows)] + [row_errors(alt, a64, rows) for alt in (g32_alt or {}).get(name, [])]
-        q_s = np.quantile(e_s, [0.5, 0.9])
-        q_o = np.max([np.quantile(e, [0.5, 0.9]) for e in evals], axis=0)
-        c_s = [int((e_s > tau).sum()) for tau in ROW_TAUS]
-        c_o = [max(int((e > tau).sum()) for e in evals) for tau in ROW_TAUS]
+        q_s, q_o, c_s, c_o, bad = row_rule(e_s, evals)
         if record is not None:
             record[name] = dict(rows=int(rows.size), q50=(float(q_s[0]), float(q_o[0])), q90=(float(q_s[1]), float(q_o[1])),
                                 tails={tau: (cs, co) for tau, cs, co in zip(ROW_TAUS, c_s, c_o)}, excluded=n_excl, visible=n_vis)
         rep.append(f"   {name:12s} {rows.size:6d} rows: q50 {q_s[0]:.1e} (oracle32 {q_o[0]:.1e}), q90 {q_s[1]:.1e} ({q_o[1]:.1e}), "
                    + ", ".join(f"rows > {tau:g}: {cs} ({co})" for tau, cs, co in zip(ROW_TAUS, c_s, c_o))
                    + (f"  [oracle32: the larger of {len(evals)} summation orders]" if len(evals) > 1 else ""))
-        bad = []
-        for q, a, b in (("q50", q_s[0], q_o[0]), ("q90", q_s[1], q_o[1])):
-            if not a <= ROW_Q_FACTOR * b:
-                bad.append(f"{q} {a:.2e} > {ROW_Q_FACTOR:g} x {b:.2e}")
-        for tau, cs, co in zip(ROW_TAUS, c_s, c_o):
-            if cs > ROW_TAIL_FACTOR * co + ROW_TAIL_SLACK:
-                bad.append(f"{cs} rows over {tau:g} > {ROW_TAIL_FACTOR:g} x {co} + {ROW_TAIL_SLACK}")
         if bad:
             amax = float(mag.max())
             e_o = evals[0]

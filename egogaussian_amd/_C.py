@@ -440,7 +440,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  dL_dout_alpha, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, alpha,
                                  debug, activation_flags=0, sh_rest=None, densify_stats=None, guard=None, sink=None,
                                  prologue_scratch=None, object_rotation=None, grad_mask=0, loss_grad=None, object_motion=None, motion_grad=False,
-                                 object_loss=None):
+                                 object_loss=None, opacity_entropy=None, scratch=None):
     """-> (dL_dmeans2D[P,3], dL_dcolors[P,3], dL_dopacity[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dsh[P,M,3],
            dL_dscales[P,3], dL_drotations[P,4]); with sh_rest, dL_dsh is [P,1,3] and a ninth element dL_dsh_rest[P,M-1,3] follows.
     densify_stats (extension): (xyz_gradient_accum[P,1], denom[P,1], max_radii2D[P] or None), float32, updated in place by the kernel
@@ -458,7 +458,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     GRAD_COLORS alone with `colors` given -- the reference's label call, /root/reference/gaussian_renderer/render_helper.py:38-54 --
     takes the colours-only backward: only dL_dcolors is produced, every other position of the result is None.
     object_motion (extension): as given to the forward; dL_dmeans3D is then the gradient of the CANONICAL positions, and one more element
-    follows the result: with motion_grad the pose gradient float32[21] (dL/dA12 [12] in A12's layout, dL/dM9 [9]), else None."""
+    follows the result: with motion_grad the pose gradient float32[21] (dL/dA12 [12] in A12's layout, dL/dM9 [9]), else None.
+    opacity_entropy (extension): an EntropyTerm -- weight * (mean entropy of the visible opacities) is part of the loss: its share joins dL_dopacity
+    (and the Adam step of a fused opacity leaf) inside the preprocess backward, and the term's n_vis / value words are written
+    (include/egs_raster.h egs_backward_entropy_lossgrad).  Not with object_motion, object_loss or the colours-only mask.
+    scratch (extension): a caller-owned uint8 tensor of egs_backward_scratch_bytes(P) for the call to work in instead of a temporary: it is left
+    holding the blend's accumulator (inspection, tests: a later call given it as prologue_scratch with R = 0 runs the per-Gaussian launches
+    alone, on those very sums)."""
     L = _lib.load()
     means3D = _f32c(means3D, "means3D")
     dev = means3D.device
@@ -473,8 +479,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     g_alpha = _opt(_f32c(dL_dout_alpha, "dL_dout_alpha"))
     sh_rest = _opt(_f32c(sh_rest, "sh_rest"))
     M = 0 if sh is None else sh.shape[1] + (0 if sh_rest is None else sh_rest.shape[1])
+    if opacity_entropy is not None and (object_motion is not None or object_loss is not None):
+        raise RuntimeError("opacity_entropy: the term belongs to the static image step (no object_motion, no object_loss)")
     if COLORS_ONLY_BACKWARD and P != 0 and grad_mask == GRAD_COLORS and colors is not None and sink is None and densify_stats is None and object_rotation is None \
-            and loss_grad is None and object_motion is None:          # (a loss gradient computed in the blend needs the full path: dL_dout_color is uninitialised then)
+            and loss_grad is None and object_motion is None and opacity_entropy is None:          # (a loss gradient computed in the blend needs the full path: dL_dout_color is uninitialised then)
         with _hip.device_ctx(dev):
             dcolors = torch.empty((P, 3), device=dev, dtype=torch.float32)
             scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
@@ -519,7 +527,25 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32)
         else:
             rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
-        if P != 0 and loss_grad is not None:
+        if P != 0 and opacity_entropy is not None:
+            if loss_grad is not None and (g_depth is not None or g_alpha is not None):
+                raise RuntimeError("loss_grad: the loss must depend on the colour output only")
+            scratch = prologue_scratch if prologue_scratch is not None else (scratch if scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8))
+            ent_st = opacity_entropy.struct(P, dev)
+            _lib.check(L.egs_backward_entropy_lossgrad(
+                P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
+                float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
+                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
+                _ptr(imageBuffer), None if loss_grad is None else C.byref(loss_grad), C.byref(ent_st),
+                None if loss_grad is not None else _ptr(g_color), None if loss_grad is not None else _ptr(g_depth),
+                None if loss_grad is not None else _ptr(g_alpha), _ptr(dmeans2D), _ptr(dcolors),
+                _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
+                _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
+                C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
+                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+            if owned:
+                sink.mark_stepped()
+        elif P != 0 and loss_grad is not None:
             if g_depth is not None or (g_alpha is not None and object_loss is None):
                 raise RuntimeError("loss_grad: the loss must depend on the colour output only (with object_loss: on colour and alpha)")
             scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
@@ -537,7 +563,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             if owned:
                 sink.mark_stepped()
         elif P != 0 and (owned or prologue_scratch is not None or rot_st is not None):
-            scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
+            scratch = prologue_scratch if prologue_scratch is not None else (scratch if scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8))
             _lib.check(L.egs_backward_adam(
                 P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
                 float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
@@ -550,7 +576,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             if owned:
                 sink.mark_stepped()
         elif P != 0:
-            scratch = torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
+            if scratch is None:
+                scratch = torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
             _lib.check(L.egs_backward(
                 P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
                 float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
@@ -563,6 +590,62 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     if sh_rest is not None:
         return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots, dsh_rest) + tail
     return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots) + tail
+
+
+# ---- opacity-entropy regularisation (include/egs_raster.h: egs_opacity_entropy_*, egs_backward_entropy_lossgrad) -------------------
+class EntropyTerm:
+    """The device words of one entropy term: `weight` float32[1] (read by the kernels: a captured step changes it without re-capture),
+    `value` float32[1] (the UNWEIGHTED mean entropy of the visible opacities, written by the reduction), `n_vis` int32[1] (the visible
+    rows it counted), `upstream` float32[1] or None (= 1), and the reduction's scratch."""
+
+    def __init__(self, weight, device, upstream=None):
+        if torch.is_tensor(weight):
+            if not (weight.is_cuda and weight.dtype == torch.float32 and weight.numel() == 1):
+                raise RuntimeError("opacity_entropy: the weight is a float or a float32 scalar tensor on the rasterizer's device")
+            self.weight = weight.detach().reshape(1)
+        else:
+            self.weight = torch.full((1,), float(weight), device=device, dtype=torch.float32)
+        self.upstream = None if upstream is None else _f32c(upstream.detach(), "upstream").reshape(1)
+        self.value = torch.empty((1,), device=device, dtype=torch.float32)
+        self.n_vis = torch.zeros((1,), device=device, dtype=torch.int32)
+        self.scratch = None
+        self._st = None
+
+    def struct(self, P, dev):
+        need = max(int(_lib.load().egs_opacity_entropy_scratch_bytes(int(P))), 256)
+        if self.scratch is None or self.scratch.numel() < need:
+            self.scratch = torch.empty((need,), device=dev, dtype=torch.uint8)
+        st = self._st = _lib.OpacityEntropy()
+        st.weight, st.upstream, st.scratch = self.weight.data_ptr(), _ptr(self.upstream), self.scratch.data_ptr()
+        st.n_vis, st.value = self.n_vis.data_ptr(), self.value.data_ptr()
+        return st
+
+
+def opacity_entropy_forward(opacity, radii, term, logit=False, active_count=None, want_activated=False):
+    """The stand-alone reduction: fills term.value / term.n_vis from `opacity` [P] (logits with logit=True) and `radii` [P] int32.
+    -> the activated opacities float32[P] the kernels formed (want_activated), else None."""
+    L = _lib.load()
+    opacity = _f32c(opacity, "opacity").reshape(-1)
+    P, dev = opacity.shape[0], opacity.device
+    if radii.dtype != torch.int32 or radii.numel() != P or radii.device != dev:
+        raise RuntimeError("opacity_entropy: radii is the rasterizer's int32[P] on the opacities' device")
+    with _hip.device_ctx(dev):
+        act = torch.empty((P,), device=dev, dtype=torch.float32) if want_activated else None
+        _lib.check(L.egs_opacity_entropy_forward(P, _ptr(opacity), ACT_LOGIT_OPACITY if logit else 0, _ptr(radii.contiguous()), _ptr(active_count),
+                                                 _ptr(act), C.byref(term.struct(P, dev)), _stream(dev)))
+    return act
+
+
+def opacity_entropy_backward(opacity, radii, term, logit=False, active_count=None):
+    """dL/dopacity float32[P] of term.weight * term.upstream * value, w.r.t. what opacity_entropy_forward received (reads term.n_vis)."""
+    L = _lib.load()
+    opacity = _f32c(opacity, "opacity").reshape(-1)
+    P, dev = opacity.shape[0], opacity.device
+    with _hip.device_ctx(dev):
+        g = torch.empty((P,), device=dev, dtype=torch.float32)
+        _lib.check(L.egs_opacity_entropy_backward(P, _ptr(opacity), ACT_LOGIT_OPACITY if logit else 0, _ptr(radii.contiguous()), _ptr(active_count),
+                                                  C.byref(term.struct(P, dev)), _ptr(g), _stream(dev)))
+    return g
 
 
 # ---- the label phase (include/egs_raster.h: egs_label_bce_*, egs_backward_label) -----------------------------------------------

@@ -61,8 +61,9 @@ def attach(gaussians, optimizer=True, capturable=False, fuse_optimizer=False, pr
     capturable=True     ... as FusedAdam(capturable=True): step counts and learning rates on the device (graph.GraphedTrainStep);
     fuse_optimizer=True this package's render() hands that optimizer to the rasterizer, whose backward then takes the Adam step of
                         the parameters it differentiates (no gradient arrays).  ONLY for trainers whose loss reaches the model
-                        through that one render -- e.g. not while the entropy term of train_static.py:97-102 is active; FusedAdam
-                        raises if a second gradient path shows up.  Needs capturable=True.
+                        through that one render; FusedAdam raises if a second gradient path shows up.  The entropy term of
+                        train_static.py:97-102 is the one such path the rasterizer takes itself: render(..., opacity_entropy=0.1)
+                        instead of the torch expression.  Needs capturable=True.
     provenance=True     the activated tensors the model's getters return remember their raw parameters, so that the rasterizer can take
                         those instead when the reference's own render() hands it the activated ones (see below); False: plain tensors.
     Returns `gaussians`."""

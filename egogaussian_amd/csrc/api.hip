@@ -7,6 +7,7 @@
 #include "backward_prologue.h"
 #include "loss_window.h"
 #include "label_bce.h"
+#include "opacity_entropy.h"
 #include <string.h>
 #include <vector>
 #include <mutex>
@@ -512,9 +513,15 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
                  float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
                  float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
                  const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
-                 void* stream, int debug, const egs_loss_grad* loss_grad = nullptr, const egs_object_loss* obj_loss = nullptr) {
+                 void* stream, int debug, const egs_loss_grad* loss_grad = nullptr, const egs_object_loss* obj_loss = nullptr,
+                 const egs_opacity_entropy* entropy = nullptr) {
     int rc = check_dims(P, width, height); if (rc) return rc;
     if (activation_flags & EGS_ACT_SCALAR_COLOR) return EGS_ERR_MODE;  // a scalar colour's gradient is egs_backward_label's: dL_dcolors here is [P,3]
+    // the opacity-entropy term (egs_backward_entropy_lossgrad): the static stages' -- no object motion, and the opacities must get their gradient
+    if (entropy) {
+        if (!entropy->weight || !entropy->n_vis || (P > 0 && !entropy->scratch) || obj_loss) return EGS_ERR_ARG;
+        if (activation_flags & EGS_ACT_OBJECT_MOTION) return EGS_ERR_MODE;
+    }
     EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     // the image loss's gradient computed by the blend itself (egs_backward_lossgrad): colour gradients only, three channels
     EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr; EgsObjLossK olk = {};
@@ -538,6 +545,7 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
     }
     if (P == 0) {
         if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, (hipStream_t)stream));
+        if (entropy) EGS_TRY(egs_launch_entropy_reduce(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, entropy->n_vis, entropy->value, (hipStream_t)stream));
         if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, (hipStream_t)stream));
         return 0;
     }
@@ -550,6 +558,7 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
         return EGS_ERR_ARG;
     if (misaligned(geom_buffer, binning_buffer, image_buffer) || ((uintptr_t)scratch & 15u)) return EGS_ERR_ARG;
     if (colors_only) {
+        if (entropy) return EGS_ERR_MODE;                             // (no opacity gradient on this path)
         if (!dL_dcolors || (R > 0 && !binning_buffer)) return EGS_ERR_ARG;
         rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
         hipStream_t s = (hipStream_t)stream;
@@ -634,11 +643,17 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
     }
     egs_prof_start(EGS_K_PREPROCESS_BWD, s);
     EgsCamera cam = { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy };
+    // the entropy term: n_vis and the value from the records and radii of this frame, then the instantiation that adds the rows' shares
+    EgsEntropy ek = {};
+    if (entropy) {
+        EGS_TRY(egs_launch_entropy_reduce(P, nullptr, g.rec, 0, radii, nullptr, nullptr, entropy->scratch, entropy->n_vis, entropy->value, s));
+        ek = EgsEntropy{ entropy->n_vis, entropy->weight, entropy->upstream };
+    }
     EGS_TRY(egs_launch_preprocess_backward(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, scales, scale_modifier, rotations,
                                            cov3D_precomp, activation_flags, cam, radii, g, grad_acc, colors_precomp != nullptr, dL_dmeans2D,
                                            dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, sh_apart ? nullptr : dL_dsh, dL_dscales,
                                            dL_drotations, stat_grad_accum, stat_denom, stat_max_radii, skip_flag, pp_sinks ? &ks : nullptr, orot, mh.k,
-                                           sh_apart ? 1 : 0, s));
+                                           sh_apart ? 1 : 0, s, entropy ? &ek : nullptr));
     if (sh_apart) EGS_TRY(egs_launch_sh_backward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, radii, g, dL_dcolors, dL_dsh,
                                                  dL_dsh_rest, dL_dmeans3D, sh_sinks ? &ks_sh : nullptr, mh.k, s));
     // the pose gradient: the lines the launch that finished the positions' gradient wrote (one per 64 rows from the spherical-harmonics
@@ -700,6 +715,25 @@ int egs_backward_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const 
                          binning_buffer, image_buffer, nullptr, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
                          dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
                          skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad);
+}
+
+int egs_backward_entropy_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
+                          const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, int width, int height, float tan_fovx, float tan_fovy, const int32_t* radii,
+                          const void* geom_buffer, const void* binning_buffer, const void* image_buffer, const egs_loss_grad* loss_grad,
+                          const egs_opacity_entropy* entropy, const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_alpha,
+                          float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
+                          float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
+                          const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
+                          void* stream, int debug) {
+    if (!entropy) return EGS_ERR_ARG;
+    if (loss_grad && (dL_dout_color || dL_dout_depth || dL_dout_alpha)) return EGS_ERR_MODE;      // (the blend forms the image gradient itself)
+    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
+                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
+                         binning_buffer, image_buffer, dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dmeans2D, dL_dcolors, dL_dopacity,
+                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
+                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad, nullptr, entropy);
 }
 
 // egs_backward_prologue (HOST struct) -> the side jobs a loss backward launch carries

@@ -175,7 +175,12 @@ hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* mean
                                           float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
                                           float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
                                           const EgsSink* sink /*NULL: gradients only*/, EgsObjRot rot, EgsMotion mot,
-                                          int motion_finished_later /*egs_launch_sh_backward follows and finishes the positions' gradient*/, hipStream_t s);
+                                          int motion_finished_later /*egs_launch_sh_backward follows and finishes the positions' gradient*/, hipStream_t s,
+                                          const struct EgsEntropy* ent = nullptr /*opacity_entropy.h: the entropy term's share of dL/dopacity is added before the sigmoid chain (no motion)*/);
+// The opacity-entropy reduction (entropy.hip): per-workgroup lines in `scratch`, then one finish workgroup -> *n_vis, *value (may be NULL).
+// rec != NULL: the activated opacities a rasterizer forward parked in its records (opac, logit, active_count, activated are not read).
+hipError_t egs_launch_entropy_reduce(int P, const float* opac, const float4* rec, int logit, const int32_t* radii, const int32_t* active_count,
+                                     float* activated, void* scratch, uint32_t* n_vis, float* value, hipStream_t s);
 // Spherical harmonics as separate launches (M > 1 coefficients, or DC / rest given as two arrays: sh_rest != NULL).  The
 // preprocess launchers are then called with shs = NULL: the forward leaves the record's colour open, the backward leaves
 // dL/dSH and the view-direction part of dL/dmean3D to egs_launch_sh_backward (which must run after it).

@@ -17,6 +17,8 @@
 #include "bin_walk.h"              // the count pass of the tile bucketing, carried by k_preprocess_count
 #include "backward_prologue.h"
 #include "object_motion.h"          // the rigid object motion of the positions (EGS_ACT_OBJECT_MOTION)
+#include "opacity_entropy.h"        // the opacity-entropy term joins dL/dopacity in k_preprocess_backward<.., ENT = true>
+#include <type_traits>
 
 namespace {
 
@@ -394,7 +396,9 @@ __global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu
 #define ST_SH 2816
 // MOT (object motion, object_motion.h): 0 none; 1 the row is placed, its gradient stays dL/dp' (the spherical-harmonics launch finishes it);
 // 2 the gradient is finished here: dL/dp = A^T dL/dp', the row's pose terms go to red[0..12).  MOT != 0: a rotated row's dL/dM terms go to red[12..21).
-template <bool SINK, int MOT>
+// ENT (opacity_entropy.h): a visible row's share of the opacity-entropy term, ent_coef * dh/do, joins dL/dopacity before the sigmoid chain, the
+// dopac store and the stage of the sink -- the Adam step inside the kernel sees the whole gradient of the logit.
+template <bool SINK, int MOT, bool ENT = false>
 __device__ __forceinline__ void pp_bwd_one(
     const int i, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ scales, float mod, const float* __restrict__ rots, const float* __restrict__ cov3D_in, int act,
@@ -404,7 +408,8 @@ __device__ __forceinline__ void pp_bwd_one(
     float* __restrict__ dopac, float* __restrict__ dmeans3D, float* __restrict__ dcov3D, float* __restrict__ dsh,
     float* __restrict__ dscales, float* __restrict__ drots,
     float* __restrict__ stat_grad_accum, float* __restrict__ stat_denom, float* __restrict__ stat_max_radii,
-    const uint32_t* __restrict__ skip_flag, float* __restrict__ stage, const unsigned fused, const EgsObjRot rot, const EgsMotion mot, float* red) {
+    const uint32_t* __restrict__ skip_flag, float* __restrict__ stage, const unsigned fused, const EgsObjRot rot, const EgsMotion mot, float* red,
+    [[maybe_unused]] const float ent_coef = 0.f) {
     // SINK: the gradients of the leaves in `fused` (bit = EGS_SINK_*) also go to `stage` (LDS), from where the workgroup applies
     // Adam to its 256 rows; their dX arrays may then be NULL (nothing written)
     const unsigned tid = threadIdx.x;
@@ -451,6 +456,7 @@ __device__ __forceinline__ void pp_bwd_one(
     if (dcolors) { dcolors[3 * i] = acc[6]; dcolors[3 * i + 1] = acc[7]; dcolors[3 * i + 2] = acc[8]; }
     {   // logit opacities: chain through the sigmoid with the activated value the forward parked in the record
         const float o = rec[(size_t)i * EGS_SPLAT_REC_F4 + 1].y;
+        if constexpr (ENT) { if (vis) acc[5] += egs_entropy_grad(ent_coef, o); }
         const float go = (vis && (act & EGS_ACT_LOGIT_OPACITY)) ? acc[5] * (o * (1.f - o)) : acc[5];
         if (dopac) dopac[i] = go;
         if (SINK && (fused & (1u << EGS_SINK_OPACITY))) stage[ST_OPAC + tid] = go;
@@ -695,7 +701,7 @@ __device__ __forceinline__ void pp_bwd_one(
 // read a second time by another launch: 16 B in + 12 B out per element become 12 + 12, and the step has one launch less.
 // 896 float4 tasks per workgroup (64 x (3 + 1 + 3 + 4 + 3)), task -> leaf boundaries fall on wave boundaries.
 // MOT: see pp_bwd_one.  The pose sums are a workgroup-uniform branch on the scratch pointers: a constant pose (no gradient asked for) pays no shuffle.
-template <bool SINK, int MOT>
+template <bool SINK, int MOT, bool ENT = false>
 __global__ __launch_bounds__(256) void k_preprocess_backward(
     int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
     const float* __restrict__ scales, float mod, const float* __restrict__ rots, const float* __restrict__ cov3D_in, int act,
@@ -705,7 +711,7 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(
     float* __restrict__ dopac, float* __restrict__ dmeans3D, float* __restrict__ dcov3D, float* __restrict__ dsh,
     float* __restrict__ dscales, float* __restrict__ drots,
     float* __restrict__ stat_grad_accum, float* __restrict__ stat_denom, float* __restrict__ stat_max_radii,
-    const uint32_t* __restrict__ skip_flag, EgsSink sink, EgsObjRot rot, EgsMotion mot) {
+    const uint32_t* __restrict__ skip_flag, EgsSink sink, EgsObjRot rot, EgsMotion mot, std::conditional_t<ENT, EgsEntropy, EgsNoEntropy> ent) {
     __shared__ __attribute__((aligned(16))) float stage[SINK ? 4 * EGS_SINK_TASKS : 4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned fused = 0;
@@ -718,10 +724,12 @@ __global__ __launch_bounds__(256) void k_preprocess_backward(
 #pragma unroll
         for (int k = 0; k < EGS_MOTION_SUMS; k++) red[k] = 0.f;
     }
+    float ent_coef = 0.f;
+    if constexpr (ENT) ent_coef = egs_entropy_coef(ent.n_vis, ent.weight, ent.upstream);
     if (i < P)
-        pp_bwd_one<SINK, MOT>(i, D, M, means3D, shs, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H, tanfovx, tanfovy, radii, clamped, rec,
+        pp_bwd_one<SINK, MOT, ENT>(i, D, M, means3D, shs, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H, tanfovx, tanfovy, radii, clamped, rec,
                          grad_acc, grad_acc + (size_t)P * EGS_GRAD_STRIDE, egs_hot_slots((size_t)P), dmeans2D, dcolors, dopac, dmeans3D, dcov3D, dsh, dscales, drots, stat_grad_accum, stat_denom,
-                         stat_max_radii, skip_flag, stage, fused, rot, mot, red);
+                         stat_max_radii, skip_flag, stage, fused, rot, mot, red, ent_coef);
     if constexpr (MOT != 0) {
         __shared__ float wsum_p[4][EGS_MOTION_POSE_SUMS], wsum_m[4][EGS_MOTION_ROT_SUMS];
         if (MOT == 2 && mot.pose_partial) egs_motion_block_sum<EGS_MOTION_POSE_SUMS>(red, wsum_p, mot.pose_partial + (size_t)blockIdx.x * EGS_MOTION_POSE_SUMS);
@@ -1429,23 +1437,29 @@ hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* mean
                                           int colors_given, float* dmeans2D, float* dcolors, float* dopac,
                                           float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
                                           float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
-                                          const EgsSink* sink, EgsObjRot rot, EgsMotion mot, int motion_finished_later, hipStream_t s) {
+                                          const EgsSink* sink, EgsObjRot rot, EgsMotion mot, int motion_finished_later, hipStream_t s,
+                                          const EgsEntropy* ent) {
     if (P == 0) return hipSuccess;
+    if (ent && mot.A) return hipErrorInvalidValue;                   // (the entropy instantiations exist without object motion: the static stages)
     EgsSink none = {};
+    const EgsNoEntropy no_ent = {};
 #define PPB_ARGS P, D, M, means3D, colors_given ? nullptr : shs, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, \
                  cam.H, cam.tanfovx, cam.tanfovy, radii, g.clamped, g.rec, grad_acc, dmeans2D, dcolors, dopac, dmeans3D, \
                  dcov3D, colors_given ? nullptr : dsh, cov3D ? nullptr : dscales, cov3D ? nullptr : drots, \
                  stat_grad_accum, stat_denom, stat_max_radii, skip_flag
     const dim3 grid((P + 255) / 256), block(256);
-    if (!mot.A) {
-        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 0>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess_backward<false, 0>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+    if (ent) {
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 0, true>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot, *ent);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 0, true>), grid, block, 0, s, PPB_ARGS, none, rot, mot, *ent);
+    } else if (!mot.A) {
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 0>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot, no_ent);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 0>), grid, block, 0, s, PPB_ARGS, none, rot, mot, no_ent);
     } else if (motion_finished_later) {
-        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 1>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess_backward<false, 1>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 1>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot, no_ent);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 1>), grid, block, 0, s, PPB_ARGS, none, rot, mot, no_ent);
     } else {
-        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 2>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess_backward<false, 2>), grid, block, 0, s, PPB_ARGS, none, rot, mot);
+        if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 2>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot, no_ent);
+        else hipLaunchKernelGGL((k_preprocess_backward<false, 2>), grid, block, 0, s, PPB_ARGS, none, rot, mot, no_ent);
     }
 #undef PPB_ARGS
     return hipGetLastError();

@@ -496,3 +496,38 @@ def label_bce_loss(image, obj_mask, grad_gate=None, running_sum=None, defer_valu
             node = fn
     m = obj_mask.reshape(image.shape[-2], image.shape[-1])
     return _LabelBCE.apply(image, m, grad_gate, running_sum, defer_value, node, node is not None)
+
+
+class _OpacityEntropy(torch.autograd.Function):
+    """weight * (mean entropy of the visible opacities) over the stand-alone kernels (include/egs_raster.h egs_opacity_entropy_forward /
+    _backward): a deterministic reduction forward (two launches), one launch backward."""
+
+    @staticmethod
+    def forward(ctx, opacity, radii, weight, logit, active_count):
+        from . import _C
+        o = _need_hip(opacity, "opacity")
+        term = _C.EntropyTerm(weight, o.device)
+        _C.opacity_entropy_forward(o.detach(), radii, term, logit=logit, active_count=active_count)
+        ctx.save_for_backward(o, radii)
+        ctx.term, ctx.logit, ctx.active_count, ctx.shape = term, bool(logit), active_count, opacity.shape
+        ctx.n_vis = term.n_vis
+        return (term.value * term.weight).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _C
+        o, radii = ctx.saved_tensors
+        ctx.term.upstream = g.detach().reshape(1).float().contiguous()
+        d = _C.opacity_entropy_backward(o.detach(), radii, ctx.term, logit=ctx.logit, active_count=ctx.active_count)
+        return d.view(ctx.shape), None, None, None, None
+
+
+def opacity_entropy(opacity, radii, weight=1.0, logit=False, active_count=None):
+    """weight * mean over the visible Gaussians (radii > 0) of -o log(o + 1e-10) - (1 - o) log(1 - o + 1e-10): the static stages' entropy
+    regulariser (losses.opacity_entropy is the torch mirror; /root/reference/trainers/train_static.py:97-102 adds it with weight 0.1).
+    opacity: [P] or [P,1], the activated opacities -- or, with logit=True, the raw parameter (`_opacity`), activated inside the kernels; the
+    gradient comes back w.r.t. what was given.  radii: the render's int32[P].  weight: a float or a float32 device scalar (a constant of the
+    loss).  active_count: int32[1] device tensor of a capacity-sized model -- rows at or beyond it are skipped whatever they hold.
+    Three HIP launches in all instead of the expression's dozen each way; deterministic (no float atomics).  No visible Gaussian: NaN and a
+    zero gradient.  For a trainer that does not fuse its optimizer; one that does asks render(opacity_entropy=) for the term instead."""
+    return _OpacityEntropy.apply(opacity, radii, weight, logit, active_count)

@@ -20,7 +20,8 @@ What is baked into the captured launches and therefore needs `recapture()` when 
 count is a device word the kernels read), the image size, `pc.active_sh_degree` (the reference raises it every 1000
 iterations, scene/gaussian_model.py:176-178), the background tensor's address, `lambda_dssim`.  What does not: camera,
 ground truth, accum_R / accum_T, gate and object-mask contents (copied in per call), the VALUES of a trainable pose's two parameters
-(pose=: they are tensors of the captured step like the model's) and the learning rates (device scalars; `__call__` pushes
+(pose=: they are tensors of the captured step like the model's), the weight of the entropy term (entropy_reg=: a device scalar pushed
+like a learning rate) and the learning rates (device scalars; `__call__` pushes
 host-side edits of `param_groups[i]["lr"]` -- the reference's per-iteration `update_learning_rate` -- before each replay).
 """
 import torch
@@ -130,8 +131,18 @@ class _StaticCamera:
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
-                 motion=False, object_loss=None, pose=None, label_phase=False):
-        """label_phase:   the label phase of the static stage (/root/reference/trainers/train_static.py:104-109) instead of the image step:
+                 motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False):
+        """entropy_reg:   the static image step with the entropy-regularisation phase available (/root/reference/trainers/train_static.py:97-102,
+                       trainers/train_static_bg.py:105-110: between std_train_iter and std_train_iter + entropy_reg_iter the loss also holds
+                       0.1 * the mean binary entropy of the visible opacities).  The rasterizer's backward adds the term's share to the
+                       gradient of the opacity logits itself (render(opacity_entropy=)), so the opacity stays a fused leaf and the step
+                       stays the captured one.  The weight is a DEVICE scalar pushed before each replay like the learning rates:
+                       `step.entropy_weight = 0.1` at std_train_iter, `= 0.0` when the phase ends -- no re-capture; it starts at 0, and with
+                       weight 0 a replay leaves every parameter and moment bit-identical to the step captured without this option.
+                       `step.entropy` (device float32[1]) holds the last replay's UNWEIGHTED mean entropy.  `step.loss` and `loss_sum` stay
+                       the image loss alone: the term's value is not added to them.  Goes with gated, densify_stats, steps_per_replay,
+                       double_buffer and capacity-sized models; not with dynamic, motion, pose, object_loss, label_phase (ValueError).
+        label_phase:   the label phase of the static stage (/root/reference/trainers/train_static.py:104-109) instead of the image step:
                        the label render with the label as one value per Gaussian, BCE-with-logits of its channel mean against the frame's
                        object mask (gated: the hand-mask hook), Adam on the label ALONE -- forward chain, backward prologue, the scalar
                        colours-only blend that forms the loss gradient itself, and one launch that reads dL/dlabel out, takes the step and
@@ -178,6 +189,14 @@ class GraphedTrainStep:
                        (renderer.render, optimizer=): no gradient arrays, no optimizer launch for them; the step's loss must then
                        depend on the model through that one render only -- which is the step this class captures.  Results are
                        bit-identical either way."""
+        self.entropy_reg = bool(entropy_reg)
+        if self.entropy_reg:
+            for name, on in (("dynamic", dynamic), ("motion", motion), ("pose", pose is not None), ("object_loss", object_loss is not None),
+                             ("label_phase", label_phase)):
+                if on:
+                    raise ValueError(f"GraphedTrainStep(entropy_reg=True) does not go with {name}: the entropy term belongs to the static image step")
+        self._entropy_weight_host, self._entropy_weight_dev, self._entropy_weight_pushed = 0.0, None, None
+        self.entropy = None
         self.label_phase = bool(label_phase)
         if self.label_phase:
             for name, on in (("dynamic", dynamic), ("motion", motion), ("pose", pose is not None), ("object_loss", object_loss is not None),
@@ -224,6 +243,24 @@ class GraphedTrainStep:
         self.recaptures = 0               # re-captures this object did on its own (overflow)
         self.skipped_frames_seen = 0      # overflow events noticed by check()
         self._calls = 0
+
+    @property
+    def entropy_weight(self):
+        """The weight of the entropy term (entropy_reg=True): a host float, pushed into the device scalar the captured kernels read
+        before the next replay -- the reference's 0.1 during its entropy phase, 0 outside."""
+        return self._entropy_weight_host
+
+    @entropy_weight.setter
+    def entropy_weight(self, w):
+        if not self.entropy_reg:
+            raise ValueError("entropy_weight: this step was built without entropy_reg=True")
+        self._entropy_weight_host = float(w)
+
+    def _sync_entropy_weight(self):
+        """A fill when the weight was edited since the last push (as FusedAdam.sync_lr for the learning rates)."""
+        if self._entropy_weight_dev is not None and self._entropy_weight_pushed != self._entropy_weight_host:
+            self._entropy_weight_dev.fill_(self._entropy_weight_host)
+            self._entropy_weight_pushed = self._entropy_weight_host
 
     def _dynamic_kwargs(self, f):
         kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=self.which_object, during_training=False)
@@ -348,6 +385,8 @@ class GraphedTrainStep:
         kw = dict(self.render_kwargs)
         if self.dynamic:
             kw.update(self._dynamic_kwargs(f))
+        if self.entropy_reg:
+            kw["opacity_entropy"] = self._entropy_weight_dev         # the device scalar itself: the kernels read it at every replay
         out = render(f["cam"], self.pc, self.pipe, self.bg, fused_densify_stats=self.densify_stats, guard=self.guard,
                      optimizer=self.opt if self.fuse_optimizer else None, color_only=self.object_loss is None, **kw)      # (the image loss reads the colour image only)
         # the loss value and the running sum are produced by the loss BACKWARD kernel (nothing reads them before): two launches less
@@ -412,6 +451,9 @@ class GraphedTrainStep:
             self.accum_T = first["accum_T"]
             self.obj_mask = first["obj_mask"]
         self._one = torch.ones((), device=dev)
+        if self.entropy_reg and self._entropy_weight_dev is None:
+            self._entropy_weight_dev = torch.zeros((), device=dev)
+        self._sync_entropy_weight()
         if getattr(self, "loss_sum", None) is None:
             self.loss_sum = torch.zeros((), device=dev)                  # sum of the losses of every iteration run through this object
         if self.object_loss is not None and self.loss_terms is None:
@@ -459,6 +501,7 @@ class GraphedTrainStep:
                     self.losses.append(self.loss)
                 self.image = out["render"].detach()
                 self.radii = out["radii"]
+                self.entropy = out.get("opacity_entropy")              # (entropy_reg: written by every replay's backward)
                 self.visibility_filter = out["visibility_filter"]      # follows every replay (a view of the rasterizer's saved state)
                 self.viewspace_grad = out["viewspace_points"].grad
             finally:
@@ -470,7 +513,7 @@ class GraphedTrainStep:
             # the same iterations recorded once more on a second set of static frames; what the two captures share -- parameters,
             # optimizer state, guard words, loss_sum -- is shared by address
             first = dict(graph=self.graph, frames=self._frames, slots=self._slots, loss=self.loss, losses=self.losses, image=self.image,
-                         radii=self.radii, visibility_filter=self.visibility_filter, viewspace_grad=self.viewspace_grad)
+                         entropy=self.entropy, radii=self.radii, visibility_filter=self.visibility_filter, viewspace_grad=self.viewspace_grad)
             frames2 = self._frames.clone()
             off, _ = self._frame_layout(self.gt)
             slots2 = []
@@ -505,6 +548,7 @@ class GraphedTrainStep:
             torch.cuda.current_stream(dev).wait_stream(side)
             torch.cuda.synchronize(dev)
             second = dict(graph=g2, frames=frames2, slots=slots2, loss=loss2, losses=losses2, image=out2["render"].detach(), radii=out2["radii"],
+                          entropy=out2.get("opacity_entropy"),
                           visibility_filter=out2["visibility_filter"], viewspace_grad=out2["viewspace_points"].grad)
             self._slots = first["slots"]
             self._sets = [first, second]
@@ -567,6 +611,7 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: the model reallocated its arrays (CapacityGaussians.grow) after this step was captured; "
                                "the captured launches point at freed memory -- call recapture() first")
         self.opt.sync_lr()                                           # a fill per group whose learning rate was edited since the last call
+        self._sync_entropy_weight()
         self.graph.replay()
         self._calls += 1
         if self.check_every > 0 and self._calls % self.check_every == 0:
@@ -600,11 +645,13 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: the model reallocated its arrays (CapacityGaussians.grow) after this step was captured; "
                                "the captured launches point at freed memory -- call recapture() first")
         self.opt.sync_lr()
+        self._sync_entropy_weight()
         main.wait_event(self._copied[b])
         st["graph"].replay()
         self._done[b].record(main)
         self._used[b] = True
         self.loss, self.losses, self.image, self.radii = st["loss"], st["losses"], st["image"], st["radii"]
+        self.entropy = st["entropy"]
         self.visibility_filter, self.viewspace_grad = st["visibility_filter"], st["viewspace_grad"]
         self._calls += 1
         if self.check_every > 0 and self._calls % self.check_every == 0:

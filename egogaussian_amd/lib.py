@@ -77,6 +77,10 @@ class LabelLoss(C.Structure):                    # egs_label_loss
                 ("n_partial", C.c_size_t), ("loss", C.c_void_p), ("running", C.c_void_p)]
 
 
+class OpacityEntropy(C.Structure):               # egs_opacity_entropy
+    _fields_ = [("weight", C.c_void_p), ("upstream", C.c_void_p), ("scratch", C.c_void_p), ("n_vis", C.c_void_p), ("value", C.c_void_p)]
+
+
 ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
@@ -138,6 +142,12 @@ SIGNATURES = {
     "egs_label_bce_backward": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egs_backward_label": (C.c_int, [i32, i64, i32, i32, vp, vp, vp, vp, vp, C.POINTER(LabelLoss), vp, C.POINTER(AdamLeaf), f32, f32, f32, vp, vp, vp,
                                      vp, vp, i32]),
+    "egs_opacity_entropy_scratch_bytes": (C.c_size_t, [i32]),
+    "egs_opacity_entropy_forward": (C.c_int, [i32, vp, i32, vp, vp, vp, C.POINTER(OpacityEntropy), vp]),
+    "egs_opacity_entropy_backward": (C.c_int, [i32, vp, i32, vp, vp, C.POINTER(OpacityEntropy), vp, vp]),
+    "egs_backward_entropy_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
+                                                vp, vp, vp, vp, C.POINTER(LossGrad), C.POINTER(OpacityEntropy), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, vp, vp, vp, C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
     "egs_adam_step": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "egs_adam_workgroups": (C.c_int64, [i64]),
     "egs_adam_step_capturable": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]),

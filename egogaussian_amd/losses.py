@@ -77,3 +77,13 @@ def label_bce_loss(render_label, obj_mask):
     fused.label_bce_loss takes it as grad_gate.  The oracle of the HIP kernels behind fused.label_bce_loss, on any device and in any float type."""
     x = render_label.mean(0, keepdim=True)
     return torch.nn.functional.binary_cross_entropy_with_logits(x, obj_mask.to(x.dtype).reshape(x.shape))
+
+
+def opacity_entropy(opacity, visibility):
+    """The static stages' entropy regulariser, unweighted (/root/reference/trainers/train_static.py:97-102, trainers/train_static_bg.py:105-110,
+    where it enters the loss with the factor 0.1): the mean over the visible Gaussians of the binary entropy of their activated opacity,
+        -o log(o + 1e-10) - (1 - o) log(1 - o + 1e-10),   o = opacity[visibility].
+    opacity: get_opacity, [P,1] or [P]; visibility: the render's visibility_filter (bool[P]).  No visible Gaussian: NaN, as torch's mean() of
+    an empty tensor.  The oracle of the HIP kernels behind fused.opacity_entropy and render(opacity_entropy=), on any device and in any float type."""
+    vis = opacity[visibility]
+    return (-vis * torch.log(vis + 1e-10) - (1 - vis) * torch.log(1 - vis + 1e-10)).mean()

@@ -238,7 +238,8 @@ class FusedAdam(torch.optim.Optimizer):
                     if p.grad is not None and not sunk[p]:
                         raise RuntimeError("FusedAdam: a parameter whose Adam step was taken inside the rasterizer backward also received a gradient "
                                            "through another path of the loss; that gradient would be lost.  Render without optimizer= (or "
-                                           "GraphedTrainStep(fuse_optimizer=False)) when the rasterizer is not the parameter's only consumer")
+                                           "GraphedTrainStep(fuse_optimizer=False)) when the rasterizer is not the parameter's only consumer; "
+                                           "for the entropy term on the opacities, ask the render for it instead: render(..., opacity_entropy=w)")
                     continue
                 if p.grad is None:
                     continue

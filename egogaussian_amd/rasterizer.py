@@ -41,8 +41,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 activation_flags=0, sh_rest=None, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                object_rotation=None, color_only=False, object_motion=None, motion_A12=None, motion_M=None):
+                object_rotation=None, color_only=False, object_motion=None, motion_A12=None, motion_M=None, opacity_entropy=None):
         rs = raster_settings
+        # opacity_entropy: a _C.EntropyTerm -- weight * (mean entropy of the visible opacities) is part of the loss this call's backward
+        # differentiates: its share joins dL/dopacity (and a fused opacity leaf's Adam step) inside the preprocess backward
+        if opacity_entropy is not None and object_motion is not None:
+            raise RuntimeError("opacity_entropy does not go with object_motion: the term belongs to the static stages")
+        ctx.opacity_entropy = opacity_entropy
         if guard is not None and getattr(guard, "deferred", False) and any(ctx.needs_input_grad) and not getattr(optimizer, "capturable", False) \
                 and not getattr(guard, "_warned", False):
             # a deferred frame that turns out clipped is voided ON THE DEVICE -- by the statistics and the Adam step that read the overflow
@@ -143,7 +148,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos, geom,
             ctx.num_rendered, binning, img, alpha, rs.debug, ctx.activation_flags, sh_rest if split else None, ctx.densify_stats, ctx.guard,
             ctx.sink, ctx.prologue_scratch, ctx.object_rotation, grad_mask, loss_grad=None if ctx.loss_grad is None else ctx.loss_grad[0],
-            object_loss=None if (ctx.loss_grad is None or len(ctx.loss_grad) <= 3) else ctx.loss_grad[3], object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]))
+            object_loss=None if (ctx.loss_grad is None or len(ctx.loss_grad) <= 3) else ctx.loss_grad[3], object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]),
+            opacity_entropy=ctx.opacity_entropy)
         g_A12 = g_M = None
         if ctx.object_motion is not None:
             pose = grads[-1]
@@ -159,7 +165,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (g_means3D, g_means2D, none_if_absent(g_sh, sh), none_if_absent(g_colors, colors_precomp),
                 g_opac, none_if_absent(g_scales, scales),
                 none_if_absent(g_rots, rotations), none_if_absent(g_cov3D, cov3Ds_precomp), None, None,
-                grads[8] if split else None, None, None, None, None, None, None, None, g_A12, g_M)
+                grads[8] if split else None, None, None, None, None, None, None, None, g_A12, g_M, None)
 
 
 class _RasterizeLabel(torch.autograd.Function):
@@ -240,13 +246,14 @@ def backward_prologue_of(node):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, activation_flags=0, sh_rest=None, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                        object_rotation=None, color_only=False, object_motion=None):
+                        object_rotation=None, color_only=False, object_motion=None, opacity_entropy=None):
     """-> (color, radii, depth, alpha, visible); upstream's function returns the first four, `visible` (bool[P] = radii > 0) is an
     extension GaussianRasterizer keeps for render()."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, activation_flags, sh_rest, densify_stats, active_count, guard, optimizer,
                                      object_rotation, color_only, object_motion,
-                                     None if object_motion is None else object_motion[0], None if object_motion is None else object_motion[2])
+                                     None if object_motion is None else object_motion[0], None if object_motion is None else object_motion[2],
+                                     opacity_entropy)
 
 
 class GaussianRasterizer(nn.Module):
@@ -262,7 +269,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, raw_parameters=False, densify_stats=None, active_count=None, guard=None, optimizer=None,
-                object_rotation=None, color_only=False, object_motion=None):
+                object_rotation=None, color_only=False, object_motion=None, opacity_entropy=None):
         """Same call as upstream's.  raw_parameters=True (an extension): `scales`, `rotations` and `opacities` are the model's RAW
         parameters (log-scales, unnormalised quaternions, opacity logits); the activations run inside the preprocess kernel and
         the gradients come back w.r.t. the raw tensors (include/egs_raster.h, EGS_ACT_*).
@@ -284,6 +291,9 @@ class GaussianRasterizer(nn.Module):
         # sole consumer of those parameters in the backward pass (optim.FusedAdam.make_sink)
         # color_only (an extension): depth and alpha come back as None and the blend leaves their sums and planes out (a training step
         # whose loss reads the colour image only)
+        # opacity_entropy (an extension): a _C.EntropyTerm -- the static stages' entropy regulariser on the visible opacities as part of the loss
+        # this call's backward differentiates (include/egs_raster.h egs_backward_entropy_lossgrad): dL/dopacity comes back with the term's
+        # share, a fused opacity leaf steps on the whole gradient, and the term's value / n_vis words are written by that backward
         # After the call `self.visible` holds radii > 0 as a bool view the preprocess kernel wrote (no compare launch); it aliases
         # state saved for the backward and, under hipGraph replay, follows every replay -- clone it to keep or edit it.
         # The reference's own render() hands over ACTIVATED tensors (opacities = get_opacity, cov3D_precomp = get_covariance(...), shs =
@@ -319,5 +329,5 @@ class GaussianRasterizer(nn.Module):
         color, radii, depth, alpha, self.visible = rasterize_gaussians(
             means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings,
             _C.ACT_RAW_PARAMETERS if raw_parameters else 0, shs_rest, densify_stats, active_count, guard, optimizer, object_rotation, color_only,
-            object_motion)
+            object_motion, opacity_entropy)
         return color, radii, depth, alpha

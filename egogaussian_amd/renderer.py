@@ -54,7 +54,7 @@ def _motion_rows(pc, which_object):
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, rot_cov=False,
            accum_R=None, which_object=None, during_training=False, fused_densify_stats=False, guard=None, optimizer=None, color_only=False,
-           object_motion=None):
+           object_motion=None, opacity_entropy=None):
     """Extensions (defaults = the reference's behaviour):
     fused_densify_stats  the backward of this render also updates pc.xyz_gradient_accum, pc.denom and pc.max_radii2D in place
                          (the trainer then skips add_densification_stats / the max_radii2D update for this iteration);
@@ -71,6 +71,14 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
                          is not read) and the raw-parameter path stays on even while the pose is trained: M and A12 get gradients, which
                          autograd carries to obj_translation / obj_rotation_6d.  A model without get_raw_parameters() cannot be rendered
                          with rot_cov and a motion (RuntimeError): the covariance producers would turn by `accum_R`;
+    opacity_entropy      w, a float or a float32 scalar tensor on the device (read by the kernels when the backward runs): the loss this
+                         render feeds also holds  w * mean over the visible Gaussians of -o log(o + 1e-10) - (1 - o) log(1 - o + 1e-10),
+                         the static stages' entropy regulariser (/root/reference/trainers/train_static.py:97-102) -- WITHOUT writing it in
+                         torch: the rasterizer's backward adds its share to dL/dopacity itself, so with optimizer= the opacity stays a
+                         fused leaf, and without it `_opacity.grad` comes back with the term included.  Do not add the term to the loss
+                         as well.  The result's "opacity_entropy" is a float32[1] tensor holding the UNWEIGHTED value: filled when the
+                         backward runs (under torch.no_grad(): right away, by the stand-alone kernels).  Static stages only: not with
+                         object_motion.  losses.opacity_entropy is the torch expression;
     a model with an `active_count` attribute (int32[1] device tensor; capacity.CapacityGaussians) renders only its live rows.
     `visibility_filter` is radii > 0 as written by the preprocess kernel: a fresh tensor in eager calls; while a hipGraph is being
     captured it is a VIEW of the rasterizer's saved state that follows every replay (no launch) -- clone it to keep or edit it."""
@@ -145,8 +153,15 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     else:
         shs = pc.get_features
 
+    opac_in = pc.get_opacity if opacity is None else opacity
+    term = None
+    if opacity_entropy is not None:
+        from . import _C
+        if not xyz.is_cuda:
+            raise RuntimeError("render(opacity_entropy=...): HIP devices only (losses.opacity_entropy is the tensor expression)")
+        term = opacity_entropy if isinstance(opacity_entropy, _C.EntropyTerm) else _C.EntropyTerm(opacity_entropy, xyz.device)
     image, radii, depth, alpha = rasterizer(means3D=xyz, means2D=screenspace_points, shs=shs,
-                                            colors_precomp=colors_precomp, opacities=pc.get_opacity if opacity is None else opacity, scales=scales,
+                                            colors_precomp=colors_precomp, opacities=opac_in, scales=scales,
                                             rotations=rotations, cov3D_precomp=cov3D_precomp, **({"raw_parameters": True} if raw else {}),
                                             **({"densify_stats": (pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)} if fused_densify_stats else {}),
                                             **({"active_count": pc.active_count} if getattr(pc, "active_count", None) is not None else {}),
@@ -154,14 +169,21 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
                                             **({"optimizer": optimizer} if optimizer is not None else {}),
                                             **({"object_rotation": object_rotation} if object_rotation is not None else {}),
                                             **({"color_only": True} if color_only else {}),
-                                            **({"object_motion": motion_arg} if motion_arg is not None else {}))
+                                            **({"object_motion": motion_arg} if motion_arg is not None else {}),
+                                            **({"opacity_entropy": term} if term is not None else {}))
     visible = rasterizer.visible                           # radii > 0 from the preprocess kernel of THIS call (returned, not shared state)
     if visible is None:
         visible = radii > 0
     elif not torch.cuda.is_current_stream_capturing():
         visible = visible.clone()                          # eager: the caller owns it, as with the reference's `radii > 0`
-    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": visible, "radii": radii,
-            "depth": depth, "alpha": alpha}
+    res = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": visible, "radii": radii,
+           "depth": depth, "alpha": alpha}
+    if term is not None:
+        if image.grad_fn is None:                          # no backward will run: the value from the stand-alone kernels, now
+            from . import _C
+            _C.opacity_entropy_forward(opac_in.detach(), radii, term, logit=raw, active_count=getattr(pc, "active_count", None))
+        res["opacity_entropy"] = term.value
+    return res
 
 
 def get_pts_label_as_rgb(gaussians_label):

@@ -10,6 +10,10 @@ number of live Gaussians is a device word, so the captured step is NOT re-captur
 reference's behaviour -- new tensors per densification, one re-capture each).  The step voids frames that outgrow its instance
 capacity on the device and re-captures itself with more room (GraphedTrainStep(check_every=...)).
 
+`--entropy-iters K` appends the reference's entropy phase (trainers/train_static.py:97-102,139-141): K more iterations of the SAME
+captured step with the weight of the opacity-entropy term switched on (`step.entropy_weight = --entropy-weight`: a device scalar, no
+re-capture), then `prune_points(get_opacity < 0.5)` on the capacity model (in place: no re-capture either).
+
 It shows the order of calls a trainer needs; it is not part of the measured path.  `--log` appends a line per report interval
 (iteration, live Gaussians, it/s so far, held-out PSNR), which is how profiles/r2_train_synth_*.log were produced.
 """
@@ -54,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--knn-init", action="store_true",
                     help="initialise the student as GaussianModel.create_from_pcd does (/root/reference/scene/gaussian_model.py:301-318): isotropic scales "
                          "from simple_knn.distCUDA2 of the (perturbed) teacher positions, identity rotations, opacity 0.1")
+    ap.add_argument("--entropy-iters", type=int, default=0,
+                    help="after --iters, this many iterations with the opacity-entropy term on, then prune opacity < 0.5 (train_static.py:97-102,139-141)")
+    ap.add_argument("--entropy-weight", type=float, default=0.1, help="weight of the entropy term during that phase (the reference: 0.1)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     H, W = a.height, a.width
@@ -101,7 +108,7 @@ def main(argv=None):
 
     report(f"# {' '.join(sys.argv)}")
     report(f"start: {live()} Gaussians, held-out PSNR {quality():.2f} dB, {'plain model' if a.plain else f'capacity {pc.capacity} rows'}")
-    step = GraphedTrainStep(pc, pc.optimizer, bg, lambda_dssim=0.2, densify_stats=True, check_every=50)
+    step = GraphedTrainStep(pc, pc.optimizer, bg, lambda_dssim=0.2, densify_stats=True, check_every=50, entropy_reg=a.entropy_iters > 0)
     step.capture(cams[0], gts[0], warmup=2, capacity_margin=1.5, capacity_cams=cams[::max(1, a.frames // 6)])
     manual_recaptures, t_eval, next_report = 0, 0.0, a.report_every
     t0, it = time.perf_counter(), 2
@@ -134,12 +141,33 @@ def main(argv=None):
             t_eval += time.perf_counter() - te
             report(f"iter {it:6d}  live {live():8d}  {it / (time.perf_counter() - t0 - t_eval):8.1f} it/s so far  held-out PSNR {q:.3f} dB  "
                    f"re-captures {manual_recaptures + step.recaptures} (overflow {step.recaptures})  instance capacity {step.capacity}")
+    entropy_report = None
+    if a.entropy_iters > 0:
+        # the entropy phase: the same captured step, the term's weight switched on in its device scalar
+        graph0, recaptures0 = step.graph, manual_recaptures + step.recaptures
+        step.entropy_weight = a.entropy_weight
+        for j in range(a.entropy_iters):
+            step(cams[(it + j) % a.frames], gts[(it + j) % a.frames])
+        step.entropy_weight = 0.0
+        torch.cuda.synchronize()
+        h_end, n_before = float(step.entropy.item()), live()
+        with torch.no_grad():
+            mask = (pc.get_opacity < 0.5).squeeze(-1)                # (a capacity model: prune_points reads its live rows only)
+        ptr = pc._xyz.data_ptr()
+        densify.prune_points(pc, mask)
+        if a.plain or pc._xyz.data_ptr() != ptr:
+            step.recapture(warmup=1); manual_recaptures += 1
+        entropy_report = dict(iterations=a.entropy_iters, mean_entropy_end=h_end, pruned=n_before - live(),
+                              recaptures=manual_recaptures + step.recaptures - recaptures0, same_graph=step.graph is graph0)
+        report(f"entropy phase: {a.entropy_iters} iterations at weight {a.entropy_weight}, mean entropy of the visible opacities {h_end:.4f}; "
+               f"pruned opacity < 0.5: {n_before} -> {live()} Gaussians, {entropy_report['recaptures']} re-capture(s)")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0 - t_eval
     step.check()
     # (what the run was, for callers that assert on it: tests/test_gpu_densify.py runs the reference's full schedule through this function)
     pc.train_report = dict(gaussians_start=a.gaussians, gaussians_end=live(), psnr_end=quality(), its_per_s=a.iters / dt, recaptures=manual_recaptures + step.recaptures,
-                           recaptures_after_overflow=step.recaptures, overflow_events=step.skipped_frames_seen, iterations=it, instance_capacity=step.capacity)
+                           recaptures_after_overflow=step.recaptures, overflow_events=step.skipped_frames_seen, iterations=it, instance_capacity=step.capacity,
+                           entropy_phase=entropy_report)
     report(f"end: {live()} Gaussians, held-out PSNR {quality():.2f} dB, {a.iters / dt:.0f} it/s including densification, opacity resets and "
            f"{manual_recaptures + step.recaptures} re-capture(s) ({step.recaptures} after an instance-capacity overflow, {step.skipped_frames_seen} overflow events)")
     if a.out:

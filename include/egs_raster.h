@@ -341,10 +341,13 @@ int egs_backward(
  *   - coef: device float[12] scratch owned by the caller, written and read by this call only.
  *   - CALLER-CHECKED PRECONDITION (the library cannot see the caller's computation graph): the gradient this backward produces for a
  *     fused leaf must be the leaf's WHOLE gradient for this optimizer step -- this rasterizer call is the only consumer of the
- *     parameter in the loss.  A second path (an entropy term on the opacities, colours computed from the positions outside the
- *     library, a second render of the same model in the same iteration) would have its share applied with stale moments or lost.
- *     The Python host side enforces it where it can (optim.FusedAdam.make_sink leaves the positions out when colors_precomp requires
- *     a gradient; FusedAdam.step raises when a fused leaf arrives with a .grad from another path); a direct C caller owns the check. */
+ *     parameter in the loss.  A second path (colours computed from the positions outside the library, a second render of the same
+ *     model in the same iteration, a regulariser written in torch on a fused leaf) would have its share applied with stale moments
+ *     or lost.  ONE second path the library takes itself: the static stages' entropy term on the visible opacities, whose share joins
+ *     dL/dopacity inside the preprocess backward, ahead of the sigmoid chain and of the Adam step (egs_backward_entropy_lossgrad
+ *     below) -- ask for it there instead of adding it outside.
+ *     The Python host side enforces the rest where it can (optim.FusedAdam.make_sink leaves the positions out when colors_precomp
+ *     requires a gradient; FusedAdam.step raises when a fused leaf arrives with a .grad from another path); a direct C caller owns the check. */
 #define EGS_SINK_MEANS3D   0    /* [P,3] */
 #define EGS_SINK_OPACITY   1    /* [P,1] */
 #define EGS_SINK_SCALES    2    /* [P,3] */
@@ -616,6 +619,56 @@ int egs_backward_label(int P, int64_t R, int width, int height, const int32_t* r
                        float* dL_dlabel /*[P] out or NULL*/, const egs_adam_leaf* adam /*HOST or NULL*/, float beta1, float beta2, float eps,
                        float* coef /*device float[12] scratch; needed with adam*/, const int32_t* active_rows /*device int32[1] or NULL*/,
                        const uint32_t* skip_flag /*device uint32[1] or NULL*/, void* scratch, void* stream, int flags);
+
+/* ---- Opacity-entropy regularisation (additions to ABI 6; nothing above changes).  Between std_train_iter and std_train_iter +
+ *      entropy_reg_iter both static trainers add to the image loss
+ *          0.1 * mean over the visible Gaussians (radii > 0) of  -o log(o + 1e-10) - (1 - o) log(1 - o + 1e-10),   o = get_opacity
+ *      (/root/reference/trainers/train_static.py:97-102, trainers/train_static_bg.py:105-110) and prune get_opacity < 0.5 when the phase ends.
+ *      Per visible row, with o the float32 activated opacity (csrc/opacity_entropy.h, the one definition every route calls):
+ *          a = o + 1e-10f   b = (1.0f - o) + 1e-10f   h = -o logf(a) - (1 - o) logf(b)   dh/do = -logf(a) - o / a + logf(b) + (1 - o) / b
+ *          value = (sum of h over the visible rows) / n_vis          dL/do += weight * upstream / n_vis * dh/do
+ *      and, when the opacity arrives as a logit (EGS_ACT_LOGIT_OPACITY), the sigmoid chain o (1 - o) after it.  Rows with radii <= 0 and rows
+ *      at or beyond *active_count contribute nothing and receive nothing (exactly 0); o == 0, 0.5 and 1 are finite.  n_vis == 0: no gradient
+ *      anywhere, value = NaN (torch's mean() of an empty tensor).  The sum is a deterministic reduction: one float32 line per 256 rows (six
+ *      __shfl_xor levels, four waves through LDS), then one finish workgroup that adds the lines in index order in float64.  No float
+ *      atomics: the same inputs give the same bits.
+ *   egs_opacity_entropy_forward   `opacity` [P] as the caller's forward received it (activation_flags: 0 or EGS_ACT_LOGIT_OPACITY) -> ent->n_vis,
+ *                                 ent->value (may be NULL), and with `activated` [P] (may be NULL) the activated opacity of every live row as
+ *                                 the kernels form it (0 in the dead rows).  Two launches.  ent->weight / upstream are not read.
+ *   egs_opacity_entropy_backward  dL/dopacity [P] of weight * upstream * value w.r.t. what the forward received; reads ent->n_vis as the
+ *                                 forward left it.  One launch, no scratch.
+ *   egs_backward_entropy_lossgrad egs_backward_lossgrad with the term inside: the reduction (of the activated opacities the forward parked in
+ *                                 the geometry buffer -- the very bits the blend used -- and `radii`) is enqueued in front of the preprocess
+ *                                 backward, whose entropy instantiation adds the row's share to dL/dopacity before the sigmoid chain, the
+ *                                 dL_dopacity store and the Adam step of EGS_SINK_OPACITY: the opacity stays a fused leaf.  loss_grad may be
+ *                                 NULL: the three dL_dout_* arrays are then read as by egs_backward_adam (with loss_grad they must be NULL).
+ *                                 skip_flag set: no step is taken, as everywhere.  Not with EGS_ACT_OBJECT_MOTION and not on the colours-only
+ *                                 path (EGS_ERR_MODE): the term belongs to the static stages. */
+typedef struct egs_opacity_entropy {     /* HOST struct */
+    const float* weight;             /* device float[1]: the term's weight (0.1 in the reference); read on the device, so a captured step changes it without re-capture */
+    const float* upstream;           /* device float[1]: dL/d(loss), or NULL = 1 */
+    void*        scratch;            /* egs_opacity_entropy_scratch_bytes(P) */
+    uint32_t*    n_vis;              /* device uint32[1]: visible rows of the frame (out of the reduction, in of egs_opacity_entropy_backward) */
+    float*       value;              /* device float[1] out or NULL: the UNWEIGHTED mean entropy of the visible opacities */
+} egs_opacity_entropy;
+size_t egs_opacity_entropy_scratch_bytes(int P);
+int egs_opacity_entropy_forward(int P, const float* opacity /*[P]*/, int activation_flags /*0 or EGS_ACT_LOGIT_OPACITY*/, const int32_t* radii /*[P]*/,
+                                const int32_t* active_count /*device int32[1] or NULL*/, float* activated /*[P] out or NULL*/,
+                                const egs_opacity_entropy* ent /*HOST*/, void* stream);
+int egs_opacity_entropy_backward(int P, const float* opacity /*[P]*/, int activation_flags, const int32_t* radii /*[P]*/,
+                                 const int32_t* active_count /*device int32[1] or NULL*/, const egs_opacity_entropy* ent /*HOST*/,
+                                 float* dL_dopacity /*[P] out*/, void* stream);
+int egs_backward_entropy_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
+                          const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, int width, int height, float tan_fovx, float tan_fovy, const int32_t* radii,
+                          const void* geom_buffer, const void* binning_buffer, const void* image_buffer, const egs_loss_grad* loss_grad /*HOST or NULL*/,
+                          const egs_opacity_entropy* entropy /*HOST*/,
+                          const float* dL_dout_color /*NULL with loss_grad*/, const float* dL_dout_depth /*or NULL*/, const float* dL_dout_alpha /*or NULL*/,
+                          float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
+                          float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
+                          const uint32_t* skip_flag, const egs_adam_sink* sink /*HOST or NULL*/, int prologue_done, const egs_object_rotation* rot /*HOST or NULL*/,
+                          int grad_mask, void* scratch, void* stream, int debug);
 
 /* ---- f-4 (optimizer part): multi-tensor Adam step in one launch.  Same update as torch.optim.Adam(weight_decay=0,
  *      amsgrad=False), which the reference builds at /root/reference/scene/gaussian_model.py:198 and steps at

@@ -5,24 +5,35 @@ import numpy as np
 import torch
 
 from egogaussian_amd.scene_synth import make_scene, make_camera
+from tests.cameras import CAMERAS, IN_CLOUD, population, assert_population      # noqa: F401  (re-exported: the general cameras)
 
 
 def make_inputs(N, H, W, seed=0, sh_degree=0, mode="sh_cov", frame=3, scale_mul=1.0, bg=(0.1, 0.2, 0.3), dtype=torch.float32,
-                opacity_shift=0.0):
+                opacity_shift=0.0, camera=None):
     """Activated rasterizer inputs for S(N,H,W,seed).
+    camera: None -> frame `frame` of the orbit (scene_synth.make_camera), scale_modifier 1; a name of tests/cameras.py CAMERAS (or a
+            dict of a camera's fields) -> that camera's pose, intrinsics and scale_modifier, the scene's positions re-oriented and
+            shifted into its world (`frame` is not read).  In the *_cov modes the modifier goes into the covariance, as the renderer
+            puts it there: the rasterizer does not read scale_modifier when it is handed cov3D_precomp.
     mode: 'sh_cov'  -> shs + cov3D_precomp   (training call, /root/reference/gaussian_renderer/__init__.py:90-98)
           'col_sr'  -> colors_precomp + scales/rotations (label call, render_helper.py:61-63)
           'sh_sr'   -> shs + scales/rotations
           'col_cov' -> colors_precomp + cov3D_precomp"""
     sc = make_scene(N, H, W, seed, sh_degree=sh_degree)
-    cam = make_camera(frame, H, W)
+    mod = 1.0
+    if camera is None:
+        cam = make_camera(frame, H, W)
+    else:
+        from tests.cameras import build_camera, world_positions
+        cam, Q, shift, mod = build_camera(camera, H, W)
+        sc["xyz"] = world_positions(sc["xyz"], Q, shift)
     t = lambda a: torch.tensor(a, dtype=dtype)
     scales = torch.exp(t(sc["log_scale"])) * scale_mul
     quat = t(sc["quat"])
     d = dict(means3D=t(sc["xyz"]), opacities=torch.sigmoid(t(sc["opacity_logit"]) + opacity_shift),
              viewmatrix=cam.world_view_transform.to(dtype), projmatrix=cam.full_proj_transform.to(dtype),
              campos=cam.camera_center.to(dtype), bg=torch.tensor(bg, dtype=dtype), image_height=H, image_width=W,
-             tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2), sh_degree=sh_degree, scale_modifier=1.0)
+             tanfovx=math.tan(cam.FoVx / 2), tanfovy=math.tan(cam.FoVy / 2), sh_degree=sh_degree, scale_modifier=mod)
     if mode in ("sh_cov", "sh_sr"):
         d["shs"] = t(sc["features"])
     else:
@@ -30,7 +41,7 @@ def make_inputs(N, H, W, seed=0, sh_degree=0, mode="sh_cov", frame=3, scale_mul=
         d["colors_precomp"] = t(rng.uniform(0, 1, (N, 3)).astype(np.float32))
     if mode in ("sh_cov", "col_cov"):
         from egogaussian_amd.covariance import covariance_from_scaling_rotation
-        d["cov3D_precomp"] = covariance_from_scaling_rotation(scales, 1.0, quat).contiguous()
+        d["cov3D_precomp"] = covariance_from_scaling_rotation(scales, mod, quat).contiguous()
     else:
         d["scales"], d["rotations"] = scales, quat
     return d

@@ -3,7 +3,9 @@
 splat size, camera) draws -- lists bit-exact with tile culling off, an ordered sub-list with it on, images and gradients
 within the test tolerances (a handful of entries may sit on the other side of an alpha threshold: the two implementations
 round alpha differently in the last place).  Complements tests/test_gpu_parity.py (fixed cases); run it for as long as you like:
-    python tests/fuzz_parity.py [seconds] [seed]
+    python tests/fuzz_parity.py [seconds] [seed] [--cameras general]
+(--cameras general: pose, world offset, fov ratio, a camera inside the cloud and the scale modifier are drawn too, tests/cameras.py;
+without it the draws of a seed are what they always were)
 (lives under tests/ because it uses the oracle, which is test infrastructure; tests/test_gpu_sweep.py runs a fixed-seed slice
 of it -- 320 draws -- under pytest -m gpu)"""
 import os, sys, time
@@ -12,30 +14,26 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests.common import FarRowOverBar, NEAR_SHARE, gaussians_contributing_to, flip_pixels, check_grads_isolating_flips, check_images_isolating_flips, make_inputs, seeded_grads, rel_err, outlier_fraction, tile_culling, check_culled_lists   # noqa: E402
+from tests.cameras import fuzz_draw, fuzz_inputs                                                                     # noqa: E402
 from tests.test_gpu_parity import hip_forward, hip_backward, oracle_forward, TOL                                     # noqa: E402
 from egogaussian_amd import _C                                                                                       # noqa: E402
 
 
-def run_draws(seed=0, budget_s=None, n_draws=None, dev=None, verbose=False, keep_going=False):
-    """Random draws until `n_draws` are done or `budget_s` seconds have passed.  -> (cases run, worst max-relative gradient errors)."""
+def run_draws(seed=0, budget_s=None, n_draws=None, dev=None, verbose=False, keep_going=False, cameras=None):
+    """Random draws until `n_draws` are done or `budget_s` seconds have passed.  -> (cases run, worst max-relative gradient errors).
+    cameras="general": every draw also draws pose, world, fov ratio, in-cloud push and scale modifier (tests/cameras.py fuzz_draw)."""
     rng = np.random.default_rng(int(seed))
     dev = torch.device("cuda:0") if dev is None else dev
     t_end, n_cases, worst = (time.time() + budget_s) if budget_s else None, 0, {}
     while (n_draws is None or n_cases < n_draws) and (t_end is None or time.time() < t_end):
-        N = int(rng.choice([1, 2, 63, 64, 65, 300, 1023, 1025, 2500, 7000, 20000, 70000]))
-        H, W = int(rng.integers(1, 300)), int(rng.integers(1, 420))
-        mode = str(rng.choice(["sh_cov", "sh_sr", "col_sr", "col_cov"]))
-        deg = int(rng.integers(0, 4)) if mode.startswith("sh") else 0
-        active = int(rng.integers(0, deg + 1))
-        smul = float(rng.choice([0.5, 1.0, 2.0, 4.0, 8.0]))
-        frame = int(rng.integers(0, 300))
-        cull = bool(rng.integers(0, 2))
-        split = bool(rng.integers(0, 2)) and deg > 0                      # hand the coefficients over as (dc, rest)
+        c = fuzz_draw(rng, cameras)                                       # (cameras=None: the stream of draws the recorded seeds were run with)
+        N, H, W, mode, deg, active, smul, frame, cull, split = (c[k] for k in ("N", "H", "W", "mode", "deg", "active", "smul", "frame", "cull", "split"))
         tag = f"N={N} {W}x{H} {mode} M={(deg + 1) ** 2} active={active} scale x{smul} frame {frame} culling {'on' if cull else 'off'}{' split-SH' if split else ''}"
+        if c["camera"] is not None:
+            tag += " camera " + " ".join(f"{k}={v:.3g}" if isinstance(v, float) else f"{k}={v}" for k, v in c["camera"].items())
         if verbose:
             print(tag, flush=True)
-        d = make_inputs(N, H, W, int(rng.integers(0, 1000)), deg, mode, frame=frame, scale_mul=smul, opacity_shift=float(rng.choice([0.0, 2.0, -2.0])))
-        d["sh_degree"] = active
+        d = fuzz_inputs(c)
         try:
             strict = _one_draw(d, N, H, W, cull, split, active, tag, dev, worst, keep_going, n_cases)
         except AssertionError as err:
@@ -57,7 +55,7 @@ def _one_draw(d, N, H, W, cull, split, active, tag, dev, worst, keep_going, n_ca
                 g = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in d.items()}
                 e0 = torch.empty(0, device=dev)
                 dc, rest = g["shs"][:, :1].contiguous(), g["shs"][:, 1:].contiguous()
-                out = _C.rasterize_gaussians(g["bg"], g["means3D"], e0, g["opacities"], g.get("scales", e0), g.get("rotations", e0), 1.0,
+                out = _C.rasterize_gaussians(g["bg"], g["means3D"], e0, g["opacities"], g.get("scales", e0), g.get("rotations", e0), g["scale_modifier"],
                                              g.get("cov3D_precomp", e0), g["viewmatrix"], g["projmatrix"], g["tanfovx"], g["tanfovy"], H, W, dc, active,
                                              g["campos"], False, False, 0, rest)
             else:
@@ -86,7 +84,7 @@ def _one_draw(d, N, H, W, cull, split, active, tag, dev, worst, keep_going, n_ca
             grads = seeded_grads(H, W, 7)
             if split:
                 gc, gd, ga = [x.to(dev) for x in grads]
-                full = _C.rasterize_gaussians_backward(g["bg"], g["means3D"], radii, e0, g.get("scales", e0), g.get("rotations", e0), 1.0,
+                full = _C.rasterize_gaussians_backward(g["bg"], g["means3D"], radii, e0, g.get("scales", e0), g.get("rotations", e0), g["scale_modifier"],
                                                        g.get("cov3D_precomp", e0), g["viewmatrix"], g["projmatrix"], g["tanfovx"], g["tanfovy"], gc, gd, ga,
                                                        dc, active, g["campos"], geom, R, binning, img, alpha, False, 0, rest)
                 hb = list(full[:8]); hb[5] = torch.cat((full[5], full[8]), dim=1)
@@ -172,8 +170,14 @@ def check_draw_gradients(names, hb, gb, st, flip_px, d, grads, tag, worst, keep_
 
 
 if __name__ == "__main__":
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    n_cases, worst = run_draws(int(sys.argv[2]) if len(sys.argv) > 2 else 0, budget_s=budget, keep_going=True)
+    argv = list(sys.argv[1:])
+    cameras = None
+    if "--cameras" in argv:                                               # opt-in: --cameras general
+        i = argv.index("--cameras")
+        cameras = argv[i + 1]
+        del argv[i:i + 2]
+    budget = float(argv[0]) if len(argv) > 0 else 120.0
+    n_cases, worst = run_draws(int(argv[1]) if len(argv) > 1 else 0, budget_s=budget, keep_going=True, cameras=cameras)
     failed = worst.pop("_failed_draws", [])
     strict = worst.pop("_strict_draws", 0)
     arb = worst.pop("_arbitrated_by_f64_oracle", 0)

@@ -605,17 +605,33 @@ def test_object_rotation_inside_the_rasterizer_matches_the_covariance_path():
     (egs_object_rotation) against the same call through the fused covariance producer (cov3D_precomp): identical covariance arithmetic,
     so radii and images are equal bit for bit; parameter gradients equal up to the order of the backward's float atomics -- including
     row 0, which the reference's [N,1]-index quirk rotates and whose gradient it multiplies (covariance.py)."""
+    object_rotation_inside_the_rasterizer_matches_the_covariance_path()
+
+
+def object_rotation_inside_the_rasterizer_matches_the_covariance_path(camera=None):
+    """The body of the test above; camera: a name of tests/cameras.py CAMERAS -> the scene in that camera's world, seen by it, both
+    routes called with its scale modifier (the raw route applies it in the preprocess kernels, the other in the producer)."""
     import math
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import l1_ssim_loss
     N, H, W = 12000, 96, 160
     teacher = make_scene(N, H, W, 3); teacher["log_scale"] += math.log(2.0)
+    mod = 1.0
+    if camera is not None:
+        from tests.cameras import build_camera, world_positions
+        cam_general, Q, shift, mod = build_camera(camera, H, W, device=DEV)
+        teacher["xyz"] = world_positions(teacher["xyz"], Q, shift)
     student = perturb_student(teacher)
+    if camera is not None:
+        # row 0 has to be seen for the last assertion to mean anything: with the splats 1.7 x as large the oracle finds it occluded at
+        # the one camera and behind the near plane at the other, so it is put on the optical axis in front of the cloud
+        front = torch.tensor([0.0, 0.0, 1.5, 1.0], dtype=torch.float64) @ torch.linalg.inv(cam_general.world_view_transform.double().cpu())
+        student["xyz"][0] = front[:3].numpy().astype(student["xyz"].dtype)
     gen = torch.Generator().manual_seed(4)
     is_obj = (torch.rand(N, 1, generator=gen) < 0.3).float().to(DEV)
     is_obj[0, 0] = 0.0                                                   # row 0 is background: only the quirk moves it
-    cam, bg = make_camera(30, H, W, device=DEV), torch.zeros(3, device=DEV)
+    cam, bg = (make_camera(30, H, W, device=DEV) if camera is None else cam_general), torch.zeros(3, device=DEV)
     c, s_ = math.cos(0.7), math.sin(0.7)
     R = torch.tensor([[c, -s_, 0.0], [s_, c * 0.9, -0.3], [0.1, 0.3, 0.95]], device=DEV)     # (any 3x3: nothing requires a rotation)
     gt = torch.rand(3, H, W, generator=gen).to(DEV)
@@ -623,7 +639,7 @@ def test_object_rotation_inside_the_rasterizer_matches_the_covariance_path():
     for inside in (True, False):
         pc = SynthGaussians(student, device=DEV); pc._is_object = is_obj
         pc.rotate_in_rasterizer = inside
-        out = render(cam, pc, Pipe, bg, rot_cov=True, accum_R=R, which_object=1, during_training=False)
+        out = render(cam, pc, Pipe, bg, scaling_modifier=mod, rot_cov=True, accum_R=R, which_object=1, during_training=False)
         l1_ssim_loss(out["render"], gt, 0.2).backward()
         torch.cuda.synchronize()
         outs.append((out, pc))

@@ -23,15 +23,24 @@ def _groups(pc):
     return g
 
 
-def _scene(N=12000, H=96, W=160, seed=0, sh_degree=0):
+def _scene(N=12000, H=96, W=160, seed=0, sh_degree=0, camera=None):
+    """camera: a name of tests/cameras.py CAMERAS -> the scene in that camera's world and four views of it a few degrees of yaw apart
+    (the orbit's four frames otherwise); the ground truth is rendered with the camera's scale modifier."""
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     teacher = make_scene(N, H, W, seed, sh_degree=sh_degree); teacher["log_scale"] += math.log(2.0)
-    cams = [make_camera(k, H, W, device=DEV) for k in (0, 40, 80, 120)]
+    mod = 1.0
+    if camera is None:
+        cams = [make_camera(k, H, W, device=DEV) for k in (0, 40, 80, 120)]
+    else:
+        from tests.cameras import CAMERAS, build_camera, world_positions
+        views = [build_camera(camera, H, W, device=DEV, yaw=CAMERAS[camera]["yaw"] + 0.05 * k) for k in range(4)]
+        cams, (_, Q, shift, mod) = [v[0] for v in views], views[0]
+        teacher["xyz"] = world_positions(teacher["xyz"], Q, shift)
     bg = torch.zeros(3, device=DEV)
     with torch.no_grad():
         tpc = SynthGaussians(teacher, device=DEV, sh_degree=sh_degree, requires_grad=False)
-        gts = [render(c, tpc, Pipe, bg)["render"].clone() for c in cams]
+        gts = [render(c, tpc, Pipe, bg, scaling_modifier=mod)["render"].clone() for c in cams]
     return perturb_student(teacher), cams, gts, bg
 
 
@@ -43,12 +52,22 @@ def test_fused_step_is_the_standalone_step_bit_for_bit(sh_degree):
     (parameter, exp_avg, exp_avg_sq) taken before the backward steps with those gradients through the stand-alone kernel: parameters,
     both moments and state["step"] must be equal bit for bit.  The fifth iteration goes the other way round -- the optimizer that was
     fused so far takes a stand-alone step (its own step counters are re-seeded from state["step"]) -- and must again agree."""
+    fused_step_is_the_standalone_step_bit_for_bit(sh_degree)
+
+
+def fused_step_is_the_standalone_step_bit_for_bit(sh_degree, camera=None):
+    """The body of the test above; camera: as in _scene, every render then called with the camera's scale modifier.  -> the radii of
+    the last render (a caller states what the frame must have held)."""
     from egogaussian_amd.scene_synth import SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import l1_ssim_loss
     from egogaussian_amd.optim import FusedAdam
     import egogaussian_amd.optim as optim
-    student, cams, gts, bg = _scene(sh_degree=sh_degree)
+    student, cams, gts, bg = _scene(sh_degree=sh_degree, camera=camera)
+    mod = 1.0
+    if camera is not None:
+        from tests.cameras import CAMERAS
+        mod = CAMERAS[camera]["scale_modifier"]
     pa = SynthGaussians(student, device=DEV, sh_degree=sh_degree)
     oa = FusedAdam(_groups(pa), lr=0.0, eps=1e-15, capturable=True)
     pb = SynthGaussians(student, device=DEV, sh_degree=sh_degree)
@@ -68,7 +87,7 @@ def test_fused_step_is_the_standalone_step_bit_for_bit(sh_degree):
         for a in LEAVES:                                            # the twin starts every iteration from the same bits
             with torch.no_grad():
                 getattr(pb, a).copy_(getattr(pa, a))
-        out = render(cams[k], pa, Pipe, bg, optimizer=oa if fused else None)
+        out = render(cams[k], pa, Pipe, bg, scaling_modifier=mod, optimizer=oa if fused else None)
         loss = l1_ssim_loss(out["render"], gts[k], 0.2)
         # capture the gradients the backward writes: hook on the rasterizer's Function is not needed -- with keep_grads the
         # backward returns them to autograd as usual AND has already stepped the leaves
@@ -95,6 +114,7 @@ def test_fused_step_is_the_standalone_step_bit_for_bit(sh_degree):
             for key in ("exp_avg", "exp_avg_sq"):
                 assert torch.equal(oa.state[x][key], ob.state[y][key]), f"iteration {it}: {a} {key} differs"
             assert float(oa.state[x]["step"]) == float(ob.state[y]["step"]) == it + 1
+    return out["radii"]
 
 
 def test_fused_leaves_have_no_gradient_arrays_and_step_once():

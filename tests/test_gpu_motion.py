@@ -33,10 +33,13 @@ def _rot(axis, angle):
     return np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * (K @ K)
 
 
-def _pose(angle=0.4, t=(0.5, -0.3, 0.4), axis=(0.3, 1.0, 0.2)):
-    """4x4: a rotation about the scene centre (0, 0, 6) and a translation of ~0.7 (the scene spans ~6 x 4 x 8)."""
+def _pose(angle=0.4, t=(0.5, -0.3, 0.4), axis=(0.3, 1.0, 0.2), world=None):
+    """4x4: a rotation about the scene centre (0, 0, 6) and a translation of ~0.7 (the scene spans ~6 x 4 x 8).
+    world: the 4x4 that carries the scene into a general camera's world (tests/cameras.py): the same motion expressed there."""
     R, c = _rot(axis, angle), np.array([0.0, 0.0, 6.0])
     T = np.eye(4); T[:3, :3] = R; T[:3, 3] = c - R @ c + np.asarray(t)
+    if world is not None:
+        T = world @ T @ np.linalg.inv(world)
     return torch.tensor(T, dtype=torch.float32)
 
 
@@ -60,32 +63,50 @@ class Move(torch.nn.Module):
         return self.matrix(self.obj_rotation_6d) @ L
 
 
+def _modifier(camera):
+    """The scaling modifier every render of a general camera's runs is called with (1 on the orbit)."""
+    from tests.cameras import CAMERAS
+    return 1.0 if camera is None else CAMERAS[camera]["scale_modifier"]
+
+
+def _scene(sh_degree=0, camera=None):
+    return _scene_cached(sh_degree, camera)                              # (one cache entry however the call is spelt)
+
+
 @functools.lru_cache(maxsize=None)
-def _scene(sh_degree=0):
+def _scene_cached(sh_degree, camera):
+    """camera: None -> frame 30 of the orbit; a name of tests/cameras.py CAMERAS -> the scene carried into that camera's world, seen
+    by it, rendered with its scale modifier, the pose expressed in that world."""
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd import motion
     teacher = make_scene(N, H, W, 3, sh_degree=sh_degree); teacher["log_scale"] += math.log(2.0)
+    world = None
+    if camera is not None:
+        from tests.cameras import build_camera, world_positions
+        cam_general, Q, shift, _ = build_camera(camera, H, W, device=DEV)
+        teacher["xyz"] = world_positions(teacher["xyz"], Q, shift)
+        world = np.eye(4); world[:3, :3] = Q; world[:3, 3] = shift
     student = perturb_student(teacher)
     gen = torch.Generator().manual_seed(4)
     is_obj = (torch.rand(N, 1, generator=gen) < 0.3).float().to(DEV)
     is_obj[0, 0] = 0.0                                                   # row 0 is background: only the covariance quirk touches it
-    cam, bg = make_camera(30, H, W, device=DEV), torch.zeros(3, device=DEV)
-    T = _pose().to(DEV)
+    cam, bg = (make_camera(30, H, W, device=DEV) if camera is None else cam_general), torch.zeros(3, device=DEV)
+    T = _pose(world=world).to(DEV)
     # the ground truth: the teacher with its object a little further along -- the loss then pulls the pose one way (no cancellation)
-    T_gt = _pose(0.45, (0.62, -0.3, 0.4)).to(DEV)
+    T_gt = _pose(0.45, (0.62, -0.3, 0.4), world=world).to(DEV)
     with torch.no_grad():
         tpc = SynthGaussians(teacher, device=DEV, sh_degree=sh_degree, requires_grad=False)
         tpc._xyz = motion.move_points(tpc._xyz, T_gt[:3], is_obj == 1)
-        gt = render(cam, tpc, Pipe, bg)["render"].clone()
+        gt = render(cam, tpc, Pipe, bg, scaling_modifier=_modifier(camera))["render"].clone()
     return student, is_obj, cam, bg, T, gt
 
 
-def _model(variant=0):
+def _model(variant=0, camera=None):
     """`variant`: a key of VARIANTS, or a degree (stored = active, the two stored arrays)."""
     from egogaussian_amd.scene_synth import SynthGaussians
     sh_degree, active, cat = VARIANTS.get(variant, (variant, variant, False))
-    student, is_obj = _scene(sh_degree)[:2]
+    student, is_obj = _scene(sh_degree, camera)[:2]
     pc = SynthGaussians(student, device=DEV, sh_degree=sh_degree)
     pc._is_object = is_obj
     pc.active_sh_degree = active
@@ -158,18 +179,18 @@ def test_pose_reduction_on_exact_inputs(n):
 
 
 # ---- the three paths of 2, 3, 5 ----------------------------------------------------------------------------------------------------
-def _inside(variant, T, R, which_object=1, grad_A=True, grad_M=False, backward=True):
+def _inside(variant, T, R, which_object=1, grad_A=True, grad_M=False, backward=True, camera=None):
     from egogaussian_amd.scene_synth import Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import l1_ssim_loss
     from egogaussian_amd.motion import ComposedMotion
-    _, _, cam, bg, _, gt = _scene(_degree(variant))
-    pc = _model(variant)
+    _, _, cam, bg, _, gt = _scene(_degree(variant), camera)
+    pc = _model(variant, camera)
     A12 = T[:3].clone().requires_grad_(grad_A)
     M = R.clone().requires_grad_(grad_M)
     xyz_ptr = pc._xyz.data_ptr()
     with torch.enable_grad() if backward else torch.no_grad():
-        out = render(cam, pc, Pipe, bg, rot_cov=True, which_object=which_object, object_motion=ComposedMotion(A12, M))
+        out = render(cam, pc, Pipe, bg, scaling_modifier=_modifier(camera), rot_cov=True, which_object=which_object, object_motion=ComposedMotion(A12, M))
         if backward:
             l1_ssim_loss(out["render"], gt, 0.2).backward()
     torch.cuda.synchronize()
@@ -177,14 +198,14 @@ def _inside(variant, T, R, which_object=1, grad_A=True, grad_M=False, backward=T
     return out, pc, A12, M
 
 
-def _comparison(variant, T, R, which_object=1, cov_path=False, backward=True):
+def _comparison(variant, T, R, which_object=1, cov_path=False, backward=True, camera=None):
     """What the reference does: the model's positions ARE the placed ones (here through egs_object_move_points, kept in the autograd graph so
     that the stand-alone backward turns g = xyz'.grad into the canonical gradient and the pose sums), same rotation, no motion."""
     from egogaussian_amd.scene_synth import Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd import fused, motion
-    _, is_obj, cam, bg, _, gt = _scene(_degree(variant))
-    pc = _model(variant)
+    _, is_obj, cam, bg, _, gt = _scene(_degree(variant), camera)
+    pc = _model(variant, camera)
     leaf = pc._xyz
     A12 = T[:3].clone().requires_grad_(True)
     M = R.clone().requires_grad_(cov_path)              # (a rotation that requires a gradient takes the covariance producer: egs_cov3d_backward's dL_dM9)
@@ -202,7 +223,7 @@ def _comparison(variant, T, R, which_object=1, cov_path=False, backward=True):
         if backward:
             placed.retain_grad()
         pc._xyz = placed
-        out = render(cam, pc, Pipe, bg, rot_cov=True, accum_R=M, which_object=which_object, during_training=False)
+        out = render(cam, pc, Pipe, bg, scaling_modifier=_modifier(camera), rot_cov=True, accum_R=M, which_object=which_object, during_training=False)
         if backward:
             fused.l1_ssim_loss(out["render"], gt, 0.2).backward()
     torch.cuda.synchronize()
@@ -210,12 +231,16 @@ def _comparison(variant, T, R, which_object=1, cov_path=False, backward=True):
     return out, pc, A12, M, placed, keep.get("cov")
 
 
+def _runs(variant, camera=None):
+    return _runs_cached(variant, camera)
+
+
 @functools.lru_cache(maxsize=None)
-def _runs(variant):
+def _runs_cached(variant, camera):
     """(the inside path, KRUNS runs of the comparison path) of one colour variant."""
-    T = _scene(_degree(variant))[4]
+    T = _scene(_degree(variant), camera)[4]
     R = T[:3, :3].contiguous()
-    return _inside(variant, T, R), tuple(_comparison(variant, T, R) for _ in range(KRUNS))
+    return _inside(variant, T, R, camera=camera), tuple(_comparison(variant, T, R, camera=camera) for _ in range(KRUNS))
 
 
 def _pose_terms(g, p, moved):
@@ -263,7 +288,7 @@ def test_turned_covariances_need_the_raw_parameter_route():
 
 
 # ---- 3. position gradients, 5. pose gradient ---------------------------------------------------------------------------------------
-def _check_position_gradient(variant, xyz_grad, label):
+def _check_position_gradient(variant, xyz_grad, label, camera=None):
     """`xyz_grad` (a render of `variant`'s model with the pose inside) against A^T g in float64, g = xyz'.grad of the comparison path's run 1.
     Per row and component:  |err| <= 4 eps32 (|A^T||g|)  [moved rows; 0 for the others]  +  4 x the row's OWN run-to-run term.
 
@@ -280,8 +305,8 @@ def _check_position_gradient(variant, xyz_grad, label):
     Both are pushed through |A^T| for the moved rows, as the noise of g is.  A share of the gradient that is missing on faint rows is an
     error of the order of |g_i| itself, seven decimal orders above this."""
     from egogaussian_amd import motion
-    runs = _runs(variant)[1]
-    is_obj, T = _scene(_degree(variant))[1], _scene(_degree(variant))[4]
+    runs = _runs(variant, camera)[1]
+    is_obj, T = _scene(_degree(variant), camera)[1], _scene(_degree(variant), camera)[4]
     m = motion.exact_mask(is_obj, 1).cpu().numpy()[:, None]
     A = _f64(T[:3, :3])
     g = np.stack([_f64(r[4].grad) for r in runs])
@@ -311,16 +336,21 @@ def test_position_and_pose_gradients(variant):
     two runs of the comparison path, whose distance is the atomics-order noise of the blend; with more than one coefficient the
     spherical-harmonics launch finishes the gradient, one line per 64 rows -- a six-deep tree, inside the same constant).  Every other
     parameter gradient: 2e-5 max + 1e-9."""
+    position_and_pose_gradients(variant)
+
+
+def position_and_pose_gradients(variant, camera=None):
+    """The body of the test above, on the orbit or at a general camera (tests/test_gpu_cameras.py: scale modifier other than 1)."""
     from egogaussian_amd import motion
-    (oa, pa, Aa, _), ((o1, p1, A1, _, x1, _), (o2, p2, A2, _, x2, _), *_) = _runs(variant)
-    is_obj = _scene(_degree(variant))[1]
+    (oa, pa, Aa, _), ((o1, p1, A1, _, x1, _), (o2, p2, A2, _, x2, _), *_) = _runs(variant, camera)
+    is_obj = _scene(_degree(variant), camera)[1]
     moved = motion.exact_mask(is_obj, 1)
     g1 = x1.grad
     # guard against a pose gradient that is a cancellation
     sums, abss = g1[moved].sum(0).abs().max(), g1[moved].abs().sum(0).max()
     print(f"{variant}: |sum g|inf {float(sums):.3e}  sum|g|inf {float(abss):.3e}  ratio {float(sums / abss):.3f}")
     assert float(sums) >= 0.05 * float(abss)
-    _check_position_gradient(variant, pa._xyz.grad, "inside")
+    _check_position_gradient(variant, pa._xyz.grad, "inside", camera)
     assert float(pa._xyz.grad[moved].abs().max()) > 0 and torch.equal(p1._xyz.grad[~moved], g1[~moved])
     for name in LEAVES + (("_features_rest",) if _degree(variant) else ()):
         ga, gb = getattr(pa, name).grad, getattr(p1, name).grad

@@ -74,10 +74,10 @@ def float64_oracle(d, grads, nthreads=8):
     return st64, o64.backward(st64, *[x.double() for x in grads])
 
 
-def check_rows(d, grads, names, hb, st, gb, near, what):
+def check_rows(d, grads, names, hb, st, gb, near, what, record=None):
     """Every gradient row of the HIP backward against its own magnitude (float64 oracle; yardstick: the float32 oracle `st`, `gb`)."""
     st64, g64 = float64_oracle(d, grads)
-    return check_grad_rows_vs_float64(names, hb, st, gb, st64, g64, near, what=what)
+    return check_grad_rows_vs_float64(names, hb, st, gb, st64, g64, near, what=what, record=record)
 
 
 CASES = [
@@ -104,9 +104,16 @@ def _reference_lists():
 @pytest.mark.parametrize("cull", [False, True], ids=["reference-lists", "tile-culling"])
 @pytest.mark.parametrize("N,H,W,seed,deg,mode,smul", CASES)
 def test_forward_and_backward_parity(N, H, W, seed, deg, mode, smul, cull):
+    check_forward_and_backward_parity(make_inputs(N, H, W, seed, deg, mode, scale_mul=smul), cull, seed + 10, mode)
+
+
+def check_forward_and_backward_parity(d, cull, grad_seed, mode, record=None):
+    """One frame (a make_inputs dictionary) through the HIP path and the oracle: integer stages bit for bit, images and gradients under
+    the bars of this file.  record: a dict that receives the figures (flipped pixels, image distances, the row figures).
+    -> (oracle state, oracle gradients, HIP forward outputs, HIP gradients)."""
     from egogaussian_amd import _C
     dev = _dev()
-    d = make_inputs(N, H, W, seed, deg, mode, scale_mul=smul)
+    N, H, W, deg = int(d["means3D"].shape[0]), d["image_height"], d["image_width"], d["sh_degree"]
     o, st = oracle_forward(d)
     with tile_culling(cull):
         g, out = hip_forward(d, dev, debug=True)
@@ -167,12 +174,13 @@ def test_forward_and_backward_parity(N, H, W, seed, deg, mode, smul, cull):
     # threshold flips (tests/common.py): found with a threshold far below the bar and PROVEN (a threshold-adjacent pair in the float64 chain
     # of the pixel, else flip_pixels fails); every other pixel of every plane within 1e-4 of the plane's maximum
     flip_px = flip_pixels(color.cpu().numpy(), iv["final_T"].cpu().numpy(), st, None if cull else nc_hip)
-    print("   images: " + check_images_isolating_flips((("color", color.cpu().numpy(), st["color"]), ("depth", depth.cpu().numpy(), st["depth"]),
-                                                         ("alpha", alpha.cpu().numpy(), st["alpha"]), ("final_T", iv["final_T"].cpu().numpy(), st["final_T"])),
-                                                        st, flip_px, TOL, what=f"[{N}@{W}x{H} {mode}]") + f"; flipped pixels {int(flip_px.sum())}")
+    img_rep = check_images_isolating_flips((("color", color.cpu().numpy(), st["color"]), ("depth", depth.cpu().numpy(), st["depth"]),
+                                            ("alpha", alpha.cpu().numpy(), st["alpha"]), ("final_T", iv["final_T"].cpu().numpy(), st["final_T"])),
+                                           st, flip_px, TOL, what=f"[{N}@{W}x{H} {mode}]")
+    print("   images: " + img_rep + f"; flipped pixels {int(flip_px.sum())}")
 
     # ---- gradients -------------------------------------------------------------------------------------
-    grads = seeded_grads(H, W, seed + 10)
+    grads = seeded_grads(H, W, grad_seed)
     hb = hip_backward(g, out, grads, dev, debug=True)
     torch.cuda.synchronize()
     gb = o.backward(st, *grads)
@@ -182,7 +190,11 @@ def test_forward_and_backward_parity(N, H, W, seed, deg, mode, smul, cull):
     rep, _, _ = check_grads_isolating_flips(names, hb, gb, st, flip_px, TOL, what=f"[{N}@{W}x{H} {mode}]", near_out=near)
     print("   grads: " + rep)
     # ... and every row to its own magnitude
-    print("   " + check_rows(d, grads, names, hb, st, gb, near[0], f"[{N}@{W}x{H} {mode}]"))
+    rows = {}
+    print("   " + check_rows(d, grads, names, hb, st, gb, near[0], f"[{N}@{W}x{H} {mode}]", record=rows))
+    if record is not None:
+        record.update(R=R, flips=int(flip_px.sum()), images=img_rep, set_aside=int(near[0].size), rows=rows)
+    return st, gb, out, hb
 
 
 @pytest.mark.parametrize("cull", [False, True], ids=["reference-lists", "tile-culling"])
@@ -228,10 +240,15 @@ def test_tile_culling_changes_no_output_bit(N, H, W, seed, mode, smul):
     """Dropping the instances whose tile the splat cannot reach (the default) must leave colour, depth, alpha, final
     transmittance and radii bit-identical to the run that keeps the reference's full rectangles, and the gradients equal
     up to the order of the floating-point accumulation; the lists must shrink, stay sorted, and keep `num_rendered`."""
+    tile_culling_changes_no_output_bit(make_inputs(N, H, W, seed, 0, mode, scale_mul=smul), seed + 3)
+
+
+def tile_culling_changes_no_output_bit(d, grad_seed):
+    """The body of the test above for one frame (a make_inputs dictionary)."""
     from egogaussian_amd import _C
     dev = _dev()
-    d = make_inputs(N, H, W, seed, 0, mode, scale_mul=smul)
-    grads = seeded_grads(H, W, seed + 3)
+    N, H, W = int(d["means3D"].shape[0]), d["image_height"], d["image_width"]
+    grads = seeded_grads(H, W, grad_seed)
     res = {}
     for cull in (False, True):
         with tile_culling(cull):
@@ -267,10 +284,14 @@ def test_fused_count_pass_changes_nothing(N, H, W, seed, mode, smul, cull):
     array the chain leaves -- radii, records, rectangles, per-block counts, the scanned table's tile starts, ranges, the sorted lists, the
     images -- must equal, bit for bit, what the separate k_preprocess + k_bin_count launches produce; twice in a row (the second frame
     finds the chunk sums the first one's chain cleared), and after a frame of ANOTHER size on the same stream in between."""
+    fused_count_pass_changes_nothing(make_inputs(N, H, W, seed, 0, mode, scale_mul=smul), make_inputs(900, 48, 80, seed + 1, 0, "rgb_sr"), cull)
+
+
+def fused_count_pass_changes_nothing(d, other, cull):
+    """The body of the test above for one frame `d` and a frame of another size `other` (make_inputs dictionaries)."""
     from egogaussian_amd import _C
     dev = _dev()
-    d = make_inputs(N, H, W, seed, 0, mode, scale_mul=smul)
-    other = make_inputs(900, 48, 80, seed + 1, 0, "rgb_sr")
+    N, H, W = int(d["means3D"].shape[0]), d["image_height"], d["image_width"]
     res = {}
     with tile_culling(cull):
         hip_forward(d, dev)                                          # establishes the capacity: the fused path needs capacity > 0
@@ -300,9 +321,16 @@ def test_sort_inside_the_forward_blend_changes_nothing(N, H, W, seed, mode, smul
     """The forward blend's workgroups sort their tile's bucket themselves (render_fwd.hip SORT; no k_tile_sort launch): ranges, lists and every
     output plane must equal, bit for bit, what the separate sort launch produces -- including tiles beyond the register path's 1 792 entries
     (the last case: 9 000 splats x 8 on 16 tiles) and the chain that clears the fused count pass's chunk sums."""
+    res = sort_inside_the_forward_blend_changes_nothing(make_inputs(N, H, W, seed, 0, mode, scale_mul=smul), cull)
+    if smul == 8.0:
+        assert res["longest"] > 1792, "this case is meant to take the slab path"
+
+
+def sort_inside_the_forward_blend_changes_nothing(d, cull):
+    """The body of the test above for one frame (a make_inputs dictionary).  -> the figures of the run with the separate sort launch."""
     from egogaussian_amd import _C
     dev = _dev()
-    d = make_inputs(N, H, W, seed, 0, mode, scale_mul=smul)
+    N, H, W = int(d["means3D"].shape[0]), d["image_height"], d["image_width"]
     res = {}
     with tile_culling(cull):
         hip_forward(d, dev)
@@ -320,8 +348,7 @@ def test_sort_inside_the_forward_blend_changes_nothing(N, H, W, seed, mode, smul
             assert cur["R"] == res["R"] and np.array_equal(cur["rng"], res["rng"]) and np.array_equal(cur["pl"], res["pl"]), "sort inside the blend changed the lists"
             for x, y in zip(cur["planes"], res["planes"]):
                 assert torch.equal(x, y), "sort inside the blend changed an output"
-    if smul == 8.0:
-        assert res["longest"] > 1792, "this case is meant to take the slab path"
+    return res
 
 
 def _init_placement(t, W, H, dev):
@@ -868,10 +895,14 @@ def test_raw_parameter_mode_matches_activated_inputs(colour_mode):
     """EGS_ACT_*: log-scales, unnormalised quaternions and opacity logits activated inside the preprocess kernel must give
     the images of the call with torch-activated inputs, and gradients that are those of the activated call chained through
     exp / normalize / sigmoid by autograd."""
+    raw_parameter_mode_matches_activated_inputs(make_inputs(5000, 96, 128, 13, 0, "sh_sr" if colour_mode == "sh" else "col_sr", scale_mul=2.5), colour_mode)
+
+
+def raw_parameter_mode_matches_activated_inputs(d, colour_mode):
+    """The body of the test above for one frame (a make_inputs dictionary in a *_sr mode; its scale_modifier is the call's)."""
     from egogaussian_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
     dev = _dev()
-    N, H, W = 5000, 96, 128
-    d = make_inputs(N, H, W, 13, 0, "sh_sr" if colour_mode == "sh" else "col_sr", scale_mul=2.5)
+    N, H, W = int(d["means3D"].shape[0]), d["image_height"], d["image_width"]
     g = _to(d, dev)
     gen = torch.Generator().manual_seed(0)
     raw_s = torch.log(g["scales"]).detach()

@@ -531,3 +531,50 @@ def opacity_entropy(opacity, radii, weight=1.0, logit=False, active_count=None):
     Three HIP launches in all instead of the expression's dozen each way; deterministic (no float atomics).  No visible Gaussian: NaN and a
     zero gradient.  For a trainer that does not fuse its optimizer; one that does asks render(opacity_entropy=) for the term instead."""
     return _OpacityEntropy.apply(opacity, radii, weight, logit, active_count)
+
+
+EVAL_ROW_WORDS = 4      # include/egs_raster.h egs_eval_row as int64 words: sse, ssim_sum (float64 bits), clipped, instances
+
+
+def eval_rows(capacity, device):
+    """(rows int64[capacity, 4] zeroed, cursor int32[1] = 0) for eval_metrics: the caller-owned result array and the device-side frame index."""
+    return torch.zeros((int(capacity), EVAL_ROW_WORDS), dtype=torch.int64, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def eval_metrics(image, gt, keep=None, rows=None, cursor=None, overflow=None, out8=False):
+    """The evaluation figures of one frame by the HIP kernel (include/egs_raster.h egs_eval_metrics; losses.eval_metrics is the torch statement
+    of the same definition): the squared error of the 8-bit images over the kept pixels and the SSIM sum of the masked 8-bit images.
+    image, gt: [C,H,W], C = 1 or 3; keep: [H,W] (1 - hand mask; binary by contract, thresholded at 0.5) or None.
+    rows, cursor: eval_rows(capacity, device) -- the kernel writes row cursor[0] and advances the cursor on the device, so a sweep (or a
+    replayed graph) fills one array and the host reads it ONCE; a full array is left untouched while the cursor still counts.  None: a fresh
+    one-row array.  overflow: a _C.StepGuard's `overflow` words of the forward that rendered `image`; they travel in the row.
+    out8: also the quantised images, uint8[C,H,W] each, unmasked -- what goes into a PNG.
+    Does not synchronise.  -> dict(rows, cursor, q_image, q_gt) of device tensors (the last two None without out8); evaluate.decode_rows reads rows.
+    HIP tensors only."""
+    L = _lib.load()
+    img, g = _need_hip(image.detach(), "image"), _need_hip(gt.detach(), "gt")
+    if img.dim() != 3 or img.shape != g.shape or img.shape[0] not in (1, 3):
+        raise RuntimeError("eval_metrics: image and gt are [C,H,W] tensors of one shape, C = 1 or 3")
+    Cc, H, W = img.shape
+    dev = img.device
+    k = None
+    if keep is not None:
+        k = _need_hip(keep.detach(), "keep")
+        if k.numel() != H * W:
+            raise RuntimeError("eval_metrics: keep holds one value per pixel ([H,W])")
+    if (rows is None) != (cursor is None):
+        raise RuntimeError("eval_metrics: rows and cursor go together (fused.eval_rows)")
+    if rows is None:
+        rows, cursor = eval_rows(1, dev)
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 2 and rows.shape[1] == EVAL_ROW_WORDS and rows.is_contiguous()
+            and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1):
+        raise RuntimeError("eval_metrics: rows is a contiguous int64[capacity, 4] tensor and cursor an int32[1] tensor on the image's device")
+    if overflow is not None and not (overflow.is_cuda and overflow.dtype == torch.int32 and overflow.numel() == 2 and overflow.is_contiguous()):
+        raise RuntimeError("eval_metrics: overflow is a StepGuard's int32[2] device tensor")
+    partial = torch.empty(max(int(L.egs_eval_metrics_partial_bytes(Cc, H, W)), 8), dtype=torch.uint8, device=dev)
+    q_img = torch.empty((Cc, H, W), dtype=torch.uint8, device=dev) if out8 else None
+    q_gt = torch.empty((Cc, H, W), dtype=torch.uint8, device=dev) if out8 else None
+    with _hip.device_ctx(dev):
+        _lib.check(L.egs_eval_metrics(Cc, H, W, _p(img), _p(g), _p(k), _p(overflow), _p(partial), _p(q_img), _p(q_gt), _p(rows), int(rows.shape[0]),
+                                      _p(cursor), _stream(dev)))
+    return dict(rows=rows, cursor=cursor, q_image=q_img, q_gt=q_gt)

@@ -123,6 +123,8 @@ SIGNATURES = {
     "egs_l1_ssim_forward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
     "egs_l1_ssim_backward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egs_l1_ssim_pair_forward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_eval_metrics_partial_bytes": (C.c_size_t, [i32, i32, i32]),
+    "egs_eval_metrics": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
 
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),

@@ -87,3 +87,35 @@ def opacity_entropy(opacity, visibility):
     an empty tensor.  The oracle of the HIP kernels behind fused.opacity_entropy and render(opacity_entropy=), on any device and in any float type."""
     vis = opacity[visibility]
     return (-vis * torch.log(vis + 1e-10) - (1 - vis) * torch.log(1 - vis + 1e-10)).mean()
+
+
+def quantize8(x):
+    """The 8-bit image a PNG of `x` holds: uint8(clamp(x * 255 + 0.5, 0, 255)), evaluated in float32 with truncation -- the conversion of
+    torchvision.utils.save_image, which the reference's eval_and_metric writes its renders and ground truths with
+    (the reference, trainers/eval_metric.py:41-175).  float32 whatever x's type is: the rule is defined there (on the 765 values around
+    the boundaries (k + 0.5) / 255 it differs from exact round-half-up in 128).  Idempotent on k / 255; NaN -> 0.  Any device."""
+    v = torch.nan_to_num(x.detach().to(torch.float32), nan=0.0, posinf=float("inf"), neginf=float("-inf"))
+    return v.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8)
+
+
+def eval_metrics(image, gt, keep=None):
+    """PSNR and SSIM of one frame as the reference's eval_and_metric reports them: on the 8-bit images, with the hand removed.
+        u = kept ? quantize8(image) / 255 : 0,  v = kept ? quantize8(gt) / 255 : 0,  kept = keep >= 0.5  (keep = 1 - hand mask, [H,W]; None: all)
+        sse = sum over kept pixels and channels of (quantize8(image) - quantize8(gt))^2      (an exact integer)
+        psnr = 10 log10(255^2 * 3HW / sse): the mean counts gated pixels too, as the reference's does; inf when sse == 0
+        ssim = mean over all 3HW entries of ssim()'s map of (u, v)
+    The reference asserts its masks binary; a non-binary `keep` is outside the contract (it is thresholded here, multiplied there).
+    image, gt: [C,H,W] in any float type on any device; the SSIM map is evaluated in that type.  -> dict(sse: int64 tensor, psnr, ssim: tensors of
+    image's type).  The oracle of the HIP kernel behind fused.eval_metrics."""
+    assert image.dim() == 3 and image.shape == gt.shape
+    dt = image.dtype if image.dtype.is_floating_point else torch.float32
+    qx, qy = quantize8(image).to(torch.int64), quantize8(gt).to(torch.int64)
+    if keep is not None:
+        kept = (keep.reshape(image.shape[-2], image.shape[-1]) >= 0.5).to(torch.int64)[None]
+        qx, qy = qx * kept, qy * kept
+    sse = ((qx - qy) ** 2).sum()
+    n = image.numel()
+    mse = sse.to(torch.float64) / (255.0 ** 2 * n)
+    psnr_v = torch.where(sse == 0, torch.full_like(mse, float("inf")), -10.0 * torch.log10(mse.clamp_min(1e-300)))
+    u, v = qx.to(dt) / 255, qy.to(dt) / 255
+    return dict(sse=sse, psnr=psnr_v.to(dt), ssim=ssim(u, v))

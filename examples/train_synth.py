@@ -28,7 +28,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from egogaussian_amd import densify, ply                                          # noqa: E402
 from egogaussian_amd.capacity import CapacityGaussians                            # noqa: E402
-from egogaussian_amd.graph import GraphedTrainStep                                # noqa: E402
+from egogaussian_amd.evaluate import EvalPass                                     # noqa: E402
+from egogaussian_amd.graph import GraphedTrainStep, pack_frame                    # noqa: E402
 from egogaussian_amd.losses import psnr                                           # noqa: E402
 from egogaussian_amd.renderer import render                                       # noqa: E402
 from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe, N_FRAMES   # noqa: E402
@@ -170,6 +171,12 @@ def main(argv=None):
                            entropy_phase=entropy_report)
     report(f"end: {live()} Gaussians, held-out PSNR {quality():.2f} dB, {a.iters / dt:.0f} it/s including densification, opacity resets and "
            f"{manual_recaptures + step.recaptures} re-capture(s) ({step.recaptures} after an instance-capacity overflow, {step.skipped_frames_seen} overflow events)")
+    # the evaluation pass over the training cameras: 8-bit PSNR / SSIM as the reference's eval_and_metric reports them (no hand here: every
+    # pixel kept), one captured graph replayed per frame, one host read at the end
+    ev = EvalPass(pc, bg).run([pack_frame(c, g) for c, g in zip(cams, gts)], cams[0])
+    pc.train_report["eval"] = dict(mean_psnr=ev["mean_psnr"], mean_ssim=ev["mean_ssim"], rerendered=len(ev["rerendered"]))
+    report(f"evaluation pass over {len(cams)} cameras: PSNR {ev['mean_psnr']:.3f} dB, SSIM {ev['mean_ssim']:.5f} (8-bit images; "
+           f"{len(ev['rerendered'])} frame(s) rendered again)")
     if a.out:
         ply.save_ply(pc, a.out)
         back = ply.load_ply(SynthGaussians(teacher, device=dev, sh_degree=a.sh_degree), a.out, device=dev)

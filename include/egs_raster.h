@@ -470,6 +470,34 @@ int egs_l1_ssim_backward(int channels, int height, int width, const float* img, 
                          float* deferred_loss /*device [1] out or NULL*/, float* loss_running_sum /*device [1] in/out or NULL*/,
                          void* stream);
 
+/* ---- evaluation figures of one frame: 8-bit, hand-masked PSNR / SSIM sums (added within ABI 6: new entries only).
+ *      What the reference's eval_and_metric measures after writing render, ground truth and 1 - hand mask to 8-bit PNGs and reading them
+ *      back (the reference, trainers/eval_metric.py:41-175):
+ *          q(v) = uint8(clamp(v * 255 + 0.5, 0, 255))   in float32, truncating; NaN -> 0 (torchvision's save_image conversion)
+ *          kept = keep >= 0.5     u = kept ? q(img) / 255 : 0     v = kept ? q(gt) / 255 : 0      (masks are binary by contract)
+ *          sse      = sum over kept pixels and channels of (q(img) - q(gt))^2                    -- an exact integer
+ *          ssim_sum = sum over all C*H*W entries of the SSIM map of (u, v)                       -- the window of egs_l1_ssim_forward
+ *      from which the host forms  psnr = 10 log10(255^2 * C*H*W / sse)  (inf for sse == 0; the divisor counts gated pixels too, as the
+ *      reference's mean does)  and  ssim = ssim_sum / (C*H*W).  Two launches on `stream`: the strips (one {float, uint32} partial each into
+ *      `partial`, egs_eval_metrics_partial_bytes of scratch) and ONE wave that adds the partials in a fixed order, int64 and float64 -- the
+ *      row is bit-identical run to run.  That wave writes rows[cursor[0]] and then stores cursor[0] + 1: the frame index lives on the device
+ *      because a captured launch cannot carry one in its arguments.  cursor[0] outside [0, capacity): nothing is written, the cursor still
+ *      advances, so the host sees an overrun.  `overflow` (device uint32[2] or NULL): the overflow word of the egs_forward_enqueue that
+ *      rendered `img` on the same stream -- [0] clipped flag, [1] instance count -- copied into the row, so that ONE host read after a sweep
+ *      tells which frames have to be rendered again.  q_img / q_gt (device uint8[C,H,W] or NULL): the quantised images, unmasked, planar --
+ *      what a caller writes to a PNG.  channels: 1 or 3 (else EGS_ERR_ARG); H*W >= 2^31: EGS_ERR_RANGE.  No allocation, no global state. */
+typedef struct egs_eval_row {
+    int64_t sse;                     /* sum of squared 8-bit differences over kept pixels and channels */
+    double  ssim_sum;                /* sum of the SSIM map over all C*H*W entries */
+    int64_t clipped;                 /* overflow[0] of the forward that produced the image (0 without `overflow`) */
+    int64_t instances;               /* overflow[1]: that forward's instance count (0 without `overflow`) */
+} egs_eval_row;                      /* 32 bytes */
+size_t egs_eval_metrics_partial_bytes(int channels, int height, int width);
+int egs_eval_metrics(int channels, int height, int width, const float* img /*[C,H,W]*/, const float* gt /*[C,H,W]*/,
+                     const float* keep /*[H,W] or NULL: all kept*/, const uint32_t* overflow /*device [2] or NULL*/, void* partial /*scratch*/,
+                     uint8_t* q_img /*[C,H,W] out or NULL*/, uint8_t* q_gt /*[C,H,W] out or NULL*/, void* rows /*egs_eval_row[capacity]*/,
+                     int capacity, int32_t* cursor /*device [1] in/out*/, void* stream);
+
 /* The same launch carrying, in extra workgroups, what a rasterizer backward of the same frame needs done before its blend
  * kernel: ordering the tiles by the cost the forward recorded, clearing the gradient accumulator (`scratch`) and, with a sink, the
  * fused optimizer's per-step bookkeeping.  In a training step this launch sits between the two blends and leaves most of the

@@ -578,3 +578,86 @@ def eval_metrics(image, gt, keep=None, rows=None, cursor=None, overflow=None, ou
         _lib.check(L.egs_eval_metrics(Cc, H, W, _p(img), _p(g), _p(k), _p(overflow), _p(partial), _p(q_img), _p(q_gt), _p(rows), int(rows.shape[0]),
                                       _p(cursor), _stream(dev)))
     return dict(rows=rows, cursor=cursor, q_image=q_img, q_gt=q_gt)
+
+
+MASK_ROW_WORDS = 6      # include/egs_raster.h egs_mask_row as int64 words: predicted, target, intersection, kept, clipped, instances
+
+
+def mask_rows(n, dev):
+    """(rows int64[n, 6] zeroed, cursor int32[1] = 0) for label_mask: the caller-owned result array and the device-side frame index."""
+    return torch.zeros((int(n), MASK_ROW_WORDS), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def _mask_plane(t, name, H=None, W=None):
+    """A mask as a contiguous float32 [H,W] tensor on its HIP device ([1,H,W] and [H,W] are both accepted; other types are converted first)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on {t.device}: fused HIP op has no CPU path (use egogaussian_amd.losses)")
+    t = t.detach()
+    if t.dim() == 3 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 2 or (H is not None and tuple(t.shape) != (H, W)):
+        raise RuntimeError(f"{name}: one value per pixel, [H,W] or [1,H,W]" + ("" if H is None else f" with H, W = {H}, {W}") + f"; got {tuple(t.shape)}")
+    return t.to(torch.float32).contiguous()
+
+
+def label_mask(image, threshold=0.5, target=None, keep=None, rows=None, cursor=None, overflow=None, mask=True, out=None):
+    """The predicted object mask of one label render and its counts against the dataset's mask, by the HIP kernel (include/egs_raster.h
+    egs_label_mask; losses.label_mask is the torch statement): set = ((c0 + c1) + c2) / 3 > threshold; the mask holds 255 / 0 for EVERY
+    pixel, the counts -- predicted, target (target >= 0.5), intersection, kept -- run over the pixels with keep >= 0.5 (None: all).
+    image: [3,H,W]; target, keep: [H,W] or [1,H,W] or None.  rows, cursor: mask_rows(capacity, device) -- the kernel writes row cursor[0] and
+    advances the cursor on the device (a full array is left untouched while the cursor still counts); None: a fresh one-row array.
+    overflow: a _C.StepGuard's `overflow` words of the forward that rendered `image`; they travel in the row.
+    mask=False: no mask bytes are written; out: a contiguous uint8[H,W] tensor to write them into.
+    Does not synchronise.  -> dict(rows, cursor, mask8) of device tensors.  HIP tensors only."""
+    L = _lib.load()
+    img = _need_hip(image.detach(), "image")
+    if img.dim() != 3 or img.shape[0] != 3:
+        raise RuntimeError("label_mask: image is a [3,H,W] label render")
+    _, H, W = img.shape
+    dev = img.device
+    t = None if target is None else _mask_plane(target, "target", H, W)
+    k = None if keep is None else _mask_plane(keep, "keep", H, W)
+    if (rows is None) != (cursor is None):
+        raise RuntimeError("label_mask: rows and cursor go together (fused.mask_rows)")
+    if rows is None:
+        rows, cursor = mask_rows(1, dev)
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 2 and rows.shape[1] == MASK_ROW_WORDS and rows.is_contiguous()
+            and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1):
+        raise RuntimeError("label_mask: rows is a contiguous int64[capacity, 6] tensor and cursor an int32[1] tensor on the image's device")
+    if overflow is not None and not (overflow.is_cuda and overflow.dtype == torch.int32 and overflow.numel() == 2 and overflow.is_contiguous()):
+        raise RuntimeError("label_mask: overflow is a StepGuard's int32[2] device tensor")
+    if out is not None:
+        if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (H, W) and out.is_contiguous()):
+            raise RuntimeError("label_mask: out is a contiguous uint8[H,W] tensor on the image's device")
+        m8 = out
+    else:
+        m8 = torch.empty((H, W), dtype=torch.uint8, device=dev) if mask else None
+    partial = torch.empty(max(int(L.egs_label_mask_partial_bytes(H, W)), 16), dtype=torch.uint8, device=dev)
+    with _hip.device_ctx(dev):
+        _lib.check(L.egs_label_mask(H, W, _p(img), float(threshold), _p(t), _p(k), _p(overflow), _p(partial), _p(m8), _p(rows), int(rows.shape[0]),
+                                    _p(cursor), _stream(dev)))
+    return dict(rows=rows, cursor=cursor, mask8=m8)
+
+
+def interaction_gate(hand_mask, obj_mask=None, dilate_size=None, out=None):
+    """The background stage's gradient gate by the HIP kernel (include/egs_raster.h egs_interaction_gate; losses.interaction_gate is the torch
+    statement): 1 - dilate_k(hand_mask | obj_mask), float32 [H,W], 1 where the image gradient passes.  A pixel is set when either mask is
+    non-zero there (torch.logical_or's rule); dilate_size = k (odd, 1..31; None: k = 1, the plain OR) is the reference's
+    conv2d(ones(k, k), padding = k // 2) > 0.  Masks: [H,W] or [1,H,W], any type (converted to float32 first).
+    out: a float32 tensor of H*W elements to write into -- e.g. the `gate` segment of a graph.pack_frame frame (a view; 4-byte alignment is
+    enough).  Does not synchronise.  HIP tensors only."""
+    L = _lib.load()
+    a = _mask_plane(hand_mask, "hand_mask")
+    H, W = a.shape
+    b = None if obj_mask is None else _mask_plane(obj_mask, "obj_mask", H, W)
+    k = 1 if dilate_size is None else int(dilate_size)
+    if k < 1 or k > 31 or k % 2 == 0:
+        raise ValueError(f"interaction_gate: dilate_size must be odd and within 1..31, got {dilate_size}")
+    dev = a.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.numel() == H * W and out.is_contiguous()):
+        raise RuntimeError("interaction_gate: out is a contiguous float32 tensor (or view) of H*W elements on the masks' device")
+    with _hip.device_ctx(dev):
+        _lib.check(L.egs_interaction_gate(H, W, _p(a), _p(b), k, _p(out), _stream(dev)))
+    return out

@@ -69,6 +69,8 @@ def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
     accum_T (a step captured with motion=True): the object's accumulated pose, 4x4 or 3x4 -- its first three rows travel as 12 floats.
     obj_mask (a step captured with object_loss=): the object mask [H,W] or [1,H,W]; the frame then stores gt * obj_mask -- the image the object
     stages compare against -- and the mask.
+    The background stage's gate, 1 - dilate_k(hand mask | object mask), can be written into the frame afterwards without a tensor of its own:
+    fused.interaction_gate(hand, obj, k, out=frame[off["gate"][0]:off["gate"][1]]) with off from frame_layout(..., gated=True).
     GraphedTrainStep(frame) then refreshes every static input of the captured step with ONE device copy."""
     off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None, obj_mask is not None)
     f = torch.zeros(size, device=gt.device, dtype=torch.float32)

@@ -81,6 +81,10 @@ class OpacityEntropy(C.Structure):               # egs_opacity_entropy
     _fields_ = [("weight", C.c_void_p), ("upstream", C.c_void_p), ("scratch", C.c_void_p), ("n_vis", C.c_void_p), ("value", C.c_void_p)]
 
 
+class MaskRow(C.Structure):                      # egs_mask_row
+    _fields_ = [(n, C.c_int64) for n in ("predicted", "target", "intersection", "kept", "clipped", "instances")]
+
+
 ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
@@ -125,6 +129,9 @@ SIGNATURES = {
     "egs_l1_ssim_pair_forward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egs_eval_metrics_partial_bytes": (C.c_size_t, [i32, i32, i32]),
     "egs_eval_metrics": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "egs_label_mask_partial_bytes": (C.c_size_t, [i32, i32]),
+    "egs_label_mask": (C.c_int, [i32, i32, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "egs_interaction_gate": (C.c_int, [i32, i32, vp, vp, i32, vp, vp]),
 
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),

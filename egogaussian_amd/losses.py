@@ -119,3 +119,42 @@ def eval_metrics(image, gt, keep=None):
     psnr_v = torch.where(sse == 0, torch.full_like(mse, float("inf")), -10.0 * torch.log10(mse.clamp_min(1e-300)))
     u, v = qx.to(dt) / 255, qy.to(dt) / 255
     return dict(sse=sse, psnr=psnr_v.to(dt), ssim=ssim(u, v))
+
+
+def label_mask(render_label, threshold=0.5, target=None, keep=None):
+    """The predicted object mask of one label render (the reference, trainers/train_static.py:187-188: mean over the channels, > 0.5, stored
+    as an 8-bit image) and its counts against the dataset's mask:
+        set = ((c0 + c1) + c2) / 3 > threshold      the channel mean in float32, added in this order; strict, so NaN is not set
+        mask = set ? 255 : 0                        uint8 [H,W], every pixel: the stored mask ignores `keep`, as the reference's PNG does
+        kept = keep >= 0.5 (None: every pixel);  predicted = #(kept & set), target = #(kept & target >= 0.5), intersection, kept = #kept
+    render_label: [3,H,W]; target, keep: [H,W] or [1,H,W].  -> dict(mask: uint8[H,W]; predicted, target, intersection, kept: int64 tensors).
+    The oracle of the HIP kernel behind fused.label_mask, on any device."""
+    assert render_label.dim() == 3 and render_label.shape[0] == 3
+    x = render_label.detach().to(torch.float32)
+    H, W = x.shape[-2], x.shape[-1]
+    mean = ((x[0] + x[1]) + x[2]) / 3
+    on = mean > threshold
+    kept = torch.ones_like(on) if keep is None else keep.reshape(H, W).to(torch.float32) >= 0.5
+    tgt = torch.zeros_like(on) if target is None else target.reshape(H, W).to(torch.float32) >= 0.5
+    count = lambda m: m.sum(dtype=torch.int64)
+    return dict(mask=on.to(torch.uint8) * 255, predicted=count(kept & on), target=count(kept & tgt), intersection=count(kept & on & tgt), kept=count(kept))
+
+
+def interaction_gate(hand_mask, obj_mask=None, dilate_size=None):
+    """The gate of the background stage's image gradient (the reference, trainers/train_static_bg.py:14-21, 81-99):
+        1 - dilate_k(hand_mask | obj_mask),   float32 [H,W]
+    a pixel is set when either mask is non-zero there (torch.logical_or); it is gated (0) when any pixel of the k x k window around it, clipped
+    to the image, is set -- a max-pool of the set indicator with stride 1 and padding k // 2 (padded entries never win).  k = dilate_size, odd;
+    None: no dilation.  The oracle of the HIP kernel behind fused.interaction_gate, on any device."""
+    a = hand_mask.detach()
+    H, W = a.shape[-2], a.shape[-1]
+    on = a.reshape(H, W) != 0
+    if obj_mask is not None:
+        on = torch.logical_or(on, obj_mask.detach().reshape(H, W) != 0)
+    k = 1 if dilate_size is None else int(dilate_size)
+    if k < 1 or k % 2 == 0:
+        raise ValueError(f"interaction_gate: dilate_size must be odd and positive, got {dilate_size}")
+    on = on.to(torch.float32)
+    if k > 1:
+        on = torch.nn.functional.max_pool2d(on[None, None], kernel_size=k, stride=1, padding=k // 2)[0, 0]
+    return 1.0 - on

@@ -1,0 +1,235 @@
+"""The mask hand-off between the static stage and the background stage: predicted object masks, the model split, the dilated gate.
+
+At the end of each static phase the reference (its trainers/train_static.py:167-197) sets is_object from the trained labels, splits the model
+into an object and a background PLY and, for every static frame, renders the label, thresholds its channel mean at 0.5 and stores the result
+as an 8-bit image; train.py:80-90 then completes the dataset's object masks with those predictions, and the background stage
+(trainers/train_static_bg.py:14-21, 81-99) gates its image gradient by 1 - dilate_5(hand mask | object mask).
+
+Here a sweep is, per frame, ONE device copy of a packed label frame (graph.pack_label_frame: camera[, gate], object mask) into static buffers
+and ONE replay of a graph captured once under torch.no_grad(): the scalar-colour label forward -- the call of GraphedTrainStep's label step --
+followed by the mask kernel (fused.label_mask / include/egs_raster.h egs_label_mask), which writes the frame's mask bytes and, at a device-side
+cursor, its row: the predicted / target / intersection / kept pixel counts and the forward's overflow word.  The mask is copied into a
+uint8[F,H,W] device tensor; the host reads the rows once, after the last frame.  A frame whose row says the captured instance capacity
+clipped it is rendered again eagerly.  The gate itself is fused.interaction_gate, which can write straight into the `gate` segment of a
+graph.pack_frame frame.  losses.label_mask / losses.interaction_gate are the torch statements of both definitions.
+
+Writing the masks to image files and copying them into a dataset is the caller's: `masks` stays on the device (0 / 255, what the PNG holds).
+"""
+import copy
+import math
+
+import numpy as np
+import torch
+
+from . import _C
+from . import fused
+from .graph import _StaticCamera, frame_layout
+
+
+def decode_rows(rows):
+    """rows: int64[F, 6] (include/egs_raster.h egs_mask_row), on any device -> dict of numpy arrays predicted, target, intersection, kept,
+    instances (int64), clipped (bool), iou (float64): intersection / (predicted + target - intersection), 1.0 where that union is 0."""
+    r = np.ascontiguousarray(rows.detach().cpu().numpy()).reshape(-1, fused.MASK_ROW_WORDS)
+    pred, tgt, inter = r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy()
+    union = pred + tgt - inter
+    iou = np.where(union == 0, 1.0, inter.astype(np.float64) / np.maximum(union, 1).astype(np.float64))
+    return dict(predicted=pred, target=tgt, intersection=inter, kept=r[:, 3].copy(), clipped=r[:, 4] != 0, instances=r[:, 5].copy(), iou=iou)
+
+
+class MaskPass:
+    def __init__(self, pc, bg, graphed=True, threshold=0.5):
+        """pc: the model whose labels are rendered (a capacity.CapacityGaussians model is followed through its live row count); bg: the
+        label render's background, float32[3].  graphed=False: the same calls, eagerly, frame by frame (no capture, no capacity to outgrow).
+        threshold: a pixel is predicted object when the channel mean of its label render exceeds it (the reference: 0.5)."""
+        self.pc, self.bg = pc, bg
+        self.graphed, self.threshold = bool(graphed), float(threshold)
+        self.graph = None
+        self.guard = None
+        self.capacity = 0
+        self.host_reads = 0               # reads of result rows this object did (one per sweep; one more when frames were rendered again)
+        self._key = None
+
+    # ---- static inputs ------------------------------------------------------------------------------------------------------------
+    def _make_static(self, cam, numel, dev):
+        H, W = int(cam.image_height), int(cam.image_width)
+        for gated in (False, True):
+            off, size = frame_layout(0, H * W, gated=gated, label_phase=True)
+            if size == numel:
+                break
+        else:
+            raise ValueError(f"MaskPass: a frame of {numel} floats is not graph.pack_label_frame(cam, obj_mask[, gate]) of a {W}x{H} camera")
+        self._frame = torch.zeros(size, device=dev, dtype=torch.float32)
+        fr = self._frame
+        self._cam = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
+        self._target = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(H, W)
+        self._gate = fr[off["gate"][0]:off["gate"][1]].view(H, W) if gated else None
+        self._mask8 = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        self._shape = (H, W)
+        self._key = (numel, H, W, float(cam.FoVx), float(cam.FoVy), dev)
+        self.graph = None
+
+    def _body(self, rows, cursor, guard):
+        """One frame on the static inputs: the label forward (GraphedTrainStep._label_body's call), then the mask kernel writing at `cursor`."""
+        pc, cam = self.pc, self._cam
+        with torch.no_grad():
+            raw = pc.get_raw_parameters() if getattr(pc, "get_raw_parameters", None) is not None else None
+            if raw is not None:
+                scales, rotations, opacity = raw
+                act = _C.ACT_RAW_PARAMETERS | _C.ACT_SCALAR_COLOR
+            else:
+                scales, rotations, opacity = pc.get_scaling, pc.get_rotation, pc.get_opacity
+                act = _C.ACT_SCALAR_COLOR
+            xyz = pc.get_xyz.detach()
+            e = torch.empty(0, device=xyz.device)
+            H, W = self._shape
+            _, color, _, _, _, geom, binning, img = _C.rasterize_gaussians(
+                self.bg, xyz, pc.get_label.detach().view(-1), opacity.detach(), scales.detach(), rotations.detach(), 1.0, e,
+                cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), H, W, e,
+                pc.active_sh_degree, cam.camera_center, False, False, act, None, getattr(pc, "active_count", None), guard, None, True, None)
+            res = fused.label_mask(color, self.threshold, target=self._target, keep=self._gate, rows=rows, cursor=cursor,
+                                   overflow=None if guard is None else guard.overflow, out=self._mask8)
+        return (color, geom, binning, img), res
+
+    # ---- capture --------------------------------------------------------------------------------------------------------------------
+    def _capture(self, first_frame, n_rows, capacity, capacity_margin):
+        dev = self._frame.device
+        self.guard = _C.StepGuard(dev)
+        self._rows, self._cursor = fused.mask_rows(n_rows, dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._frame.copy_(first_frame)
+            self._body(None, None, None)                               # eager: sets the capacity hint, allocator pools, lazy state
+            r_seen = _C.stats["num_rendered"]
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.capacity = max(int(r_seen * capacity_margin), _C.stats["capacity"]) if capacity is None else max(int(capacity), 1)
+        _C.set_capacity_hint(self.capacity, dev)
+        self._model_version = getattr(self.pc, "model_version", 0)
+        self.graph = torch.cuda.CUDAGraph()
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self.graph.capture_begin(capture_error_mode="thread_local")
+            try:
+                self._captured = self._body(self._rows, self._cursor, self.guard)
+            finally:
+                self.graph.capture_end()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+
+    def recapture(self):
+        """Forget the captured graph (after the model reallocated its arrays): the next run() captures again."""
+        self.graph = None
+
+    def _read_rows(self, rows):
+        """THE device-to-host read of a sweep's results (tests wrap it to count)."""
+        self.host_reads += 1
+        return rows.cpu()
+
+    # ---- the sweep ------------------------------------------------------------------------------------------------------------------
+    def run(self, frames, cam, capacity=None, capacity_margin=1.25):
+        """frames: packed frames of graph.pack_label_frame(cam, obj_mask[, gate=keep]) -- a list or an [F, frame] tensor; `gate` is
+        keep = 1 - hand mask (frames packed without it count every pixel), the object mask is the target the prediction is counted against.
+        cam: any camera of the sweep: the image size and field of view (a captured pass is specific to one).  capacity: the instance
+        capacity to capture with, as is (default: capacity_margin x the first frame's count; frames that outgrow it are rendered again eagerly).
+        -> dict(masks: uint8[F,H,W] on the device, 255 where the label render's channel mean exceeds the threshold -- every pixel, gated or
+        not; predicted, target, intersection, kept: int64[F], counted over the kept pixels; iou: float64[F] (1.0 where the union is empty);
+        mean_iou; rerendered: indices of the frames rendered again; instances: int64[F], the captured forwards' instance counts (0 for eager
+        frames))."""
+        n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
+        if n == 0:
+            raise ValueError("MaskPass.run: no frames")
+        first = frames[0]
+        if not first.is_cuda:
+            raise RuntimeError(f"MaskPass: frames are on {first.device}: the mask pass has no CPU path (losses.label_mask is the torch statement)")
+        dev = first.device
+        key = (first.numel(), int(cam.image_height), int(cam.image_width), float(cam.FoVx), float(cam.FoVy), dev)
+        if self._key != key:
+            self._make_static(cam, first.numel(), dev)
+        masks = torch.empty((n,) + self._shape, dtype=torch.uint8, device=dev)
+        if self.graphed:
+            if self.graph is not None and getattr(self.pc, "model_version", 0) != self._model_version:
+                raise RuntimeError("MaskPass: the model reallocated its arrays (CapacityGaussians.grow) after this pass was captured; "
+                                   "the captured launches point at freed memory -- call recapture() first")
+            if self.graph is None or self._rows.shape[0] < n or (capacity is not None and int(capacity) != self.capacity):
+                self._capture(first, max(n, 64), capacity, capacity_margin)
+            rows, cursor = self._rows, self._cursor
+            rows.zero_(); cursor.zero_()
+            for i in range(n):
+                self._frame.copy_(frames[i], non_blocking=True)          # the frame's every input: one copy
+                self.graph.replay()
+                masks[i].copy_(self._mask8, non_blocking=True)
+        else:
+            rows, cursor = fused.mask_rows(n, dev)
+            for i in range(n):
+                self._frame.copy_(frames[i], non_blocking=True)
+                self._body(rows, cursor, None)
+                masks[i].copy_(self._mask8, non_blocking=True)
+        fig = decode_rows(self._read_rows(rows[:n]))
+        again = [int(i) for i in np.nonzero(fig["clipped"])[0]]
+        if again:
+            rows2, cursor2 = fused.mask_rows(len(again), dev)
+            for i in again:
+                self._frame.copy_(frames[i], non_blocking=True)
+                self._body(rows2, cursor2, None)                           # eager: the forward grows its buffers by itself
+                masks[i].copy_(self._mask8, non_blocking=True)
+            fig2 = decode_rows(self._read_rows(rows2))
+            for k in ("predicted", "target", "intersection", "kept", "iou"):
+                fig[k][again] = fig2[k]
+        return dict(masks=masks, predicted=fig["predicted"], target=fig["target"], intersection=fig["intersection"], kept=fig["kept"],
+                    iou=fig["iou"], mean_iou=float(np.mean(fig["iou"])), rerendered=again, instances=fig["instances"])
+
+
+def infer_is_object_from_label(g):
+    """GaussianModel.infer_is_object_from_label (the reference, scene/gaussian_model.py:1116-1121): is_object = 1 where the trained label
+    exceeds 0.5, else 0, int32 [N,1].  A capacity.CapacityGaussians model keeps its array and only its live rows are written."""
+    with torch.no_grad():
+        label = g.get_label.detach()
+        n = getattr(g, "n_active", None)
+        if n is None:
+            g._is_object = (label > 0.5).to(torch.int32).reshape(-1, 1)
+            return g._is_object
+        if g._is_object.dtype != torch.int32:
+            g._is_object = g._is_object.to(torch.int32)
+        g._is_object[:n] = (label[:n] > 0.5).to(torch.int32).reshape(-1, 1)
+    return g._is_object
+
+
+def split_object_background(g):
+    """-> (obj, bg): two copies of `g`, one pruned to the Gaussians with is_object == 1 and one to those with is_object == 0, as the
+    reference does before it saves the two PLY files (trainers/train_static.py:172-178: deepcopy, prune_points) -- pruned by
+    densify.prune_points(..., during_training=False), which builds new arrays and writes into none.  `g` is unchanged and shares no
+    per-Gaussian array with the halves; they carry no optimizer, and a capacity-sized model's halves hold its live rows only, as plain
+    models.  Both are ready for ply.save_ply."""
+    from .densify import prune_points
+    n = getattr(g, "n_active", None)
+    is_obj = g.get_is_object.detach()[:n].flatten()
+    halves = []
+    with torch.no_grad():
+        for drop in (is_obj != 1, is_obj != 0):
+            h = copy.copy(g)                                             # the arrays are replaced below, never written
+            h.optimizer = None
+            h.__dict__.pop("_sel_cache", None)
+            if n is not None:                                            # a plain model of the live rows: nothing beyond them belongs to it
+                from .capacity import CapacityGaussians
+                from .scene_synth import SynthGaussians
+                if type(h) is CapacityGaussians:
+                    h.__class__ = SynthGaussians
+                for a in ("capacity", "n_active", "active_count"):
+                    h.__dict__.pop(a, None)
+            for a in _PER_GAUSSIAN:
+                t = getattr(h, a, None)
+                if torch.is_tensor(t):
+                    setattr(h, a, t.detach()[:n])
+            prune_points(h, drop, during_training=False)
+            for a in _STATS:                                             # (prune_points leaves the training statistics to a training model)
+                t = getattr(h, a, None)
+                if torch.is_tensor(t):
+                    setattr(h, a, t[~drop].clone())
+            halves.append(h)
+    return halves[0], halves[1]
+
+
+_PER_GAUSSIAN = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "_label", "_is_object", "_generation",
+                 "max_radii2D", "xyz_gradient_accum", "denom")
+_STATS = ("max_radii2D", "xyz_gradient_accum", "denom")

@@ -14,6 +14,12 @@ capacity on the device and re-captures itself with more room (GraphedTrainStep(c
 captured step with the weight of the opacity-entropy term switched on (`step.entropy_weight = --entropy-weight`: a device scalar, no
 re-capture), then `prune_points(get_opacity < 0.5)` on the capacity model (in place: no re-capture either).
 
+`--mask-handoff` appends the hand-off between the reference's static stage and its background stage (trainers/train_static.py:104-109,
+167-197, train.py:80-90, trainers/train_static_bg.py:81-99): a short label phase (GraphedTrainStep(label_phase=True)) against object masks
+rendered from the teacher, the predicted masks of every frame by one captured sweep (masks.MaskPass), is_object from the labels, the split
+into an object and a background model, and a few background-stage steps on the background model, their image gradient gated by
+fused.interaction_gate(hand mask, predicted mask, 5) written straight into the packed frame.
+
 It shows the order of calls a trainer needs; it is not part of the measured path.  `--log` appends a line per report interval
 (iteration, live Gaussians, it/s so far, held-out PSNR), which is how profiles/r2_train_synth_*.log were produced.
 """
@@ -26,13 +32,74 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from egogaussian_amd import densify, ply                                          # noqa: E402
+from egogaussian_amd import densify, fused, masks, ply                            # noqa: E402
 from egogaussian_amd.capacity import CapacityGaussians                            # noqa: E402
 from egogaussian_amd.evaluate import EvalPass                                     # noqa: E402
-from egogaussian_amd.graph import GraphedTrainStep, pack_frame                    # noqa: E402
+from egogaussian_amd.graph import GraphedTrainStep, frame_layout, pack_frame, pack_label_frame      # noqa: E402
 from egogaussian_amd.losses import psnr                                           # noqa: E402
-from egogaussian_amd.renderer import render                                       # noqa: E402
+from egogaussian_amd.renderer import get_render_label, render                     # noqa: E402
 from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe, N_FRAMES   # noqa: E402
+
+
+def mask_handoff(pc, teacher, cams, gts, bg, a, report):
+    """The hand-off between the static stage and the background stage on the trained model `pc` -> dict of what happened."""
+    import numpy as np
+    dev, (H, W), F = bg.device, gts[0].shape[-2:], len(cams)
+    # the dataset's side: the object is the 30 % of the teacher with the smallest x; its masks are the teacher's label renders, thresholded;
+    # the hand is a rectangle of its own per frame
+    with torch.no_grad():
+        tpc = SynthGaussians(teacher, device=dev, sh_degree=a.sh_degree, requires_grad=False)
+        x = tpc._xyz[:, :1]
+        tpc._label = torch.where(x < torch.quantile(x, 0.3), 4.0, -4.0)
+        obj_masks = [(get_render_label(c, tpc, bg, scalar=True).mean(0) > 0.5).float() for c in cams]
+        del tpc
+    hands = []
+    for k in range(F):
+        h = torch.zeros(H, W, device=dev)
+        y0, x0 = (H // 8) + (k * 7) % (H // 2), (W // 8) + (k * 13) % (W // 2)
+        h[y0:y0 + H // 5, x0:x0 + W // 6] = 1.0
+        hands.append(h)
+    # 1. the label phase: only the labels move, the hand is gated out of the loss (train_static.py:104-109)
+    for g in pc.optimizer.param_groups:
+        if g["name"] == "label":
+            g["lr"] = a.label_lr
+    lstep = GraphedTrainStep(pc, pc.optimizer, bg, label_phase=True, gated=True)
+    lstep.capture(cams[0], obj_mask=obj_masks[0], gate=1.0 - hands[0], warmup=1, capacity_margin=1.5)
+    lframes = [pack_label_frame(cams[k], obj_masks[k], gate=1.0 - hands[k]) for k in range(F)]
+    for j in range(a.label_iters):
+        lstep(lframes[j % F])
+    torch.cuda.synchronize()
+    lstep.check()
+    # 2. the predicted masks of every frame: one captured sweep, one host read (train_static.py:183-196)
+    mp = masks.MaskPass(pc, bg)
+    res = mp.run(lframes, cams[0], capacity_margin=1.5)
+    report(f"mask hand-off: {a.label_iters} label iterations (loss {float(lstep.loss):.4f}); predicted masks of {F} frames, mean IoU against the "
+           f"object masks {res['mean_iou']:.4f} over the pixels outside the hand, {len(res['rerendered'])} frame(s) rendered again, {mp.host_reads} host read(s)")
+    # 3. is_object from the labels, the two models (train_static.py:167-178)
+    masks.infer_is_object_from_label(pc)
+    obj, bgm = masks.split_object_background(pc)
+    report(f"mask hand-off: {obj._xyz.shape[0]} object + {bgm._xyz.shape[0]} background Gaussians")
+    # 4. a few background-stage steps (train_static_bg.py:81-110): the image gradient gated by 1 - dilate_5(hand | predicted mask), the gate
+    #    written by the kernel into the packed frame's own segment
+    for name in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "_label"):
+        setattr(bgm, name, getattr(bgm, name).detach().clone().requires_grad_(True))
+    bgm.training_setup(capturable=True)
+    off, _ = frame_layout(gts[0].numel(), H * W, gated=True)
+    bframes = []
+    for k in range(F):
+        fr = pack_frame(cams[k], gts[k], gate=hands[k])
+        fused.interaction_gate(hands[k], res["masks"][k], a.dilate_size, out=fr[off["gate"][0]:off["gate"][1]])
+        bframes.append(fr)
+    gated = float(np.mean([float((fr[off["gate"][0]:off["gate"][1]] == 0).float().mean()) for fr in bframes]))
+    bstep = GraphedTrainStep(bgm, bgm.optimizer, bg, lambda_dssim=0.2, gated=True, densify_stats=True, entropy_reg=True)
+    bstep.capture(cams[0], gts[0], warmup=1, capacity_margin=1.5, gate=bframes[0][off["gate"][0]:off["gate"][1]].view(H, W))
+    for j in range(a.bg_iters):
+        bstep(bframes[j % F])
+    torch.cuda.synchronize()
+    bstep.check()
+    report(f"mask hand-off: {a.bg_iters} background-stage steps, {100 * gated:.1f} % of the pixels gated (dilate {a.dilate_size}), loss {float(bstep.loss):.4f}")
+    return dict(mean_iou=res["mean_iou"], rerendered=len(res["rerendered"]), host_reads=mp.host_reads, n_object=int(obj._xyz.shape[0]),
+                n_background=int(bgm._xyz.shape[0]), gated_fraction=gated, object=obj, background=bgm, masks=res["masks"])
 
 
 def main(argv=None):
@@ -62,6 +129,13 @@ def main(argv=None):
     ap.add_argument("--entropy-iters", type=int, default=0,
                     help="after --iters, this many iterations with the opacity-entropy term on, then prune opacity < 0.5 (train_static.py:97-102,139-141)")
     ap.add_argument("--entropy-weight", type=float, default=0.1, help="weight of the entropy term during that phase (the reference: 0.1)")
+    ap.add_argument("--mask-handoff", action="store_true",
+                    help="after training: a label phase, the predicted object masks of every frame (masks.MaskPass), the object / background split "
+                         "and a few background-stage steps gated by fused.interaction_gate(hand, predicted mask, --dilate-size)")
+    ap.add_argument("--label-iters", type=int, default=200, help="iterations of the label phase of --mask-handoff")
+    ap.add_argument("--label-lr", type=float, default=0.1, help="learning rate of the labels during that phase")
+    ap.add_argument("--bg-iters", type=int, default=50, help="background-stage steps of --mask-handoff")
+    ap.add_argument("--dilate-size", type=int, default=5, help="dilation of the background stage's gate (the reference's train.py: 5)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     H, W = a.height, a.width
@@ -177,6 +251,8 @@ def main(argv=None):
     pc.train_report["eval"] = dict(mean_psnr=ev["mean_psnr"], mean_ssim=ev["mean_ssim"], rerendered=len(ev["rerendered"]))
     report(f"evaluation pass over {len(cams)} cameras: PSNR {ev['mean_psnr']:.3f} dB, SSIM {ev['mean_ssim']:.5f} (8-bit images; "
            f"{len(ev['rerendered'])} frame(s) rendered again)")
+    if a.mask_handoff:
+        pc.train_report["mask_handoff"] = mask_handoff(pc, teacher, cams, gts, bg, a, report)
     if a.out:
         ply.save_ply(pc, a.out)
         back = ply.load_ply(SynthGaussians(teacher, device=dev, sh_degree=a.sh_degree), a.out, device=dev)

@@ -498,6 +498,42 @@ int egs_eval_metrics(int channels, int height, int width, const float* img /*[C,
                      uint8_t* q_img /*[C,H,W] out or NULL*/, uint8_t* q_gt /*[C,H,W] out or NULL*/, void* rows /*egs_eval_row[capacity]*/,
                      int capacity, int32_t* cursor /*device [1] in/out*/, void* stream);
 
+/* ---- the mask hand-off between the static stage and the background stage (added within ABI 6: new entries only).
+ *      The reference thresholds the label render of every static frame at the end of each static phase and stores the result as an 8-bit
+ *      image (trainers/train_static.py:167-197); the background stage gates its image gradient by 1 - dilate_k(hand mask | object mask)
+ *      (trainers/train_static_bg.py:14-21, 81-99).  Both results are integer-exact.
+ *
+ *      egs_label_mask: per pixel  x = ((c0 + c1) + c2) / 3  in float32 (the label phase's logit, the same definition),
+ *          set = x > threshold   (strict; NaN is not set)          mask8 = set ? 255 : 0   for EVERY pixel: the stored mask ignores `keep`
+ *          kept = keep >= 0.5 (NULL: every pixel)                  tgt = target >= 0.5 (NULL: none)
+ *          predicted = #(kept & set)   target = #(kept & tgt)   intersection = #(kept & set & tgt)   kept = #kept       -- exact integers
+ *      Two launches on `stream`: the pixels (one uint32[4] partial per workgroup into `partial`, egs_label_mask_partial_bytes of scratch) and
+ *      ONE wave that adds the partials in a fixed order as int64, writes rows[cursor[0]] and stores cursor[0] + 1 -- the conventions of
+ *      egs_eval_metrics: cursor[0] outside [0, capacity) writes nothing and still advances; `overflow` (device uint32[2] or NULL) is the
+ *      overflow word of the forward that rendered `img`, copied into the row.  img needs 4-byte alignment only, mask8 none; 16-byte loads
+ *      and 4-byte mask stores are used when every address and H*W allow them, with the same result.  H*W >= 2^31: EGS_ERR_RANGE.
+ *
+ *      egs_interaction_gate: a pixel is SET when a != 0 || b != 0 (torch.logical_or's rule: NaN and negative values are set; at least one
+ *      of a, b is given); gate = 0.0f when any pixel of the k x k window around it, clipped to the image, is set, else 1.0f -- the
+ *      reference's conv2d(ones(k, k), padding = k / 2) > 0 with its zero padding, subtracted from one.  k odd, 1 <= k <= 31 (else
+ *      EGS_ERR_ARG); k = 1 is the plain OR.  gate needs 4-byte alignment only (it may be a view into a packed frame) and must not overlap
+ *      a or b.  One launch.  No allocation, no global state. */
+typedef struct egs_mask_row {
+    int64_t predicted;               /* kept pixels whose label logit exceeds the threshold */
+    int64_t target;                  /* kept pixels with target >= 0.5 */
+    int64_t intersection;            /* kept pixels with both */
+    int64_t kept;                    /* pixels with keep >= 0.5 (H*W without `keep`) */
+    int64_t clipped;                 /* overflow[0] of the forward that produced the image (0 without `overflow`) */
+    int64_t instances;               /* overflow[1]: that forward's instance count (0 without `overflow`) */
+} egs_mask_row;                      /* 48 bytes */
+size_t egs_label_mask_partial_bytes(int height, int width);
+int egs_label_mask(int height, int width, const float* img /*[3,H,W]*/, float threshold, const float* target /*[H,W] or NULL*/,
+                   const float* keep /*[H,W] or NULL: all kept*/, const uint32_t* overflow /*device [2] or NULL*/, void* partial /*scratch*/,
+                   uint8_t* mask8 /*[H,W] out or NULL*/, void* rows /*egs_mask_row[capacity]*/, int capacity,
+                   int32_t* cursor /*device [1] in/out*/, void* stream);
+int egs_interaction_gate(int height, int width, const float* a /*[H,W] or NULL*/, const float* b /*[H,W] or NULL*/, int k,
+                         float* gate /*[H,W] out*/, void* stream);
+
 /* The same launch carrying, in extra workgroups, what a rasterizer backward of the same frame needs done before its blend
  * kernel: ordering the tiles by the cost the forward recorded, clearing the gradient accumulator (`scratch`) and, with a sink, the
  * fused optimizer's per-step bookkeeping.  In a training step this launch sits between the two blends and leaves most of the

@@ -17,7 +17,8 @@ import torch
 
 from . import _C
 from . import fused
-from .graph import _StaticCamera, frame_layout
+from .frames import FrameStore
+from .graph import _StaticCamera, begin_capture, end_capture, frame_layout
 from .renderer import render
 from .scene_synth import Pipe
 
@@ -60,6 +61,14 @@ class EvalPass:
                 return off, size, gated, H, W
         raise ValueError(f"EvalPass: a frame of {numel} floats is not graph.pack_frame(cam, gt[, accum_R][, gate][, accum_T]) of a {W}x{H} camera "
                          f"with dynamic={self.dynamic}, motion={self.motion}")
+
+    def _check_store(self, store, cam):
+        lay = store.layout
+        if lay["label_phase"] or lay["object_loss"] or lay["dynamic"] != self.dynamic or lay["motion"] != self.motion:
+            raise ValueError(f"EvalPass: a store of layout {lay} does not hold graph.pack_frame(cam, gt[, accum_R][, gate][, accum_T]) frames "
+                             f"with dynamic={self.dynamic}, motion={self.motion}")
+        if (store.H, store.W) != (int(cam.image_height), int(cam.image_width)):
+            raise ValueError(f"EvalPass: the store's frames are {store.W}x{store.H}, the camera {cam.image_width}x{cam.image_height}")
 
     def _make_static(self, cam, numel, dev):
         off, size, gated, H, W = self._layout(cam, numel)
@@ -111,11 +120,11 @@ class EvalPass:
         self.graph = torch.cuda.CUDAGraph()
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            self.graph.capture_begin(capture_error_mode="thread_local")
+            begin_capture(self.graph)
             try:
                 self._captured = self._body(self._rows, self._cursor, self.guard)
             finally:
-                self.graph.capture_end()
+                end_capture(self.graph)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
 
@@ -131,15 +140,26 @@ class EvalPass:
     # ---- the sweep ------------------------------------------------------------------------------------------------------------------
     def run(self, frames, cam, capacity=None, capacity_margin=1.25):
         """frames: packed frames of graph.pack_frame(cam, gt, accum_R=, gate=keep, accum_T=) -- a list or an [F, frame] tensor; `gate` is
-        keep = 1 - hand mask (frames packed without it keep every pixel).  cam: any camera of the sweep: the image size and field of view
+        keep = 1 - hand mask (frames packed without it keep every pixel) --, or a frames.FrameStore of that layout: every frame of it, each
+        brought into the static buffers by one decode launch (from a ring set to 0 .. F - 1 before the sweep) instead of a copy.  cam: any camera of the sweep: the image size and field of view
         (a captured pass is specific to one, like a captured step).  capacity: the instance capacity to capture with, as is (default:
         capacity_margin x the first frame's count; frames that outgrow it are rendered again eagerly).
         -> dict(psnr, ssim: float64[F]; sse: int64[F]; mean_psnr, mean_ssim: the plain means; rerendered: indices of the frames rendered
         again; instances: int64[F], the captured forwards' instance counts (0 for eager frames)[; images: uint8[F,3,H,W] on the device])."""
-        n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
-        if n == 0:
-            raise ValueError("EvalPass.run: no frames")
-        first = frames[0]
+        store = frames if isinstance(frames, FrameStore) else None
+        if store is not None:
+            self._check_store(store, cam)
+            n, first = store.n_frames, store.frame(0)
+            ring = store.new_ring(n)
+            ring.set(range(n))                                          # the sweep's frames 0 .. n - 1: the decode walks them on the device
+            load = lambda i: store.decode(self._frame, ring=ring)       # (called once per frame, in order)
+            reload = lambda i: store.decode(self._frame, indices=[i])
+        else:
+            n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
+            if n == 0:
+                raise ValueError("EvalPass.run: no frames")
+            first = frames[0]
+            load = reload = lambda i: self._frame.copy_(frames[i], non_blocking=True)      # the frame's every input: one copy
         if not first.is_cuda:
             raise RuntimeError(f"EvalPass: frames are on {first.device}: the evaluation pass has no CPU path (losses.eval_metrics is the torch statement)")
         dev = first.device
@@ -157,14 +177,14 @@ class EvalPass:
             rows.zero_(); cursor.zero_()
             q = self._captured[1]["q_image"]
             for i in range(n):
-                self._frame.copy_(frames[i], non_blocking=True)          # the frame's every input: one copy
+                load(i)
                 self.graph.replay()
                 if images is not None:
                     images[i].copy_(q, non_blocking=True)
         else:
             rows, cursor = fused.eval_rows(n, dev)
             for i in range(n):
-                self._frame.copy_(frames[i], non_blocking=True)
+                load(i)
                 _, res = self._body(rows, cursor, None)
                 if images is not None:
                     images[i].copy_(res["q_image"], non_blocking=True)
@@ -174,7 +194,7 @@ class EvalPass:
         if again:
             rows2, cursor2 = fused.eval_rows(len(again), dev)
             for i in again:
-                self._frame.copy_(frames[i], non_blocking=True)
+                reload(i)
                 _, res = self._body(rows2, cursor2, None)                  # eager: the forward grows its buffers by itself
                 if images is not None:
                     images[i].copy_(res["q_image"], non_blocking=True)

@@ -24,6 +24,8 @@ ground truth, accum_R / accum_T, gate and object-mask contents (copied in per ca
 like a learning rate) and the learning rates (device scalars; `__call__` pushes
 host-side edits of `param_groups[i]["lr"]` -- the reference's per-iteration `update_learning_rate` -- before each replay).
 """
+import gc
+
 import torch
 
 from . import _C
@@ -102,6 +104,33 @@ def pack_label_frame(cam, obj_mask, gate=None):
     return f
 
 
+_gc_was_enabled = []
+
+
+def begin_capture(graph):
+    """graph.capture_begin with the cyclic garbage collector paused until end_capture.  A collection that starts while the capture is open
+    may finalise CUDAGraph objects and device allocations of steps dropped earlier, and their HIP calls are not allowed on a capturing
+    thread: the process aborts.  torch.cuda.graph avoids that with a gc.collect() before every capture, which costs milliseconds per
+    re-capture; pausing the collector for the capture costs nothing, and what it would have freed is freed at the next collection."""
+    _gc_was_enabled.append(gc.isenabled())
+    gc.disable()
+    try:
+        # thread_local: calls other threads make meanwhile (e.g. the RCCL watchdog polling its events) must not abort the capture
+        graph.capture_begin(capture_error_mode="thread_local")
+    except BaseException:
+        if _gc_was_enabled.pop():
+            gc.enable()
+        raise
+
+
+def end_capture(graph):
+    try:
+        graph.capture_end()
+    finally:
+        if _gc_was_enabled.pop():
+            gc.enable()
+
+
 class _StaticCamera:
     """Camera whose tensors are fixed device buffers; `load(cam)` copies another camera of the same intrinsics in."""
 
@@ -133,8 +162,18 @@ class _StaticCamera:
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
-                 motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False):
-        """entropy_reg:   the static image step with the entropy-regularisation phase available (/root/reference/trainers/train_static.py:97-102,
+                 motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False, frame_store=None, ring_capacity=4096):
+        """frame_store:   a frames.FrameStore of this step's layout (dynamic, motion, gated, object_loss, label_phase as given here, else
+                       ValueError): the dataset stays on the device in 8 bits and the captured graph BEGINS with one decode launch that
+                       writes the static frames of all `steps_per_replay` iterations from it, by index (include/egs_raster.h
+                       egs_frame_decode) -- no frame copy, no host work per replay beyond the launch.  capture(cam, index=i0): `cam` gives
+                       the image size and field of view, the warm-up steps run on frame i0.  step(indices) -- an int (steps_per_replay = 1),
+                       a sequence of S ints or an int32 device tensor of S entries -- writes them to the step's ring (`ring_capacity`
+                       entries, its own: a sweep over the same store leaves it alone) and replays; set_schedule(indices) writes K = a
+                       multiple of S entries once, after which step() only pushes learning rates and replays: replay n trains on entries
+                       nS .. nS + S - 1, wrapping at K.  Host indices are range-checked (IndexError); store_ok() tells whether the kernel
+                       ever had to clamp one.  Not with double_buffer (ValueError): nothing is left to hide.  None: packed float frames.
+        entropy_reg:   the static image step with the entropy-regularisation phase available (/root/reference/trainers/train_static.py:97-102,
                        trainers/train_static_bg.py:105-110: between std_train_iter and std_train_iter + entropy_reg_iter the loss also holds
                        0.1 * the mean binary entropy of the visible opacities).  The rasterizer's backward adds the term's share to the
                        gradient of the opacity logits itself (render(opacity_entropy=)), so the opacity stays a fused leaf and the step
@@ -191,6 +230,16 @@ class GraphedTrainStep:
                        (renderer.render, optimizer=): no gradient arrays, no optimizer launch for them; the step's loss must then
                        depend on the model through that one render only -- which is the step this class captures.  Results are
                        bit-identical either way."""
+        self.frame_store, self._ring = frame_store, None
+        if frame_store is not None:
+            if double_buffer:
+                raise ValueError("GraphedTrainStep(frame_store=) does not go with double_buffer: the decode is part of the graph, no copy is left to hide")
+            mine = dict(dynamic=bool(dynamic), motion=bool(motion), gated=bool(gated), object_loss=object_loss is not None, label_phase=bool(label_phase))
+            if frame_store.layout != mine:
+                raise ValueError(f"GraphedTrainStep(frame_store=): the store's layout {frame_store.layout} is not this step's {mine}")
+            self._ring_capacity = int(ring_capacity)
+            if self._ring_capacity < max(1, int(steps_per_replay)):
+                raise ValueError("GraphedTrainStep(frame_store=): ring_capacity >= steps_per_replay")
         self.entropy_reg = bool(entropy_reg)
         if self.entropy_reg:
             for name, on in (("dynamic", dynamic), ("motion", motion), ("pose", pose is not None), ("object_loss", object_loss is not None),
@@ -364,8 +413,9 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            self.graph.capture_begin(capture_error_mode="thread_local")
+            begin_capture(self.graph)
             try:
+                self._decode_frames()
                 self.losses, self.label_grads, keeps = [], [], []
                 for k in range(self.steps_per_replay):
                     self.loss, out = self._label_body(k)
@@ -374,7 +424,7 @@ class GraphedTrainStep:
                 self.image, self.radii, self.label_grad = out["render"], out["radii"], out["label_grad"]
                 self.visibility_filter = self.viewspace_grad = None
             finally:
-                self.graph.capture_end()
+                end_capture(self.graph)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self._sets = None
@@ -406,13 +456,38 @@ class GraphedTrainStep:
     def _frame_layout(self, gt):
         return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion, self.object_loss is not None)
 
+    def _decode_frames(self):
+        """frame_store=: the first launch of the captured graph -- every static frame from the store, by the ring; the cursor advances on the device."""
+        if self.frame_store is not None:
+            self.frame_store.decode(self._frames, ring=self._ring)
+
+    def _store_frame(self, index, given):
+        """frame_store=: the inputs of capture() from frame `index` of the store (the static frames are filled from them, the warm-up runs on them)."""
+        if any(v is not None for v in given):
+            raise ValueError("GraphedTrainStep(frame_store=).capture(cam, index=i0): the frame's contents come from the store")
+        store = self.frame_store
+        parts = store.parts(0 if index is None else index)
+        if self._ring is None:
+            self._ring = store.new_ring(self._ring_capacity)
+        self._ring.set([0 if index is None else int(index)] * self.steps_per_replay)
+        self._ring_set = False
+        return parts
+
     def capture(self, cam, gt=None, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
-                obj_mask=None):
+                obj_mask=None, index=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
         more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
         capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow).
         obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask."""
+        if self.frame_store is not None and not isinstance(cam, _StaticCamera):
+            if (int(cam.image_height), int(cam.image_width)) != (self.frame_store.H, self.frame_store.W):
+                raise ValueError(f"GraphedTrainStep(frame_store=).capture: the camera is {cam.image_width}x{cam.image_height}, the store's frames "
+                                 f"{self.frame_store.W}x{self.frame_store.H}")
+            parts = self._store_frame(index, (gt, accum_R, gate, accum_T, obj_mask))
+            gt, accum_R, gate, accum_T, obj_mask = parts["gt"], parts["accum_R"], parts["gate"], parts["accum_T"], parts["obj_mask"]
+        elif index is not None:
+            raise ValueError("capture(index=) goes with GraphedTrainStep(frame_store=)")
         if self.label_phase:
             if obj_mask is None and not isinstance(cam, _StaticCamera):
                 raise ValueError("GraphedTrainStep(label_phase=True).capture(cam, obj_mask=...): the label step's frame is camera[, gate], obj_mask")
@@ -492,9 +567,9 @@ class GraphedTrainStep:
         # torch.cuda.empty_cache() (3 ms at this size), which a trainer that re-captures after every densification pays each time
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            # thread_local: calls other threads make meanwhile (e.g. the RCCL watchdog polling its events) must not abort the capture
-            self.graph.capture_begin(capture_error_mode="thread_local")
+            begin_capture(self.graph)
             try:
+                self._decode_frames()
                 self.losses = []
                 for k in range(self.steps_per_replay):
                     if k:
@@ -507,7 +582,7 @@ class GraphedTrainStep:
                 self.visibility_filter = out["visibility_filter"]      # follows every replay (a view of the rasterizer's saved state)
                 self.viewspace_grad = out["viewspace_points"].grad
             finally:
-                self.graph.capture_end()
+                end_capture(self.graph)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self._sets = None
@@ -537,7 +612,7 @@ class GraphedTrainStep:
             g2 = torch.cuda.CUDAGraph()
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
-                g2.capture_begin(capture_error_mode="thread_local")
+                begin_capture(g2)
                 try:
                     losses2 = []
                     for k in range(self.steps_per_replay):
@@ -546,7 +621,7 @@ class GraphedTrainStep:
                         loss2, out2 = self._body(k)
                         losses2.append(loss2)
                 finally:
-                    g2.capture_end()
+                    end_capture(g2)
             torch.cuda.current_stream(dev).wait_stream(side)
             torch.cuda.synchronize(dev)
             second = dict(graph=g2, frames=frames2, slots=slots2, loss=loss2, losses=losses2, image=out2["render"].detach(), radii=out2["radii"],
@@ -572,16 +647,29 @@ class GraphedTrainStep:
             return self.capture(cam, None, warmup=warmup, capacity_margin=capacity_margin, obj_mask=self.obj_mask, gate=self.gate)
         return self.capture(cam, gt, warmup=warmup, capacity_margin=capacity_margin, capacity_cams=capacity_cams)
 
-    def __call__(self, cam, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None):
+    def __call__(self, cam=None, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None):
         """One training iteration (steps_per_replay of them): copy inputs in, replay.  Returns the (device, static) loss tensor of
         the last iteration (`self.losses` has all).  Either (camera, ground-truth image[, accum_R][, gate]) or packed frames from
         pack_frame(): one for a single-iteration step, a [S, frame] tensor (one copy) or a list of S for steps_per_replay = S.
         ready (double_buffer only): a torch.cuda.Event recorded after the packed frames were COMPLETELY written; the side-stream copy
         waits for it.  Without it the copy waits for everything enqueued on the current stream so far -- always correct, but frames
         produced on the current stream right before the call then serialise behind the replay that is still running."""
-        if gt is None and self._sets is not None:
+        if self.frame_store is not None:
+            if any(v is not None for v in (gt, accum_R, gate, ready, accum_T, obj_mask)):
+                raise ValueError("GraphedTrainStep(frame_store=): step(indices) or, after set_schedule(), step()")
+            if cam is not None:                                          # frame indices: ring[0:S], ctl = {0, S} as one small copy
+                k = 1 if isinstance(cam, int) else int(cam.numel()) if torch.is_tensor(cam) else len(cam)
+                if k != self.steps_per_replay:
+                    raise ValueError(f"step(indices): {k} indices given, {self.steps_per_replay} frames per replay")
+                self._ring.set(cam)
+                self._ring_set = True
+            elif not self._ring_set:
+                raise ValueError("step(): no frame indices yet -- step(indices) or set_schedule(indices) first")
+        elif cam is None:
+            raise ValueError("GraphedTrainStep: a camera or packed frames (step() without arguments goes with frame_store=)")
+        elif gt is None and self._sets is not None:
             return self._call_double_buffered(cam, ready)
-        if self.label_phase and obj_mask is not None:
+        elif self.label_phase and obj_mask is not None:
             if self.steps_per_replay != 1:
                 raise ValueError("steps_per_replay > 1 takes packed frames")
             self.cam.load(cam)
@@ -619,6 +707,25 @@ class GraphedTrainStep:
         if self.check_every > 0 and self._calls % self.check_every == 0:
             self.check()
         return self.loss
+
+    def set_schedule(self, indices):
+        """frame_store=: the frames of the coming replays, once: a 1-D sequence (or int32 device tensor) whose length K is a multiple of
+        steps_per_replay and at most the ring's capacity (ValueError), range-checked on the host (IndexError), written to the ring with
+        ctl = {0, K} as one small copy.  step() then only replays: replay n trains on entries nS .. nS + S - 1, wrapping at K."""
+        if self.frame_store is None:
+            raise ValueError("set_schedule: this step was built without frame_store=")
+        if self._ring is None:
+            raise ValueError("set_schedule: capture() first (the ring is made there)")
+        k = int(indices.numel()) if torch.is_tensor(indices) else len(indices)
+        if k < 1 or k % self.steps_per_replay or k > self._ring.capacity:
+            raise ValueError(f"set_schedule: {k} indices; a positive multiple of steps_per_replay = {self.steps_per_replay}, at most the ring's "
+                             f"capacity {self._ring.capacity}")
+        self._ring.set(indices)
+        self._ring_set = True
+
+    def store_ok(self):
+        """frame_store=: True while the decode never had to clamp a frame index (reads the store's status word: synchronises)."""
+        return self.frame_store.ok()
 
     def _call_double_buffered(self, frames, ready=None):
         """Packed frames, two captured graphs: the copy into set b's static frames runs on a side stream as soon as set b's previous

@@ -85,6 +85,12 @@ class MaskRow(C.Structure):                      # egs_mask_row
     _fields_ = [(n, C.c_int64) for n in ("predicted", "target", "intersection", "kept", "clipped", "instances")]
 
 
+class FrameLayout(C.Structure):                  # egs_frame_layout
+    _fields_ = [(n, C.c_int64) for n in ("frame_floats", "image_floats", "small_begin", "small_floats", "gate_begin", "obj_mask_begin",
+                                         "image_stride", "plane_words", "n_planes")]
+
+
+FRAME_DYNAMIC, FRAME_MOTION, FRAME_GATED, FRAME_OBJECT_LOSS, FRAME_LABEL_PHASE = 1, 2, 4, 8, 16      # EGS_FRAME_*
 ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
@@ -132,6 +138,8 @@ SIGNATURES = {
     "egs_label_mask_partial_bytes": (C.c_size_t, [i32, i32]),
     "egs_label_mask": (C.c_int, [i32, i32, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "egs_interaction_gate": (C.c_int, [i32, i32, vp, vp, i32, vp, vp]),
+    "egs_frame_store_layout": (C.c_int, [i32, i32, i32, C.POINTER(FrameLayout)]),
+    "egs_frame_decode": (C.c_int, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
 
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),

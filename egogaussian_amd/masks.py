@@ -23,7 +23,8 @@ import torch
 
 from . import _C
 from . import fused
-from .graph import _StaticCamera, frame_layout
+from .frames import FrameStore
+from .graph import _StaticCamera, begin_capture, end_capture, frame_layout
 
 
 def decode_rows(rows):
@@ -50,6 +51,12 @@ class MaskPass:
         self._key = None
 
     # ---- static inputs ------------------------------------------------------------------------------------------------------------
+    def _check_store(self, store, cam):
+        if not store.layout["label_phase"]:
+            raise ValueError(f"MaskPass: a store of layout {store.layout} does not hold graph.pack_label_frame frames (label_phase=True)")
+        if (store.H, store.W) != (int(cam.image_height), int(cam.image_width)):
+            raise ValueError(f"MaskPass: the store's frames are {store.W}x{store.H}, the camera {cam.image_width}x{cam.image_height}")
+
     def _make_static(self, cam, numel, dev):
         H, W = int(cam.image_height), int(cam.image_width)
         for gated in (False, True):
@@ -109,11 +116,11 @@ class MaskPass:
         self.graph = torch.cuda.CUDAGraph()
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            self.graph.capture_begin(capture_error_mode="thread_local")
+            begin_capture(self.graph)
             try:
                 self._captured = self._body(self._rows, self._cursor, self.guard)
             finally:
-                self.graph.capture_end()
+                end_capture(self.graph)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
 
@@ -129,17 +136,29 @@ class MaskPass:
     # ---- the sweep ------------------------------------------------------------------------------------------------------------------
     def run(self, frames, cam, capacity=None, capacity_margin=1.25):
         """frames: packed frames of graph.pack_label_frame(cam, obj_mask[, gate=keep]) -- a list or an [F, frame] tensor; `gate` is
-        keep = 1 - hand mask (frames packed without it count every pixel), the object mask is the target the prediction is counted against.
+        keep = 1 - hand mask (frames packed without it count every pixel), the object mask is the target the prediction is counted against --,
+        or a frames.FrameStore(label_phase=True): every frame of it, each brought into the static buffers by one decode launch (from a ring
+        set to 0 .. F - 1 before the sweep) instead of a copy.
         cam: any camera of the sweep: the image size and field of view (a captured pass is specific to one).  capacity: the instance
         capacity to capture with, as is (default: capacity_margin x the first frame's count; frames that outgrow it are rendered again eagerly).
         -> dict(masks: uint8[F,H,W] on the device, 255 where the label render's channel mean exceeds the threshold -- every pixel, gated or
         not; predicted, target, intersection, kept: int64[F], counted over the kept pixels; iou: float64[F] (1.0 where the union is empty);
         mean_iou; rerendered: indices of the frames rendered again; instances: int64[F], the captured forwards' instance counts (0 for eager
         frames))."""
-        n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
-        if n == 0:
-            raise ValueError("MaskPass.run: no frames")
-        first = frames[0]
+        store = frames if isinstance(frames, FrameStore) else None
+        if store is not None:
+            self._check_store(store, cam)
+            n, first = store.n_frames, store.frame(0)
+            ring = store.new_ring(n)
+            ring.set(range(n))                                          # the sweep's frames 0 .. n - 1: the decode walks them on the device
+            load = lambda i: store.decode(self._frame, ring=ring)       # (called once per frame, in order)
+            reload = lambda i: store.decode(self._frame, indices=[i])
+        else:
+            n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
+            if n == 0:
+                raise ValueError("MaskPass.run: no frames")
+            first = frames[0]
+            load = reload = lambda i: self._frame.copy_(frames[i], non_blocking=True)      # the frame's every input: one copy
         if not first.is_cuda:
             raise RuntimeError(f"MaskPass: frames are on {first.device}: the mask pass has no CPU path (losses.label_mask is the torch statement)")
         dev = first.device
@@ -156,13 +175,13 @@ class MaskPass:
             rows, cursor = self._rows, self._cursor
             rows.zero_(); cursor.zero_()
             for i in range(n):
-                self._frame.copy_(frames[i], non_blocking=True)          # the frame's every input: one copy
+                load(i)
                 self.graph.replay()
                 masks[i].copy_(self._mask8, non_blocking=True)
         else:
             rows, cursor = fused.mask_rows(n, dev)
             for i in range(n):
-                self._frame.copy_(frames[i], non_blocking=True)
+                load(i)
                 self._body(rows, cursor, None)
                 masks[i].copy_(self._mask8, non_blocking=True)
         fig = decode_rows(self._read_rows(rows[:n]))
@@ -170,7 +189,7 @@ class MaskPass:
         if again:
             rows2, cursor2 = fused.mask_rows(len(again), dev)
             for i in again:
-                self._frame.copy_(frames[i], non_blocking=True)
+                reload(i)
                 self._body(rows2, cursor2, None)                           # eager: the forward grows its buffers by itself
                 masks[i].copy_(self._mask8, non_blocking=True)
             fig2 = decode_rows(self._read_rows(rows2))

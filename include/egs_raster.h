@@ -534,6 +534,57 @@ int egs_label_mask(int height, int width, const float* img /*[3,H,W]*/, float th
 int egs_interaction_gate(int height, int width, const float* a /*[H,W] or NULL*/, const float* b /*[H,W] or NULL*/, int k,
                          float* gate /*[H,W] out*/, void* stream);
 
+/* ---- the 8-bit frame store (added within ABI 6: new entries only).
+ *      The reference's images come from 8-bit files (utils/general_utils.py: uint8 -> float / 255) and its masks are binarised to {0, 1}; a
+ *      packed float32 frame of the captured steps (camera, image, accumulated pose, gate, object mask) therefore says in 16 - 20 bytes per
+ *      pixel what 3 bytes and 1 - 2 bits hold.  A store keeps F frames of one image size and one frame layout in that precision on the
+ *      device; egs_frame_decode writes n_rows complete packed frames from it, chosen on the device through a ring of frame indices, so a
+ *      captured step fetches the frames of its next iterations itself.
+ *
+ *      flags (EGS_FRAME_*) name the layout, as the Python package's graph.frame_layout: DYNAMIC adds accum_R (9 floats), MOTION accum_T (12),
+ *      GATED the gate plane, OBJECT_LOSS the obj_mask plane (the image is then stored pre-multiplied by it); LABEL_PHASE is the label step's
+ *      frame -- camera[, gate], obj_mask, no image -- and goes with GATED only (else EGS_ERR_MODE).  Every segment of a packed frame starts on
+ *      a 16-byte boundary and is padded with 0.0f to the next:   [image] cam [accum_R] [accum_T] [gate] [obj_mask].
+ *      egs_frame_store_layout fills the sizes below.  The store's arrays, all caller-owned:
+ *          img    uint8  [F][image_stride]              3 H W bytes in CHW order, then zero bytes; image_stride = 3 H W rounded up to 16
+ *          bits   uint32 [F][n_planes][plane_words]     pixel p is bit p % 32 of word p / 32; gate first, then obj_mask; 1 means 1.0f;
+ *                                                       plane_words = ceil(H W / 32) rounded up to 4; unused bits are 0
+ *          small  float  [F][small_floats]              floats small_begin .. small_begin + small_floats of the packed frame, untouched
+ *          table  float  [256]                          byte -> float.  The image value of byte b is b / 255.0f by TRUE division; the host
+ *                                                       fills the table with exactly that (b * (1 / 255.f) differs at 126 codes).
+ *
+ *      egs_frame_decode: two launches on `stream`.  The first writes out[k][0 .. frame_floats) for k < n_rows -- every float, the padding as
+ *      0.0f, nothing beyond -- from frame ring[(ctl[0] + k) % ctl[1]]: `ring` is a device int32[ring_capacity], `ctl` two device int32 words,
+ *      cursor and length, read on the device because a captured launch cannot carry them in its arguments.  The second, one lane, stores
+ *      ctl[0] = (ctl[0] + n_rows) % ctl[1]; it is a launch of its own because no workgroup of the first may change the cursor while another
+ *      may still read it.  A frame index outside [0, n_frames) is clamped into it and the sticky device word status[0] is incremented (once
+ *      per such row; once more per call whose ctl had to be brought into 0 <= cursor < length, 1 <= length <= ring_capacity): whatever the
+ *      ring and ctl hold, nothing outside the store is read.  16-byte loads and stores are used when out, img and small are 16-byte
+ *      aligned, 4-byte ones otherwise (out may be any 4-byte aligned view), with the same result.
+ *      EGS_ERR_ARG before any device work: height, width, n_frames, n_rows or ring_capacity < 1, unknown flag bits, a NULL small / ring /
+ *      ctl / status / out, a NULL img or table for a layout with an image, a NULL bits for a layout with planes.  H*W >= 2^31 or
+ *      n_rows > 65535: EGS_ERR_RANGE.  No allocation, no global state. */
+#define EGS_FRAME_DYNAMIC      1
+#define EGS_FRAME_MOTION       2
+#define EGS_FRAME_GATED        4
+#define EGS_FRAME_OBJECT_LOSS  8
+#define EGS_FRAME_LABEL_PHASE 16
+typedef struct egs_frame_layout {
+    int64_t frame_floats;            /* floats of one packed frame (a multiple of 4) */
+    int64_t image_floats;            /* 3 H W, 0 for the label layout; the image segment starts at float 0 */
+    int64_t small_begin;             /* first float of `cam` in the packed frame */
+    int64_t small_floats;            /* 36, 48 or 60: cam[, accum_R][, accum_T] with their padding */
+    int64_t gate_begin;              /* first float of the gate segment, -1 without one */
+    int64_t obj_mask_begin;          /* first float of the obj_mask segment, -1 without one */
+    int64_t image_stride;            /* bytes per frame of `img` (0 for the label layout) */
+    int64_t plane_words;             /* uint32 words per plane and frame of `bits` */
+    int64_t n_planes;                /* 0, 1 or 2 */
+} egs_frame_layout;                  /* 72 bytes */
+int egs_frame_store_layout(int height, int width, int flags, egs_frame_layout* layout /*HOST out*/);
+int egs_frame_decode(int height, int width, int flags, int n_frames, int n_rows, const uint8_t* img, const uint32_t* bits, const float* small,
+                     const float* table, const int32_t* ring, int ring_capacity, int32_t* ctl /*device [2] in/out*/,
+                     int32_t* status /*device [1] in/out*/, float* out /*[n_rows][frame_floats]*/, void* stream);
+
 /* The same launch carrying, in extra workgroups, what a rasterizer backward of the same frame needs done before its blend
  * kernel: ordering the tiles by the cost the forward recorded, clearing the gradient accumulator (`scratch`) and, with a sink, the
  * fused optimizer's per-step bookkeeping.  In a training step this launch sits between the two blends and leaves most of the

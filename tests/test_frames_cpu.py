@@ -1,0 +1,301 @@
+"""CPU: the 8-bit frame store -- its C ABI (declared, bound, exported; argument errors before any device work; the strides the library and
+the Python side compute), FrameStore.put / from_packed / frame on CPU tensors against graph.pack_frame / pack_label_frame, the 256 codes, the
+rejections, the sizes, and the host-side checks of GraphedTrainStep(frame_store=).  Every decoded value has one right answer: every
+comparison is an equality of bits."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("egs_frame_decode", "egs_frame_store_layout")
+SHAPES = [(1, 1), (3, 5), (7, 65), (37, 53), (48, 64)]
+LAYOUTS = {"static-gated": dict(gated=True),
+           "dynamic-motion-gated": dict(dynamic=True, motion=True, gated=True),
+           "object-loss": dict(dynamic=True, motion=True, gated=True, object_loss=True),
+           "label-gated": dict(label_phase=True, gated=True),
+           "label": dict(label_phase=True),
+           "plain": dict()}
+
+
+def bits_equal(a, b):
+    return a.dtype == b.dtype == torch.float32 and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def frame_inputs(H, W, layout, seed, device="cpu"):
+    """-> (camera, put() keywords with a uint8 image, the packed float frame graph.pack_frame / pack_label_frame gives for the same inputs)."""
+    from egogaussian_amd.graph import pack_frame, pack_label_frame
+    from egogaussian_amd.scene_synth import make_camera
+    g = torch.Generator().manual_seed(seed)
+    cam = make_camera(seed % 300, H, W, device=device)
+    gt8 = torch.randint(0, 256, (3, H, W), generator=g, dtype=torch.uint8).to(device)
+    gate = (torch.rand(H, W, generator=g) < 0.7).float().to(device)
+    mask = (torch.rand(H, W, generator=g) < 0.4).float().to(device)
+    R = torch.rand(3, 3, generator=g).to(device)
+    T = torch.rand(4, 4, generator=g).to(device)
+    gt = gt8.float() / 255.0
+    if layout.get("label_phase"):
+        kw = dict(obj_mask=mask)
+        if layout.get("gated"):
+            kw["gate"] = gate
+        return cam, kw, pack_label_frame(cam, mask, gate if layout.get("gated") else None)
+    kw = dict(gt=gt8)
+    if layout.get("dynamic"):
+        kw["accum_R"] = R
+    if layout.get("motion"):
+        kw["accum_T"] = T
+    if layout.get("gated"):
+        kw["gate"] = gate
+    if layout.get("object_loss"):
+        kw["obj_mask"] = mask
+    want = pack_frame(cam, gt, kw.get("accum_R"), kw.get("gate"), kw.get("accum_T"), kw.get("obj_mask"))
+    return cam, kw, want
+
+
+def test_header_binding_and_library_agree_within_abi_6():
+    from egogaussian_amd import lib
+    L = lib.load()
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "egs_raster.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(egs_[a-z0-9_]+)\s*\(", text))
+    for n in NEW:
+        assert n in declared and n in lib.SIGNATURES and hasattr(L, n), n
+    assert declared == set(lib.SIGNATURES)
+    assert L.egs_abi_version() == 6 and lib.ABI_VERSION == 6 and re.search(r"#define\s+EGS_ABI_VERSION\s+6\b", text)
+    assert C.sizeof(lib.FrameLayout) == 72 and "typedef struct egs_frame_layout" in text
+    for name, value in (("DYNAMIC", lib.FRAME_DYNAMIC), ("MOTION", lib.FRAME_MOTION), ("GATED", lib.FRAME_GATED), ("OBJECT_LOSS", lib.FRAME_OBJECT_LOSS),
+                        ("LABEL_PHASE", lib.FRAME_LABEL_PHASE)):
+        assert re.search(r"#define\s+EGS_FRAME_%s\s+%d\b" % (name, value), text), name
+    assert "frames.hip" in open(os.path.join(ROOT, "egogaussian_amd", "csrc", "Makefile")).read()
+
+
+def test_decode_argument_errors_precede_device_work():
+    from egogaussian_amd import lib
+    L = lib.load()
+    p = 4096                                                           # (fake non-null pointers are never dereferenced before the checks)
+    GATED = lib.FRAME_GATED
+
+    def call(H=8, W=8, flags=GATED, F=3, S=2, img=p, bits=p, small=p, table=p, ring=p, cap=16, ctl=p, status=p, out=p):
+        return L.egs_frame_decode(H, W, flags, F, S, img, bits, small, table, ring, cap, ctl, status, out, None)
+
+    for name in ("img", "bits", "small", "table", "ring", "ctl", "status", "out"):
+        assert call(**{name: None}) == -1, name
+    for name in ("H", "W", "F", "S", "cap"):
+        assert call(**{name: 0}) == -1 and call(**{name: -2}) == -1, name
+    assert call(H=65536, W=32768) == -3                                  # H W = 2^31
+    assert call(H=32768, W=65536, flags=lib.FRAME_LABEL_PHASE, img=None, table=None) == -3
+    assert call(flags=64) == -1                                          # an unknown flag
+    assert call(flags=lib.FRAME_LABEL_PHASE | lib.FRAME_DYNAMIC) == -2   # the label frame carries no pose
+    # what a layout does not have may be NULL: the check passes them and stops at the next missing pointer
+    assert call(flags=lib.FRAME_LABEL_PHASE, img=None, table=None, out=None) == -1
+    assert call(flags=0, bits=None, out=None) == -1
+    fl = lib.FrameLayout()
+    assert L.egs_frame_store_layout(8, 8, GATED, None) == -1 and L.egs_frame_store_layout(0, 8, GATED, C.byref(fl)) == -1
+    assert L.egs_frame_store_layout(65536, 32768, GATED, C.byref(fl)) == -3
+
+
+@pytest.mark.parametrize("shape", SHAPES + [(540, 960)], ids=lambda s: "x".join(map(str, s)))
+def test_library_and_python_agree_on_the_layout(shape):
+    """egs_frame_store_layout against graph.frame_layout and FrameStore's strides; the alignment every 16-byte access relies on."""
+    from egogaussian_amd import lib
+    from egogaussian_amd.frames import FrameStore
+    from egogaussian_amd.graph import frame_layout
+    L = lib.load()
+    H, W = shape
+    for name, lay in LAYOUTS.items():
+        st = FrameStore(H, W, 1, **lay)
+        fl = lib.FrameLayout()
+        assert L.egs_frame_store_layout(H, W, st.flags, C.byref(fl)) == 0
+        off, size = frame_layout(0 if lay.get("label_phase") else 3 * H * W, H * W, **lay)
+        assert (fl.frame_floats, fl.image_floats, fl.small_begin) == (size, off["gt"][1] if "gt" in off else 0, off["cam"][0]), name
+        assert fl.gate_begin == (off["gate"][0] if "gate" in off else -1) and fl.obj_mask_begin == (off["obj_mask"][0] if "obj_mask" in off else -1), name
+        assert (fl.image_stride, fl.plane_words, fl.small_floats, fl.n_planes) == (st.image_stride, st.plane_words, st.small_floats, len(st.planes)), name
+        assert st.frame_floats == size and st.off == off
+        assert fl.frame_floats % 4 == 0 and fl.image_stride % 16 == 0 and fl.plane_words % 4 == 0 and fl.small_floats % 4 == 0 and fl.small_begin % 4 == 0
+        assert fl.image_stride >= fl.image_floats and fl.plane_words * 32 >= H * W
+        last = max(off[n][1] for n in ("cam", "accum_R", "accum_T") if n in off)
+        assert fl.small_begin + fl.small_floats == (last + 3) // 4 * 4
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("layout", list(LAYOUTS), ids=list(LAYOUTS))
+def test_frame_equals_pack_frame_bit_for_bit(layout, shape):
+    from egogaussian_amd.frames import FrameStore
+    H, W = shape
+    lay = LAYOUTS[layout]
+    store = FrameStore(H, W, 3, **lay)
+    wants = []
+    for i in range(3):
+        cam, kw, want = frame_inputs(H, W, lay, seed=100 * H + W + i)
+        if i == 1 and "gt" in kw:
+            kw["gt"] = kw["gt"].float() / 255.0                         # a float image of exact quotients goes in as well
+        if i == 2 and "gate" in kw:
+            kw["gate"] = kw["gate"].bool()[None]                         # [1,H,W], another type
+        store.put(i, cam, **kw)
+        wants.append(want)
+    for i in range(3):
+        got = store.frame(i)
+        assert got.numel() == store.frame_floats and bits_equal(got, wants[i]), (layout, shape, i)
+    assert bits_equal(store.frames(), torch.stack(wants)) and bits_equal(store.frames([2, 0]), torch.stack([wants[2], wants[0]]))
+    # the inverse of packing, from a list and from an [F, frame] tensor
+    for packed in (wants, torch.stack(wants)):
+        back = FrameStore.from_packed(packed, H, W, **lay)
+        assert back.n_frames == 3 and all(bits_equal(back.frame(i), wants[i]) for i in range(3))
+        if store.img is not None:
+            assert torch.equal(back.img, store.img)
+        if store.bits is not None:
+            assert torch.equal(back.bits, store.bits)
+        assert torch.equal(back.small, store.small)
+    parts = store.parts(1)
+    assert bits_equal(parts["frame"], wants[1]) and tuple(parts["cam"].shape) == (35,)
+    assert (parts["gt"] is None) == bool(lay.get("label_phase")) and (parts["gate"] is None) == (not lay.get("gated"))
+
+
+def test_all_256_codes_decode_to_the_quotient_and_the_reciprocal_product_does_not():
+    from egogaussian_amd.frames import FrameStore, byte_table
+    from egogaussian_amd.scene_synth import make_camera
+    codes = torch.arange(256, dtype=torch.uint8)
+    want = torch.arange(256, dtype=torch.uint8).float() / 255.0
+    store = FrameStore(16, 16, 1)
+    store.put(0, make_camera(0, 16, 16), gt=codes.view(1, 16, 16).expand(3, 16, 16))
+    got = store.frame(0)[:768].view(3, 256)
+    assert all(bits_equal(got[c], want) for c in range(3))
+    assert bits_equal(byte_table(), want)
+    product = codes.float() * torch.tensor(1.0 / 255.0, dtype=torch.float32)
+    differ = int((product.view(torch.int32) != want.view(torch.int32)).sum())
+    assert differ == 126, differ                                          # (what this test guards against would pass a weaker comparison)
+
+
+def test_rejections():
+    from egogaussian_amd.frames import FrameStore, FrameRing
+    from egogaussian_amd.graph import pack_frame
+    from egogaussian_amd.scene_synth import make_camera
+    H, W = 5, 7
+    cam = make_camera(1, H, W)
+    gt = torch.randint(0, 256, (3, H, W), generator=torch.Generator().manual_seed(1), dtype=torch.uint8).float() / 255.0
+    ones = torch.ones(H, W)
+    store = FrameStore(H, W, 2, gated=True)
+    before = store.frame(0).clone()
+    half = gt.clone(); half[1, 2, 3] = 0.5
+    with pytest.raises(ValueError, match="k / 255"):
+        store.put(0, cam, gt=half, gate=ones)
+    for bad in (float("nan"), 1.5, -0.25, float(torch.nextafter(torch.tensor(1.0 / 255.0), torch.tensor(1.0)))):
+        x = gt.clone(); x[0, 0, 0] = bad
+        with pytest.raises(ValueError):
+            store.put(0, cam, gt=x, gate=ones)
+    soft = ones.clone(); soft[2, 2] = 0.3
+    with pytest.raises(ValueError, match="exactly 0 or 1"):
+        store.put(0, cam, gt=gt, gate=soft)
+    with pytest.raises(ValueError):
+        store.put(0, cam, gt=gt)                                          # the layout has a gate
+    with pytest.raises(ValueError):
+        store.put(0, cam, gt=gt, gate=ones, obj_mask=ones)                # and no object mask
+    with pytest.raises(ValueError):
+        store.put(0, cam, gt=gt[:, :4], gate=ones)
+    assert bits_equal(store.frame(0), before), "a refused put() left something behind"
+    store.put(0, cam, gt=half, gate=ones, quantize=True)
+    assert int(store.img[0, 1 * H * W + 2 * W + 3]) == round(0.5 * 255) == 128
+    assert float(store.frame(0)[1 * H * W + 2 * W + 3]) == float(torch.tensor(128, dtype=torch.uint8).float() / 255.0)
+    # a layout mismatch in from_packed; soft values in packed frames
+    packed = pack_frame(cam, gt, gate=ones)
+    with pytest.raises(ValueError, match="layout"):
+        FrameStore.from_packed([packed], H, W)
+    with pytest.raises(ValueError, match="layout"):
+        FrameStore.from_packed([packed], H, W, gated=True, dynamic=True)
+    with pytest.raises(ValueError):
+        FrameStore.from_packed([pack_frame(cam, half, gate=ones)], H, W, gated=True)
+    with pytest.raises(ValueError):
+        FrameStore.from_packed([pack_frame(cam, gt, gate=soft)], H, W, gated=True)
+    leak = pack_frame(cam, gt, torch.eye(3), ones, torch.eye(4), obj_mask=torch.zeros(H, W))
+    leak[0] = 1.0                                                       # an image value outside the object mask: not a pack_frame frame
+    with pytest.raises(ValueError, match="object mask"):
+        FrameStore.from_packed([leak], H, W, dynamic=True, motion=True, gated=True, object_loss=True)
+    with pytest.raises(ValueError):
+        FrameStore(H, W, 1, label_phase=True, dynamic=True)
+    # host indices
+    for i in (-1, 2):
+        with pytest.raises(IndexError):
+            store.frame(i)
+        with pytest.raises(IndexError):
+            store.put(i, cam, gt=gt, gate=ones)
+        with pytest.raises(IndexError):
+            store._ring.set([0, i])
+    ring = FrameRing(4, 2, "cpu")
+    assert ring.set([1, 0, 1]) == 3 and ring.ctl.tolist() == [0, 3] and ring.ring.tolist() == [1, 0, 1, 0]
+    assert ring.set(1) == 1 and ring.ctl.tolist() == [0, 1]
+    with pytest.raises(ValueError):
+        ring.set([0] * 5)
+    with pytest.raises(ValueError):
+        ring.set([])
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        store.decode(torch.zeros(store.frame_floats))
+    assert store.ring.numel() == 4096 and store.ctl.numel() == 2 and store.status.dtype == torch.int32 and store.ok()
+
+
+def test_sizes_at_540x960():
+    """Derived, not measured: 3 bytes + 1 bit per pixel against 16 bytes (0.1953), 3 bytes + 2 bits against 20 bytes (0.1625), the small
+    float blocks included."""
+    from egogaussian_amd.frames import FrameStore
+    H, W, F = 540, 960, 2
+    a = FrameStore(H, W, F, gated=True)
+    assert a.float_nbytes == F * a.frame_floats * 4 == F * 4 * (3 * H * W + 36 + H * W)
+    assert a.nbytes == F * (3 * H * W + H * W // 8 + 36 * 4)
+    assert a.nbytes / a.float_nbytes <= 0.20
+    b = FrameStore(H, W, F, dynamic=True, motion=True, gated=True, object_loss=True)
+    assert b.nbytes == F * (3 * H * W + 2 * (H * W // 8) + 60 * 4)
+    assert b.nbytes / b.float_nbytes <= 0.17
+    c = FrameStore(H, W, F, gated=True, object_loss=True)
+    assert c.nbytes / c.float_nbytes <= 0.17
+
+
+class _Opt:
+    capturable = True
+    param_groups = []
+
+
+def test_step_refuses_a_foreign_layout_double_buffering_and_calls_without_a_store():
+    from egogaussian_amd.frames import FrameStore
+    from egogaussian_amd.graph import GraphedTrainStep
+    bg = torch.zeros(3)
+    store = FrameStore(4, 4, 2, gated=True)
+    for kw in (dict(), dict(gated=True, dynamic=True), dict(gated=True, object_loss=dict(lambda_image=1.0))):
+        with pytest.raises(ValueError, match="layout"):
+            GraphedTrainStep(None, _Opt(), bg, frame_store=store, **kw)
+    with pytest.raises(ValueError, match="double_buffer"):
+        GraphedTrainStep(None, _Opt(), bg, gated=True, frame_store=store, double_buffer=True)
+    with pytest.raises(ValueError, match="ring_capacity"):
+        GraphedTrainStep(None, _Opt(), bg, gated=True, frame_store=store, steps_per_replay=4, ring_capacity=2)
+    step = GraphedTrainStep(None, _Opt(), bg, gated=True, frame_store=store, steps_per_replay=2)
+    assert step.frame_store is store and step.steps_per_replay == 2
+    with pytest.raises(ValueError):
+        step.set_schedule([0, 1])                                         # before capture() there is no ring
+    plain = GraphedTrainStep(None, _Opt(), bg, gated=True)
+    assert plain.frame_store is None
+    with pytest.raises(ValueError, match="frame_store"):
+        plain.set_schedule([0])
+    with pytest.raises(ValueError):
+        plain()
+    with pytest.raises(ValueError, match="frame_store"):
+        plain.capture(None, index=0)
+
+
+def test_sweeps_refuse_a_foreign_store_and_cpu_stores():
+    from egogaussian_amd.evaluate import EvalPass
+    from egogaussian_amd.frames import FrameStore
+    from egogaussian_amd.masks import MaskPass
+    from egogaussian_amd.scene_synth import make_camera
+    cam = make_camera(0, 4, 4)
+    bg = torch.zeros(3)
+    with pytest.raises(ValueError, match="layout"):
+        EvalPass(None, bg).run(FrameStore(4, 4, 2, label_phase=True), cam)
+    with pytest.raises(ValueError, match="layout"):
+        EvalPass(None, bg, dynamic=True).run(FrameStore(4, 4, 2, gated=True), cam)
+    with pytest.raises(ValueError, match="layout"):
+        MaskPass(None, bg).run(FrameStore(4, 4, 2, gated=True), cam)
+    with pytest.raises(ValueError):
+        MaskPass(None, bg).run(FrameStore(8, 4, 2, label_phase=True), cam)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        EvalPass(None, bg).run(FrameStore(4, 4, 2, gated=True), cam)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        MaskPass(None, bg).run(FrameStore(4, 4, 2, label_phase=True, gated=True), cam)

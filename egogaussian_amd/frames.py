@@ -21,7 +21,7 @@ import torch
 
 from . import lib as _lib
 from . import _hip
-from .graph import frame_layout, pack_camera
+from .graph import frame_layout, frame_views, pack_camera
 
 LAYOUT_OPTIONS = ("dynamic", "motion", "gated", "object_loss", "label_phase")
 DEFAULT_RING_CAPACITY = 4096
@@ -266,9 +266,7 @@ class FrameStore:
         """Frame i as the named float32 tensors a step is captured on: dict(frame, cam[35], gt[3,H,W], accum_R[3,3], accum_T[3,4], gate[H,W],
         obj_mask[H,W]) -- views of frame(i), None where the layout has none."""
         f = self.frame(i)
-        seg = lambda name, *shape: f[self.off[name][0]:self.off[name][1]].view(*shape) if name in self.off else None
-        return dict(frame=f, cam=seg("cam", 35), gt=seg("gt", 3, self.H, self.W), accum_R=seg("accum_R", 3, 3), accum_T=seg("accum_T", 3, 4),
-                    gate=seg("gate", self.H, self.W), obj_mask=seg("obj_mask", self.H, self.W))
+        return dict(frame_views(f, self.off, self.H, self.W), frame=f)
 
     # ---- reading: the kernel --------------------------------------------------------------------------------------------------------------------
     def decode(self, out, indices=None, ring=None):

@@ -30,7 +30,7 @@ import torch
 
 from . import _C
 from .fused import l1_ssim_loss, object_stage_loss
-from .renderer import render
+from .renderer import label_forward, render
 from .scene_synth import Pipe
 
 
@@ -44,15 +44,9 @@ def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_
     object_loss: an `obj_mask` segment of n_pix floats follows everything else (the other segments keep their offsets).
     label_phase: the frame of a label step -- no image segment (n_img is not read): camera[, gate], obj_mask."""
     up4 = lambda x: (x + 3) & ~3
-    if label_phase:
-        off = {"cam": (0, 35)}
-        end = up4(35)
-        if gated:
-            off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
-        off["obj_mask"] = (end, end + n_pix); end = up4(end + n_pix)
-        return off, end
-    off = {"gt": (0, n_img)}
-    end = up4(n_img)
+    off, end = {}, 0
+    if not label_phase:                                             # (the label frame has no "gt" key at all: FrameStore tests `name in off`)
+        off["gt"] = (0, n_img); end = up4(n_img)
     off["cam"] = (end, end + 35); end = up4(end + 35)
     if dynamic:
         off["accum_R"] = (end, end + 9); end = up4(end + 9)
@@ -60,9 +54,31 @@ def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_
         off["accum_T"] = (end, end + 12); end = up4(end + 12)      # the object's accumulated pose as A12 = [A | b], row-major 3x4
     if gated:
         off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
-    if object_loss:
+    if object_loss or label_phase:
         off["obj_mask"] = (end, end + n_pix); end = up4(end + n_pix)
     return off, end
+
+
+def frame_views(frame, off, H, W):
+    """The named views of ONE packed frame (a flat float32 tensor of the layout `off`): dict(gt [3,H,W], cam [35] -- the storage of a
+    _StaticCamera --, accum_R [3,3], accum_T [3,4], gate [H,W], obj_mask [H,W]); None where the layout has no such segment."""
+    seg = lambda name, *shape: frame[off[name][0]:off[name][1]].view(*shape) if name in off else None
+    return dict(gt=seg("gt", 3, H, W), cam=seg("cam", 35), accum_R=seg("accum_R", 3, 3), accum_T=seg("accum_T", 3, 4),
+                gate=seg("gate", H, W), obj_mask=seg("obj_mask", H, W))
+
+
+def dynamic_kwargs(f, which_object, pose=None):
+    """render()'s keywords of the `fine_all` call shape from the static views `f` of a frame (frame_views): rot_cov with the frame's accum_R
+    and, where the frame carries an accum_T, the object placed by it inside the rasterizer -- with `pose`, a trainable pose on top."""
+    kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=which_object, during_training=False)
+    if f["accum_T"] is not None:
+        from .motion import ComposedMotion, ObjectMotion
+        if pose is not None:
+            # composed INSIDE the capture from the static buffers and the two parameters: autograd carries dL/dA12, dL/dM9 back to them
+            kw["object_motion"] = ObjectMotion(f["accum_T"], pose, f["accum_R"])
+        else:
+            kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
+    return kw
 
 
 def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
@@ -129,6 +145,45 @@ def end_capture(graph):
     finally:
         if _gc_was_enabled.pop():
             gc.enable()
+
+
+def record_graph(body, side, dev):
+    """Records body() -- without executing it -- into a new CUDAGraph on the side stream `side` -> (graph, what body returned).
+    capture_begin / capture_end directly (begin_capture): the torch.cuda.graph context manager also runs gc.collect() and
+    torch.cuda.empty_cache() (3 ms at 500k Gaussians), which a trainer that re-captures after every densification pays each time."""
+    graph = torch.cuda.CUDAGraph()
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        begin_capture(graph)
+        try:
+            out = body()
+        finally:
+            end_capture(graph)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    return graph, out
+
+
+def warm_up(calls, side, dev):
+    """Runs every callable of `calls` eagerly on the side stream `side` (the stream the capture will use) -> the largest instance count
+    (`_C.stats["num_rendered"]`) any of them left.  Eager calls set the capacity hint, the allocator pools and the lazy state."""
+    r_seen = 0
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for call in calls:
+            call()
+            r_seen = max(r_seen, _C.stats["num_rendered"])
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    return r_seen
+
+
+def capture_capacity(r_seen, margin, dev, floor=0, capacity=None):
+    """The instance capacity to capture with, made the library's hint: `margin` x the largest count the warm-up saw, at least what the
+    library holds already and `floor`; `capacity` overrides the rule, as is."""
+    cap = max(int(r_seen * margin), _C.stats["capacity"], floor) if capacity is None else max(int(capacity), 1)
+    _C.set_capacity_hint(cap, dev)
+    return cap
 
 
 class _StaticCamera:
@@ -313,20 +368,8 @@ class GraphedTrainStep:
             self._entropy_weight_dev.fill_(self._entropy_weight_host)
             self._entropy_weight_pushed = self._entropy_weight_host
 
-    def _dynamic_kwargs(self, f):
-        kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=self.which_object, during_training=False)
-        if self.motion:
-            from .motion import ComposedMotion, ObjectMotion
-            if self.pose is not None:
-                # composed INSIDE the capture from the static buffers and the two parameters: autograd carries dL/dA12, dL/dM9 back to them
-                kw["object_motion"] = ObjectMotion(f["accum_T"], self.pose, f["accum_R"])
-            else:
-                kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
-        return kw
-
     def _label_body(self, k=0):
         """One iteration of the label phase on static frame k: no autograd, the library's calls in order."""
-        import math
         from . import lib as _lib
         from .optim import _touched
         f, pc, opt, group = self._slots[k], self.pc, self.opt, self._label_group
@@ -335,19 +378,8 @@ class GraphedTrainStep:
         dev = p.device
         capturing = torch.cuda.is_current_stream_capturing()
         with torch.no_grad():
-            raw = pc.get_raw_parameters() if getattr(pc, "get_raw_parameters", None) is not None else None
-            if raw is not None:
-                scales, rotations, opacity = raw
-                act = _C.ACT_RAW_PARAMETERS | _C.ACT_SCALAR_COLOR
-            else:
-                scales, rotations, opacity = pc.get_scaling, pc.get_rotation, pc.get_opacity
-                act = _C.ACT_SCALAR_COLOR
-            e = torch.empty(0, device=dev)
             H, W = int(cam.image_height), int(cam.image_width)
-            R, color, _, _, radii, geom, binning, img = _C.rasterize_gaussians(
-                self.bg, pc.get_xyz.detach(), p.detach().view(-1), opacity.detach(), scales.detach(), rotations.detach(), 1.0, e,
-                cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), H, W, e,
-                pc.active_sh_degree, cam.camera_center, False, False, act, None, getattr(pc, "active_count", None), self.guard, None, True, None)
+            R, color, radii, geom, binning, img = label_forward(cam, pc, p, self.bg, guard=self.guard)
             m, v, step, lr_t = opt._capturable_state(p, group)
             coef = opt._coef.get(dev)
             if coef is None:
@@ -367,76 +399,12 @@ class GraphedTrainStep:
         self._label_keep = (keep, m, v, step, lr_t, coef, geom, binning, img)
         return loss, {"render": color, "radii": radii, "label_grad": dl}
 
-    def _capture_label(self, cam, obj_mask, gate, warmup, capacity_margin, capacity):
-        """capture() of a label step: the static frame holds camera[, gate], obj_mask (frame_layout(label_phase=True))."""
-        dev = self._label_group["params"][0].device
-        if not isinstance(cam, _StaticCamera):
-            H, W = int(cam.image_height), int(cam.image_width)
-            off, size = frame_layout(0, H * W, gated=self.gated, label_phase=True)
-            self._frames = torch.zeros((self.steps_per_replay, size), device=dev, dtype=torch.float32)
-            self._slots = []
-            for k in range(self.steps_per_replay):
-                fr = self._frames[k]
-                slot = {"gt": None, "accum_R": None, "accum_T": None, "gate": None}
-                slot["cam"] = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
-                slot["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(H, W)
-                if obj_mask is not None:
-                    slot["obj_mask"].copy_(obj_mask.to(dev, torch.float32).reshape(H, W))
-                if self.gated:
-                    slot["gate"] = fr[off["gate"][0]:off["gate"][1]].view(H, W)
-                    slot["gate"].copy_(torch.ones((H, W), device=dev) if gate is None else gate.reshape(H, W))
-                self._slots.append(slot)
-            self._frame = self._frames[0]
-            first = self._slots[0]
-            self.gt, self.cam, self.accum_R, self.accum_T, self.gate, self.obj_mask = None, first["cam"], None, None, first["gate"], first["obj_mask"]
-        self._one = torch.ones((), device=dev)
-        if getattr(self, "loss_sum", None) is None:
-            self.loss_sum = torch.zeros((), device=dev)
-        self.guard = _C.StepGuard(dev)
-        self.opt.guard = self.guard
-        self.opt.sync_lr()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        r_seen = 0
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):                          # eager: real label steps; they set the capacity hint and the lazy state
-                self._label_body()
-                r_seen = max(r_seen, _C.stats["num_rendered"])
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.capacity = max(int(r_seen * capacity_margin), _C.stats["capacity"], getattr(self, "_min_capacity", 0))
-        if capacity is not None:
-            self.capacity = max(int(capacity), 1)
-        _C.set_capacity_hint(self.capacity, dev)
-        self.P = self.pc.get_xyz.shape[0]
-        self._model_version = getattr(self.pc, "model_version", 0)
-        self.graph = torch.cuda.CUDAGraph()
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            begin_capture(self.graph)
-            try:
-                self._decode_frames()
-                self.losses, self.label_grads, keeps = [], [], []
-                for k in range(self.steps_per_replay):
-                    self.loss, out = self._label_body(k)
-                    self.losses.append(self.loss); self.label_grads.append(out["label_grad"]); keeps.append(self._label_keep)
-                self._label_keeps = keeps
-                self.image, self.radii, self.label_grad = out["render"], out["radii"], out["label_grad"]
-                self.visibility_filter = self.viewspace_grad = None
-            finally:
-                end_capture(self.graph)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self._sets = None
-        self.guard.running_max.zero_(); self.guard.overflow.zero_()
-        return self
-
     def _body(self, k=0):
         """One training iteration on static frame k."""
         f = self._slots[k]
         kw = dict(self.render_kwargs)
         if self.dynamic:
-            kw.update(self._dynamic_kwargs(f))
+            kw.update(dynamic_kwargs(f, self.which_object, self.pose))
         if self.entropy_reg:
             kw["opacity_entropy"] = self._entropy_weight_dev         # the device scalar itself: the kernels read it at every replay
         out = render(f["cam"], self.pc, self.pipe, self.bg, fused_densify_stats=self.densify_stats, guard=self.guard,
@@ -453,8 +421,9 @@ class GraphedTrainStep:
         self.opt.step()                                              # whatever the backward did not step itself (fuse_optimizer)
         return loss.detach(), out
 
-    def _frame_layout(self, gt):
-        return frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], self.dynamic, self.gated, self.motion, self.object_loss is not None)
+    def _layout(self, H, W):
+        return frame_layout(0 if self.label_phase else 3 * H * W, H * W, self.dynamic, self.gated, self.motion, self.object_loss is not None,
+                            self.label_phase)
 
     def _decode_frames(self):
         """frame_store=: the first launch of the captured graph -- every static frame from the store, by the ring; the cursor advances on the device."""
@@ -473,14 +442,54 @@ class GraphedTrainStep:
         self._ring_set = False
         return parts
 
+    def _make_slots(self, frames, cams):
+        """The static inputs of the captured iterations: per row k of `frames` its named views (frame_views), the camera segment as a
+        _StaticCamera filled from cams[k]."""
+        H, W = int(cams[0].image_height), int(cams[0].image_width)
+        off, _ = self._layout(H, W)
+        slots = []
+        for fr, cam in zip(frames, cams):
+            slot = frame_views(fr, off, H, W)
+            slot["cam"] = _StaticCamera(cam, storage=slot["cam"])
+            slots.append(slot)
+        return slots
+
+    def _record(self):
+        """The body of the captured graph on the current slots: the decode of a frame store, then `steps_per_replay` iterations ->
+        what a replay leaves behind, under the attribute names it is published by."""
+        self._decode_frames()
+        losses, label_grads, keeps = [], [], []
+        for k in range(self.steps_per_replay):
+            if self.label_phase:
+                loss, out = self._label_body(k)
+                label_grads.append(out["label_grad"]); keeps.append(self._label_keep)
+            else:
+                if k:
+                    self.opt.zero_grad(set_to_none=True)             # (the next backward writes fresh gradients instead of accumulating)
+                loss, out = self._body(k)
+            losses.append(loss)
+        if self.label_phase:
+            return dict(loss=loss, losses=losses, image=out["render"], radii=out["radii"], label_grad=out["label_grad"], label_grads=label_grads,
+                        _label_keeps=keeps, visibility_filter=None, viewspace_grad=None)
+        return dict(loss=loss, losses=losses, image=out["render"].detach(), radii=out["radii"],
+                    entropy=out.get("opacity_entropy"),                  # (entropy_reg: written by every replay's backward)
+                    visibility_filter=out["visibility_filter"],          # follows every replay (a view of the rasterizer's saved state)
+                    viewspace_grad=out["viewspace_points"].grad)
+
+    def _publish(self, out):
+        for name, value in out.items():
+            setattr(self, name, value)
+
     def capture(self, cam, gt=None, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
                 obj_mask=None, index=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
         more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
         capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow).
-        obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask."""
-        if self.frame_store is not None and not isinstance(cam, _StaticCamera):
+        obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask.
+        A label step (label_phase=True) takes capture(cam, obj_mask=, gate=): its static frame holds camera[, gate], obj_mask."""
+        label, fresh = self.label_phase, not isinstance(cam, _StaticCamera)
+        if self.frame_store is not None and fresh:
             if (int(cam.image_height), int(cam.image_width)) != (self.frame_store.H, self.frame_store.W):
                 raise ValueError(f"GraphedTrainStep(frame_store=).capture: the camera is {cam.image_width}x{cam.image_height}, the store's frames "
                                  f"{self.frame_store.W}x{self.frame_store.H}")
@@ -488,45 +497,32 @@ class GraphedTrainStep:
             gt, accum_R, gate, accum_T, obj_mask = parts["gt"], parts["accum_R"], parts["gate"], parts["accum_T"], parts["obj_mask"]
         elif index is not None:
             raise ValueError("capture(index=) goes with GraphedTrainStep(frame_store=)")
-        if self.label_phase:
-            if obj_mask is None and not isinstance(cam, _StaticCamera):
-                raise ValueError("GraphedTrainStep(label_phase=True).capture(cam, obj_mask=...): the label step's frame is camera[, gate], obj_mask")
-            return self._capture_label(cam, obj_mask, gate, warmup, capacity_margin, capacity)
-        dev = gt.device
-        if self.object_loss is not None and obj_mask is not None:
-            obj_mask = obj_mask.to(dev, torch.float32).reshape(gt.shape[-2], gt.shape[-1])
-            gt = gt * obj_mask
-        if isinstance(cam, _StaticCamera):                           # recapture: keep the static buffers
-            if gt is not self.gt:
+        if label and obj_mask is None and fresh:
+            raise ValueError("GraphedTrainStep(label_phase=True).capture(cam, obj_mask=...): the label step's frame is camera[, gate], obj_mask")
+        dev = self._label_group["params"][0].device if label else gt.device
+        H, W = int(cam.image_height), int(cam.image_width)
+        if obj_mask is not None and (label or self.object_loss is not None):
+            obj_mask = obj_mask.to(dev, torch.float32).reshape(H, W)
+            if not label:
+                gt = gt * obj_mask
+        if not fresh:                                                # recapture: keep the static buffers
+            if not label and gt is not self.gt:
                 self.gt.copy_(gt)
         else:
-            off, size = self._frame_layout(gt)
-            # per captured iteration: image, camera[, accum_R][, gate] -- ONE copy target for all of them
-            self._frames = torch.empty((self.steps_per_replay, size), device=dev, dtype=torch.float32)
-            self._slots = []
-            for k in range(self.steps_per_replay):
-                fr = self._frames[k]
-                slot = {"gt": fr[off["gt"][0]:off["gt"][1]].view(gt.shape), "accum_R": None, "gate": None, "accum_T": None, "obj_mask": None}
-                slot["gt"].copy_(gt)
-                if self.object_loss is not None:
-                    slot["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(gt.shape[-2], gt.shape[-1])
-                    slot["obj_mask"].copy_(torch.ones(gt.shape[-2:], device=dev) if obj_mask is None else obj_mask)
-                slot["cam"] = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
-                if self.dynamic:
-                    slot["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
-                    slot["accum_R"].copy_(torch.eye(3, device=dev) if accum_R is None else accum_R)
-                if self.motion:
-                    slot["accum_T"] = fr[off["accum_T"][0]:off["accum_T"][1]].view(3, 4)
-                    slot["accum_T"].copy_(torch.eye(4, device=dev)[:3] if accum_T is None else accum_T.reshape(-1, 4)[:3])
-                if self.gated:
-                    slot["gate"] = fr[off["gate"][0]:off["gate"][1]].view(gt.shape[-2], gt.shape[-1])
-                    slot["gate"].copy_(torch.ones(gt.shape[-2:], device=dev) if gate is None else gate)
-                self._slots.append(slot)
+            # per captured iteration: image, camera[, accum_R][, accum_T][, gate][, obj_mask] -- ONE copy target for all of them
+            self._frames = torch.zeros((self.steps_per_replay, self._layout(H, W)[1]), device=dev, dtype=torch.float32)
+            self._slots = self._make_slots(self._frames, [cam] * self.steps_per_replay)
+            ones = lambda: torch.ones((H, W), device=dev)
+            given = (("gt", gt, None), ("accum_R", accum_R, lambda: torch.eye(3, device=dev)),
+                     ("accum_T", None if accum_T is None else accum_T.reshape(-1, 4)[:3], lambda: torch.eye(4, device=dev)[:3]),
+                     ("gate", gate.reshape(H, W) if gate is not None and gate.numel() == H * W else gate, ones), ("obj_mask", obj_mask, ones))
+            for slot in self._slots:
+                for name, value, default in given:
+                    if slot[name] is not None:
+                        slot[name].copy_(default() if value is None else value)
             self._frame = self._frames[0]
             first = self._slots[0]                                   # (the single-iteration names)
-            self.gt, self.cam, self.accum_R, self.gate = first["gt"], first["cam"], first["accum_R"], first["gate"]
-            self.accum_T = first["accum_T"]
-            self.obj_mask = first["obj_mask"]
+            self.gt, self.cam, self.accum_R, self.accum_T, self.gate, self.obj_mask = (first[n] for n in ("gt", "cam", "accum_R", "accum_T", "gate", "obj_mask"))
         self._one = torch.ones((), device=dev)
         if self.entropy_reg and self._entropy_weight_dev is None:
             self._entropy_weight_dev = torch.zeros((), device=dev)
@@ -537,96 +533,43 @@ class GraphedTrainStep:
             self.loss_terms = torch.zeros(3, device=dev)
         self.guard = _C.StepGuard(dev)
         self.opt.guard = self.guard                                  # the Adam launch of an overflowed frame does nothing
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            r_seen = 0
-            if capacity_cams:
-                kw = dict(self.render_kwargs)
-                if self.dynamic:
-                    kw.update(self._dynamic_kwargs(self._slots[0]))
+        if label:
+            self.opt.sync_lr()                                       # (the label body reads the device learning rate itself)
+        calls = []
+        if capacity_cams and not label:                              # (a label step sizes its capacity on `cam` alone)
+            kw = dict(self.render_kwargs)
+            if self.dynamic:
+                kw.update(dynamic_kwargs(self._slots[0], self.which_object, self.pose))
+
+            def look(c):
                 with torch.no_grad():
-                    for c in capacity_cams:
-                        render(c, self.pc, self.pipe, self.bg, **kw)
-                        r_seen = max(r_seen, _C.stats["num_rendered"])
-            for _ in range(max(1, warmup)):                          # eager: sets the capacity hint, allocator pools, lazy state
-                self.opt.zero_grad(set_to_none=True)
-                self._body()
-                r_seen = max(r_seen, _C.stats["num_rendered"])
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.capacity = max(int(r_seen * capacity_margin), _C.stats["capacity"], getattr(self, "_min_capacity", 0))
-        if capacity is not None:
-            self.capacity = max(int(capacity), 1)
-        _C.set_capacity_hint(self.capacity, dev)
+                    render(c, self.pc, self.pipe, self.bg, **kw)
+            calls += [lambda c=c: look(c) for c in capacity_cams]
+
+        def one_step():                                              # eager: a real step; sets the capacity hint, allocator pools, lazy state
+            if label:
+                return self._label_body()
+            self.opt.zero_grad(set_to_none=True)
+            self._body()
+        side = torch.cuda.Stream(device=dev)
+        r_seen = warm_up(calls + [one_step] * max(1, warmup), side, dev)
+        self.capacity = capture_capacity(r_seen, capacity_margin, dev, getattr(self, "_min_capacity", 0), capacity)
         self.P = self.pc.get_xyz.shape[0]
         self._model_version = getattr(self.pc, "model_version", 0)
-        self.opt.zero_grad(set_to_none=True)
-        self.graph = torch.cuda.CUDAGraph()
-        # capture_begin/capture_end directly: the torch.cuda.graph context manager also runs gc.collect() and
-        # torch.cuda.empty_cache() (3 ms at this size), which a trainer that re-captures after every densification pays each time
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            begin_capture(self.graph)
-            try:
-                self._decode_frames()
-                self.losses = []
-                for k in range(self.steps_per_replay):
-                    if k:
-                        self.opt.zero_grad(set_to_none=True)         # (the next backward writes fresh gradients instead of accumulating)
-                    self.loss, out = self._body(k)
-                    self.losses.append(self.loss)
-                self.image = out["render"].detach()
-                self.radii = out["radii"]
-                self.entropy = out.get("opacity_entropy")              # (entropy_reg: written by every replay's backward)
-                self.visibility_filter = out["visibility_filter"]      # follows every replay (a view of the rasterizer's saved state)
-                self.viewspace_grad = out["viewspace_points"].grad
-            finally:
-                end_capture(self.graph)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
+        if not label:
+            self.opt.zero_grad(set_to_none=True)
+        self.graph, out = record_graph(self._record, side, dev)
+        self._publish(out)
         self._sets = None
         if self.double_buffer:
             # the same iterations recorded once more on a second set of static frames; what the two captures share -- parameters,
             # optimizer state, guard words, loss_sum -- is shared by address
-            first = dict(graph=self.graph, frames=self._frames, slots=self._slots, loss=self.loss, losses=self.losses, image=self.image,
-                         entropy=self.entropy, radii=self.radii, visibility_filter=self.visibility_filter, viewspace_grad=self.viewspace_grad)
+            first = dict(graph=self.graph, frames=self._frames, slots=self._slots, out=out)
             frames2 = self._frames.clone()
-            off, _ = self._frame_layout(self.gt)
-            slots2 = []
-            for k in range(self.steps_per_replay):
-                fr, src = frames2[k], self._slots[k]
-                sl = {"gt": fr[off["gt"][0]:off["gt"][1]].view(src["gt"].shape), "accum_R": None, "gate": None, "accum_T": None, "obj_mask": None}
-                if self.object_loss is not None:
-                    sl["obj_mask"] = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(src["gt"].shape[-2], src["gt"].shape[-1])
-                sl["cam"] = _StaticCamera(src["cam"], storage=fr[off["cam"][0]:off["cam"][1]])
-                if self.dynamic:
-                    sl["accum_R"] = fr[off["accum_R"][0]:off["accum_R"][1]].view(3, 3)
-                if self.motion:
-                    sl["accum_T"] = fr[off["accum_T"][0]:off["accum_T"][1]].view(3, 4)
-                if self.gated:
-                    sl["gate"] = fr[off["gate"][0]:off["gate"][1]].view(src["gt"].shape[-2], src["gt"].shape[-1])
-                slots2.append(sl)
-            self._slots = slots2
+            self._slots = self._make_slots(frames2, [s["cam"] for s in first["slots"]])
             self.opt.zero_grad(set_to_none=True)
-            g2 = torch.cuda.CUDAGraph()
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                begin_capture(g2)
-                try:
-                    losses2 = []
-                    for k in range(self.steps_per_replay):
-                        if k:
-                            self.opt.zero_grad(set_to_none=True)
-                        loss2, out2 = self._body(k)
-                        losses2.append(loss2)
-                finally:
-                    end_capture(g2)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            second = dict(graph=g2, frames=frames2, slots=slots2, loss=loss2, losses=losses2, image=out2["render"].detach(), radii=out2["radii"],
-                          entropy=out2.get("opacity_entropy"),
-                          visibility_filter=out2["visibility_filter"], viewspace_grad=out2["viewspace_points"].grad)
+            g2, out2 = record_graph(self._record, side, dev)
+            second = dict(graph=g2, frames=frames2, slots=self._slots, out=out2)
             self._slots = first["slots"]
             self._sets = [first, second]
             self._copy_stream = torch.cuda.Stream(device=dev)
@@ -697,12 +640,18 @@ class GraphedTrainStep:
                 self.accum_T.copy_(accum_T.reshape(-1, 4)[:3], non_blocking=True)
             if self.gated and gate is not None:
                 self.gate.copy_(gate, non_blocking=True)
+        self._before_replay()
+        self.graph.replay()
+        return self._after_replay()
+
+    def _before_replay(self):
         if getattr(self.pc, "model_version", 0) != self._model_version:
             raise RuntimeError("GraphedTrainStep: the model reallocated its arrays (CapacityGaussians.grow) after this step was captured; "
                                "the captured launches point at freed memory -- call recapture() first")
         self.opt.sync_lr()                                           # a fill per group whose learning rate was edited since the last call
         self._sync_entropy_weight()
-        self.graph.replay()
+
+    def _after_replay(self):
         self._calls += 1
         if self.check_every > 0 and self._calls % self.check_every == 0:
             self.check()
@@ -750,22 +699,13 @@ class GraphedTrainStep:
                 st["frames"].copy_(frames.view(st["frames"].shape), non_blocking=True)
                 frames.record_stream(self._copy_stream)
             self._copied[b].record(self._copy_stream)
-        if getattr(self.pc, "model_version", 0) != self._model_version:
-            raise RuntimeError("GraphedTrainStep: the model reallocated its arrays (CapacityGaussians.grow) after this step was captured; "
-                               "the captured launches point at freed memory -- call recapture() first")
-        self.opt.sync_lr()
-        self._sync_entropy_weight()
+        self._before_replay()
         main.wait_event(self._copied[b])
         st["graph"].replay()
         self._done[b].record(main)
         self._used[b] = True
-        self.loss, self.losses, self.image, self.radii = st["loss"], st["losses"], st["image"], st["radii"]
-        self.entropy = st["entropy"]
-        self.visibility_filter, self.viewspace_grad = st["visibility_filter"], st["viewspace_grad"]
-        self._calls += 1
-        if self.check_every > 0 and self._calls % self.check_every == 0:
-            self.check()
-        return self.loss
+        self._publish(st["out"])
+        return self._after_replay()
 
     def check(self, capacity_margin=1.25):
         """Reads the running maximum of the instance count (synchronises).  If a replayed frame was clipped -- its parameter

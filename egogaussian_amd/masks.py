@@ -16,15 +16,14 @@ graph.pack_frame frame.  losses.label_mask / losses.interaction_gate are the tor
 Writing the masks to image files and copying them into a dataset is the caller's: `masks` stays on the device (0 / 255, what the PNG holds).
 """
 import copy
-import math
 
 import numpy as np
 import torch
 
-from . import _C
 from . import fused
-from .frames import FrameStore
-from .graph import _StaticCamera, begin_capture, end_capture, frame_layout
+from .graph import frame_layout
+from .renderer import label_forward
+from .sweep import CapturedSweep
 
 
 def decode_rows(rows):
@@ -37,103 +36,51 @@ def decode_rows(rows):
     return dict(predicted=pred, target=tgt, intersection=inter, kept=r[:, 3].copy(), clipped=r[:, 4] != 0, instances=r[:, 5].copy(), iou=iou)
 
 
-class MaskPass:
+class MaskPass(CapturedSweep):
+    _what, _statement = "mask pass", "losses.label_mask"
+    _packed = "graph.pack_label_frame(cam, obj_mask[, gate])"
+    _replaced = ("predicted", "target", "intersection", "kept", "iou")
+
     def __init__(self, pc, bg, graphed=True, threshold=0.5):
         """pc: the model whose labels are rendered (a capacity.CapacityGaussians model is followed through its live row count); bg: the
         label render's background, float32[3].  graphed=False: the same calls, eagerly, frame by frame (no capture, no capacity to outgrow).
         threshold: a pixel is predicted object when the channel mean of its label render exceeds it (the reference: 0.5)."""
-        self.pc, self.bg = pc, bg
-        self.graphed, self.threshold = bool(graphed), float(threshold)
-        self.graph = None
-        self.guard = None
-        self.capacity = 0
-        self.host_reads = 0               # reads of result rows this object did (one per sweep; one more when frames were rendered again)
-        self._key = None
+        super().__init__(pc, bg, graphed)
+        self.threshold = float(threshold)
 
-    # ---- static inputs ------------------------------------------------------------------------------------------------------------
-    def _check_store(self, store, cam):
+    # ---- what the shared sweep asks for ----------------------------------------------------------------------------------------------
+    def _frame_layout(self, H, W, gated):
+        return frame_layout(0, H * W, gated=gated, label_phase=True)
+
+    def _check_store(self, store):
         if not store.layout["label_phase"]:
             raise ValueError(f"MaskPass: a store of layout {store.layout} does not hold graph.pack_label_frame frames (label_phase=True)")
-        if (store.H, store.W) != (int(cam.image_height), int(cam.image_width)):
-            raise ValueError(f"MaskPass: the store's frames are {store.W}x{store.H}, the camera {cam.image_width}x{cam.image_height}")
 
-    def _make_static(self, cam, numel, dev):
-        H, W = int(cam.image_height), int(cam.image_width)
-        for gated in (False, True):
-            off, size = frame_layout(0, H * W, gated=gated, label_phase=True)
-            if size == numel:
-                break
-        else:
-            raise ValueError(f"MaskPass: a frame of {numel} floats is not graph.pack_label_frame(cam, obj_mask[, gate]) of a {W}x{H} camera")
-        self._frame = torch.zeros(size, device=dev, dtype=torch.float32)
-        fr = self._frame
-        self._cam = _StaticCamera(cam, storage=fr[off["cam"][0]:off["cam"][1]])
-        self._target = fr[off["obj_mask"][0]:off["obj_mask"][1]].view(H, W)
-        self._gate = fr[off["gate"][0]:off["gate"][1]].view(H, W) if gated else None
+    def _set_static(self, views, H, W, dev):
+        self._target, self._gate = views["obj_mask"], views["gate"]
         self._mask8 = torch.zeros((H, W), dtype=torch.uint8, device=dev)
         self._shape = (H, W)
-        self._key = (numel, H, W, float(cam.FoVx), float(cam.FoVy), dev)
-        self.graph = None
 
     def _body(self, rows, cursor, guard):
-        """One frame on the static inputs: the label forward (GraphedTrainStep._label_body's call), then the mask kernel writing at `cursor`."""
-        pc, cam = self.pc, self._cam
+        """One frame on the static inputs: the label forward of GraphedTrainStep's label step, then the mask kernel writing at `cursor`."""
         with torch.no_grad():
-            raw = pc.get_raw_parameters() if getattr(pc, "get_raw_parameters", None) is not None else None
-            if raw is not None:
-                scales, rotations, opacity = raw
-                act = _C.ACT_RAW_PARAMETERS | _C.ACT_SCALAR_COLOR
-            else:
-                scales, rotations, opacity = pc.get_scaling, pc.get_rotation, pc.get_opacity
-                act = _C.ACT_SCALAR_COLOR
-            xyz = pc.get_xyz.detach()
-            e = torch.empty(0, device=xyz.device)
-            H, W = self._shape
-            _, color, _, _, _, geom, binning, img = _C.rasterize_gaussians(
-                self.bg, xyz, pc.get_label.detach().view(-1), opacity.detach(), scales.detach(), rotations.detach(), 1.0, e,
-                cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), H, W, e,
-                pc.active_sh_degree, cam.camera_center, False, False, act, None, getattr(pc, "active_count", None), guard, None, True, None)
+            _, color, _, geom, binning, img = label_forward(self._cam, self.pc, self.pc.get_label, self.bg, guard=guard)
             res = fused.label_mask(color, self.threshold, target=self._target, keep=self._gate, rows=rows, cursor=cursor,
                                    overflow=None if guard is None else guard.overflow, out=self._mask8)
         return (color, geom, binning, img), res
 
-    # ---- capture --------------------------------------------------------------------------------------------------------------------
-    def _capture(self, first_frame, n_rows, capacity, capacity_margin):
-        dev = self._frame.device
-        self.guard = _C.StepGuard(dev)
-        self._rows, self._cursor = fused.mask_rows(n_rows, dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._frame.copy_(first_frame)
-            self._body(None, None, None)                               # eager: sets the capacity hint, allocator pools, lazy state
-            r_seen = _C.stats["num_rendered"]
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.capacity = max(int(r_seen * capacity_margin), _C.stats["capacity"]) if capacity is None else max(int(capacity), 1)
-        _C.set_capacity_hint(self.capacity, dev)
-        self._model_version = getattr(self.pc, "model_version", 0)
-        self.graph = torch.cuda.CUDAGraph()
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            begin_capture(self.graph)
-            try:
-                self._captured = self._body(self._rows, self._cursor, self.guard)
-            finally:
-                end_capture(self.graph)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
+    def _new_rows(self, n, dev):
+        return fused.mask_rows(n, dev)
 
-    def recapture(self):
-        """Forget the captured graph (after the model reallocated its arrays): the next run() captures again."""
-        self.graph = None
+    def _decode(self, rows):
+        return decode_rows(rows)
 
-    def _read_rows(self, rows):
-        """THE device-to-host read of a sweep's results (tests wrap it to count)."""
-        self.host_reads += 1
-        return rows.cpu()
+    def _new_out(self, n, dev):
+        return torch.empty((n,) + self._shape, dtype=torch.uint8, device=dev)
 
-    # ---- the sweep ------------------------------------------------------------------------------------------------------------------
+    def _bytes(self, res):
+        return self._mask8
+
     def run(self, frames, cam, capacity=None, capacity_margin=1.25):
         """frames: packed frames of graph.pack_label_frame(cam, obj_mask[, gate=keep]) -- a list or an [F, frame] tensor; `gate` is
         keep = 1 - hand mask (frames packed without it count every pixel), the object mask is the target the prediction is counted against --,
@@ -145,56 +92,7 @@ class MaskPass:
         not; predicted, target, intersection, kept: int64[F], counted over the kept pixels; iou: float64[F] (1.0 where the union is empty);
         mean_iou; rerendered: indices of the frames rendered again; instances: int64[F], the captured forwards' instance counts (0 for eager
         frames))."""
-        store = frames if isinstance(frames, FrameStore) else None
-        if store is not None:
-            self._check_store(store, cam)
-            n, first = store.n_frames, store.frame(0)
-            ring = store.new_ring(n)
-            ring.set(range(n))                                          # the sweep's frames 0 .. n - 1: the decode walks them on the device
-            load = lambda i: store.decode(self._frame, ring=ring)       # (called once per frame, in order)
-            reload = lambda i: store.decode(self._frame, indices=[i])
-        else:
-            n = frames.shape[0] if torch.is_tensor(frames) else len(frames)
-            if n == 0:
-                raise ValueError("MaskPass.run: no frames")
-            first = frames[0]
-            load = reload = lambda i: self._frame.copy_(frames[i], non_blocking=True)      # the frame's every input: one copy
-        if not first.is_cuda:
-            raise RuntimeError(f"MaskPass: frames are on {first.device}: the mask pass has no CPU path (losses.label_mask is the torch statement)")
-        dev = first.device
-        key = (first.numel(), int(cam.image_height), int(cam.image_width), float(cam.FoVx), float(cam.FoVy), dev)
-        if self._key != key:
-            self._make_static(cam, first.numel(), dev)
-        masks = torch.empty((n,) + self._shape, dtype=torch.uint8, device=dev)
-        if self.graphed:
-            if self.graph is not None and getattr(self.pc, "model_version", 0) != self._model_version:
-                raise RuntimeError("MaskPass: the model reallocated its arrays (CapacityGaussians.grow) after this pass was captured; "
-                                   "the captured launches point at freed memory -- call recapture() first")
-            if self.graph is None or self._rows.shape[0] < n or (capacity is not None and int(capacity) != self.capacity):
-                self._capture(first, max(n, 64), capacity, capacity_margin)
-            rows, cursor = self._rows, self._cursor
-            rows.zero_(); cursor.zero_()
-            for i in range(n):
-                load(i)
-                self.graph.replay()
-                masks[i].copy_(self._mask8, non_blocking=True)
-        else:
-            rows, cursor = fused.mask_rows(n, dev)
-            for i in range(n):
-                load(i)
-                self._body(rows, cursor, None)
-                masks[i].copy_(self._mask8, non_blocking=True)
-        fig = decode_rows(self._read_rows(rows[:n]))
-        again = [int(i) for i in np.nonzero(fig["clipped"])[0]]
-        if again:
-            rows2, cursor2 = fused.mask_rows(len(again), dev)
-            for i in again:
-                reload(i)
-                self._body(rows2, cursor2, None)                           # eager: the forward grows its buffers by itself
-                masks[i].copy_(self._mask8, non_blocking=True)
-            fig2 = decode_rows(self._read_rows(rows2))
-            for k in ("predicted", "target", "intersection", "kept", "iou"):
-                fig[k][again] = fig2[k]
+        fig, again, masks = self._sweep(frames, cam, capacity, capacity_margin)
         return dict(masks=masks, predicted=fig["predicted"], target=fig["target"], intersection=fig["intersection"], kept=fig["kept"],
                     iou=fig["iou"], mean_iou=float(np.mean(fig["iou"])), rerendered=again, instances=fig["instances"])
 

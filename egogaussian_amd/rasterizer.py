@@ -168,6 +168,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grads[8] if split else None, None, None, None, None, None, None, None, g_A12, g_M, None)
 
 
+def scalar_label_forward(label, means3D, opacities, scales, rotations, raster_settings, activation_flags=0, active_count=None, guard=None):
+    """THE forward of the scalar-colour label render: `label` is float32[P], one value per Gaussian (EGS_ACT_SCALAR_COLOR); activation_flags:
+    what else the library has to apply (_C.ACT_RAW_PARAMETERS when scales, rotations and opacities are the stored parameters).  Colour only.
+    -> (num_rendered, label image [3,H,W], radii, geom, binning, img: the state egs_backward_label reads)."""
+    rs = raster_settings
+    empty = torch.empty(0, device=means3D.device, dtype=torch.float32)
+    num_rendered, color, _, _, radii, geom, binning, img = _C.rasterize_gaussians(
+        rs.bg, means3D, label, opacities, scales, rotations, rs.scale_modifier, empty, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+        rs.image_height, rs.image_width, empty, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, _C.ACT_SCALAR_COLOR | activation_flags, None,
+        active_count, guard, None, True, None)
+    return num_rendered, color, radii, geom, binning, img
+
+
 class _RasterizeLabel(torch.autograd.Function):
     """The label render with the label as ONE value per Gaussian (include/egs_raster.h EGS_ACT_SCALAR_COLOR, egs_backward_label): the preprocess
     kernel fills the record's three colour slots from it -- no [P,3] copy --, the backward is the scalar colours-only blend and returns dL/dlabel.
@@ -176,14 +189,10 @@ class _RasterizeLabel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, label, means3D, opacities, scales, rotations, raster_settings, active_count=None, guard=None):
         rs = raster_settings
-        empty = torch.empty(0, device=means3D.device, dtype=torch.float32)
         flat = label.detach().reshape(-1).float().contiguous()
         if flat.numel() != means3D.shape[0]:
             raise RuntimeError("get_render_label(scalar=True): the label holds one value per Gaussian")
-        num_rendered, color, _, _, radii, geom, binning, img = _C.rasterize_gaussians(
-            rs.bg, means3D, flat, opacities, scales, rotations, rs.scale_modifier, empty, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-            rs.image_height, rs.image_width, empty, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, _C.ACT_SCALAR_COLOR, None, active_count, guard,
-            None, True, None)
+        num_rendered, color, radii, geom, binning, img = scalar_label_forward(flat, means3D, opacities, scales, rotations, rs, 0, active_count, guard)
         ctx.raster_settings, ctx.num_rendered, ctx.guard, ctx.label_shape = rs, num_rendered, guard, tuple(label.shape)
         ctx.egs_label_node = True                   # fused.label_bce_loss(raster_lossgrad=True) recognises its input's grad_fn by this
         ctx.label_loss = None                       # (lib.LabelLoss, tensors it points to, (address, version) of the gradient tensor handed over)

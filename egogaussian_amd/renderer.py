@@ -197,6 +197,23 @@ def gaussians_to_label_rendervar(gaussians):
             "scales": gaussians.get_scaling.detach(), "means2D": _screenspace_leaf(xyz).detach()}      # (the reference: zeros_like(xyz) + 0, two launches; nothing reads the values)
 
 
+def label_forward(viewpoint_camera, pc, label, bg_color, guard=None):
+    """The scalar-colour label forward of a captured label step and of the mask sweep, outside autograd: `label` ([P] or [P,1]) as one value
+    per Gaussian, the model's scales, rotations and opacity as stored where it offers them (get_raw_parameters: the library activates them),
+    activated otherwise.  -> rasterizer.scalar_label_forward's tuple."""
+    from . import _C
+    from .rasterizer import scalar_label_forward
+    raw = pc.get_raw_parameters() if getattr(pc, "get_raw_parameters", None) is not None else None
+    if raw is not None:
+        scales, rotations, opacity = raw
+        act = _C.ACT_RAW_PARAMETERS
+    else:
+        scales, rotations, opacity = pc.get_scaling, pc.get_rotation, pc.get_opacity
+        act = 0
+    return scalar_label_forward(label.detach().view(-1), pc.get_xyz.detach(), opacity.detach(), scales.detach(), rotations.detach(),
+                                get_raster_settings(viewpoint_camera, pc, bg_color), act, getattr(pc, "active_count", None), guard)
+
+
 def get_render_label(viewpoint_camera, pc, bg_color, scalar=False):
     """Per-Gaussian scalar label rendered as a grey colour through a fresh rasterizer (object segmentation).
     scalar (extension; default: the reference's call): `pc.get_label` goes to the rasterizer as ONE value per Gaussian -- no [P,3] expansion,

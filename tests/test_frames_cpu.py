@@ -152,6 +152,62 @@ def test_frame_equals_pack_frame_bit_for_bit(layout, shape):
     assert (parts["gt"] is None) == bool(lay.get("label_phase")) and (parts["gate"] is None) == (not lay.get("gated"))
 
 
+# graph.frame_layout at 5 x 7 (35 pixels: every segment but accum_T ends off a 16-byte boundary) for every legal option set -- literal
+# numbers, taken from the function as it stood before its label branch was folded into the general one
+LAYOUT_TABLE_5x7 = [
+    (dict(), {"gt": (0, 105), "cam": (108, 143)}, 144),
+    (dict(object_loss=True), {"gt": (0, 105), "cam": (108, 143), "obj_mask": (144, 179)}, 180),
+    (dict(gated=True), {"gt": (0, 105), "cam": (108, 143), "gate": (144, 179)}, 180),
+    (dict(gated=True, object_loss=True), {"gt": (0, 105), "cam": (108, 143), "gate": (144, 179), "obj_mask": (180, 215)}, 216),
+    (dict(dynamic=True), {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153)}, 156),
+    (dict(dynamic=True, object_loss=True), {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "obj_mask": (156, 191)}, 192),
+    (dict(dynamic=True, gated=True), {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "gate": (156, 191)}, 192),
+    (dict(dynamic=True, gated=True, object_loss=True),
+     {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "gate": (156, 191), "obj_mask": (192, 227)}, 228),
+    (dict(dynamic=True, motion=True), {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "accum_T": (156, 168)}, 168),
+    (dict(dynamic=True, motion=True, object_loss=True),
+     {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "accum_T": (156, 168), "obj_mask": (168, 203)}, 204),
+    (dict(dynamic=True, motion=True, gated=True),
+     {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "accum_T": (156, 168), "gate": (168, 203)}, 204),
+    (dict(dynamic=True, motion=True, gated=True, object_loss=True),
+     {"gt": (0, 105), "cam": (108, 143), "accum_R": (144, 153), "accum_T": (156, 168), "gate": (168, 203), "obj_mask": (204, 239)}, 240),
+    (dict(label_phase=True), {"cam": (0, 35), "obj_mask": (36, 71)}, 72),
+    (dict(label_phase=True, gated=True), {"cam": (0, 35), "gate": (36, 71), "obj_mask": (72, 107)}, 108),
+]
+
+
+@pytest.mark.parametrize("case", LAYOUT_TABLE_5x7, ids=lambda c: "-".join(sorted(c[0])) or "plain")
+def test_layout_table_and_frame_views_at_5x7(case):
+    """Every legal option set: the offsets and the size are the table's; frame_views over the packed frame gives back what was packed
+    (gt * obj_mask with an object mask), bit for bit, None for what the layout lacks; FrameStore.parts(i) gives the same views."""
+    from egogaussian_amd.frames import FrameStore
+    from egogaussian_amd.graph import frame_layout, frame_views, pack_camera
+    lay, want_off, want_size = case
+    H, W = 5, 7
+    off, size = frame_layout(0 if lay.get("label_phase") else 3 * H * W, H * W, **lay)
+    assert off == want_off and list(off) == list(want_off) and size == want_size
+    cam, kw, packed = frame_inputs(H, W, lay, seed=57)
+    assert packed.numel() == size
+    views = frame_views(packed, off, H, W)
+    assert set(views) == {"gt", "cam", "accum_R", "accum_T", "gate", "obj_mask"}
+    want = {"cam": pack_camera(cam), "gt": None, "accum_R": kw.get("accum_R"), "accum_T": kw["accum_T"][:3] if "accum_T" in kw else None,
+            "gate": kw.get("gate"), "obj_mask": kw.get("obj_mask")}
+    if "gt" in kw:
+        want["gt"] = kw["gt"].float() / 255.0 * (kw["obj_mask"] if lay.get("object_loss") else 1.0)
+    shapes = {"cam": (35,), "gt": (3, H, W), "accum_R": (3, 3), "accum_T": (3, 4), "gate": (H, W), "obj_mask": (H, W)}
+    store = FrameStore(H, W, 2, **lay)
+    store.put(1, cam, **kw)
+    parts = store.parts(1)
+    assert set(parts) == set(views) | {"frame"} and bits_equal(parts["frame"], packed)
+    for name, w in want.items():
+        if w is None:
+            assert views[name] is None and parts[name] is None and name not in off, name
+            continue
+        assert tuple(views[name].shape) == shapes[name] and bits_equal(views[name], w.float()), name
+        assert views[name].data_ptr() == packed.data_ptr() + 4 * off[name][0], name      # a view of the frame, not a copy
+        assert bits_equal(parts[name], views[name]) and parts[name].data_ptr() == parts["frame"].data_ptr() + 4 * off[name][0], name
+
+
 def test_all_256_codes_decode_to_the_quotient_and_the_reciprocal_product_does_not():
     from egogaussian_amd.frames import FrameStore, byte_table
     from egogaussian_amd.scene_synth import make_camera

@@ -656,12 +656,79 @@ def object_rotation_inside_the_rasterizer_matches_the_covariance_path(camera=Non
     assert pc.get_raw_parameters_rotated(R.clone().requires_grad_(True), 1, False) is None
 
 
+def _double_buffered_with_every_frame_segment():
+    """GraphedTrainStep(dynamic=True, motion=True, gated=True, object_loss=..., steps_per_replay=2) single- and double-buffered on the
+    one-wave scene of tests/test_gpu_frames.py (_grid_scene at 37 x 53: every Gaussian inside one 8x8 quadrant, so no order of float atomics
+    can vary and two runs of ONE step are bit-identical -- asserted first; equality between two steps is then a statement about how they
+    are fed).  Six frames with an image, accum_R, accum_T, gate and object mask of their own -- the accum_T are translations of a tenth of
+    a pixel or less per frame index, which keep every Gaussian inside its quadrant --, four calls of two frames, so each set of buffers is
+    filled twice.  Every parameter, both Adam moments, the step counts, loss_sum, the loss terms and every call's losses are bit-identical
+    to the single-buffered step's."""
+    from tests.test_gpu_frames import _grid_scene
+    from egogaussian_amd.scene_synth import SynthGaussians
+    from egogaussian_amd.optim import FusedAdam
+    from egogaussian_amd.graph import GraphedTrainStep, pack_frame
+    H, W = 37, 53
+    s = _grid_scene(H, W)
+    w_obj = dict(lambda_image=0.7, lambda_l1_alpha=0.3, lambda_l2_alpha=0.2)
+    Ts = []
+    for k in range(6):
+        T = torch.eye(4, device=DEV)
+        T[:3, 3] = torch.tensor([0.004 * k, -0.003 * k, 0.002 * k], device=DEV)      # (a pixel at the nearest depth, 3, spans 0.065)
+        Ts.append(T)
+    gts = [(g8.cpu().float() / 255.0).to(DEV) for g8 in s["gt8"]]
+    frames = [pack_frame(s["cam"], gts[k], s["Rs"][k], s["gates"][k], Ts[k], obj_mask=s["masks"][k]) for k in range(6)]
+    for k in range(1, 6):                                                # the segments do differ from frame to frame
+        assert not torch.equal(frames[k][3 * H * W:], frames[0][3 * H * W:]) and not torch.equal(Ts[k], Ts[k - 1])
+    calls = [(3, 0), (5, 1), (4, 2), (0, 5)]
+
+    def run(double_buffer):
+        pc = SynthGaussians(s["student"], device=DEV)
+        pc._is_object = s["is_object"]
+        opt = pc.training_setup(FusedAdam, capturable=True)
+        step = GraphedTrainStep(pc, opt, s["bg"], 0.2, dynamic=True, motion=True, gated=True, object_loss=w_obj, steps_per_replay=2,
+                                double_buffer=double_buffer).capture(s["cam"], gts[0], warmup=1, capacity_margin=2.0, accum_R=s["Rs"][0], gate=s["gates"][0],
+                                                                     accum_T=Ts[0], obj_mask=s["masks"][0])
+        state = {}
+        for c, (i, j) in enumerate(calls):
+            step(torch.stack([frames[i], frames[j]]))
+            state[f"losses of call {c}"] = torch.stack([l.detach().clone() for l in step.losses])
+            state[f"terms of call {c}"] = step.loss_terms.clone()
+        torch.cuda.synchronize()
+        assert step.ok()
+        state["loss_sum"] = step.loss_sum.detach().clone().reshape(1)
+        for a in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
+            p = getattr(pc, a)
+            state[a] = p.detach().clone()
+            for key in ("exp_avg", "exp_avg_sq", "step"):
+                if p in opt.state and key in opt.state[p]:
+                    state[a + "." + key] = opt.state[p][key].detach().clone().reshape(-1).float()
+        return state
+
+    differing = lambda a, b: {k: int((a[k].contiguous().view(torch.int32) != b[k].contiguous().view(torch.int32)).sum()) for k in a if not torch.equal(a[k], b[k])}
+    single, again = run(False), run(False)
+    assert set(single) == set(again) and not differing(single, again), "two runs of the single-buffered step differ: the scene does not make the step deterministic"
+    assert float(single["_xyz.step"][0]) == 1 + 2 * len(calls) and float(single["_opacity.exp_avg"].abs().max()) > 0
+    fresh = torch.tensor(s["student"]["opacity_logit"]).reshape(-1)
+    assert not torch.equal(single["_opacity"].cpu().reshape(-1), fresh), "nothing was trained"
+    assert len({float(single[f"losses of call {c}"][0]) for c in range(len(calls))}) == len(calls)
+    double = run(True)
+    diff = differing(single, double)
+    print("arrays compared", len(single), "differing", diff)
+    assert set(single) == set(double) and not diff, diff
+
+
 @pytest.mark.gpu
-def test_double_buffered_graph_step_matches_single_buffered():
+@pytest.mark.parametrize("case", ["image-only", "every-frame-segment"])
+def test_double_buffered_graph_step_matches_single_buffered(case):
     """GraphedTrainStep(double_buffer=True): two captures of the same iterations on two sets of static frames, alternated, the copy of
     the next call's frames on a side stream.  Ten calls of three iterations each must leave the parameters where the single-buffered
     step leaves them (same frames in the same order; only the accumulation order of the atomics differs), count every step, and
-    report each call's losses."""
+    report each call's losses.
+    every-frame-segment: the step whose frames carry accum_R, accum_T, gate and object mask, on a scene without that freedom: bit for bit
+    (_double_buffered_with_every_frame_segment)."""
+    if case == "every-frame-segment":
+        return _double_buffered_with_every_frame_segment()
     import math
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render

@@ -397,6 +397,42 @@ def test_captured_label_step():
     assert all(torch.equal(a, b) for a, b in zip(before, _label_state(pc, opt))), "a clipped frame takes no step and counts none"
 
 
+def test_captured_label_step_recaptures_after_an_overflow():
+    """check() of a label step whose replayed frame outgrew the (forced-small) capacity: it re-captures once with room, on the SAME static
+    buffers, and the step works afterwards -- a further replay moves the label and nothing else."""
+    from egogaussian_amd.graph import GraphedTrainStep
+    dev = _dev()
+    bg = torch.zeros(3, device=dev)
+    frames = _frames(dev, 3)
+    pc, opt = _label_model(dev)
+    cap = dict(obj_mask=frames[0][1], gate=frames[0][2], warmup=1)
+    sized = GraphedTrainStep(pc, opt, bg, label_phase=True, gated=True).capture(frames[0][0], capacity_margin=2.0, **cap)
+    sized(frames[1][0], obj_mask=frames[1][1], gate=frames[1][2])
+    torch.cuda.synchronize()
+    count = sized.last_instance_count()
+    small = max(count // 2, 1)
+    step = GraphedTrainStep(pc, opt, bg, label_phase=True, gated=True).capture(frames[0][0], capacity=small, **cap)
+    ptrs = (step.obj_mask.data_ptr(), step.gate.data_ptr(), step.cam.packed.data_ptr())
+    step(frames[1][0], obj_mask=frames[1][1], gate=frames[1][2])
+    torch.cuda.synchronize()
+    assert step.capacity == small and step.last_frame_overflowed() and not step.ok()
+    assert step.check() is False
+    print(f"\ninstances {count}, capacity {small} -> {step.capacity}")
+    assert step.recaptures == 1 and step.skipped_frames_seen == 1 and step.capacity > small and step.capacity >= count and step.ok()
+    assert (step.obj_mask.data_ptr(), step.gate.data_ptr(), step.cam.packed.data_ptr()) == ptrs
+    assert torch.equal(step.obj_mask, frames[1][1]) and torch.equal(step.gate, frames[1][2])      # the buffers kept their contents too
+    assert step.visibility_filter is None and step.viewspace_grad is None and len(step.label_grads) == len(step._label_keeps) == 1
+    others = {a: getattr(pc, a).detach().clone() for a in OTHERS}
+    p0, _, _, s0 = _label_state(pc, opt)
+    step(frames[2][0], obj_mask=frames[2][1], gate=frames[2][2])
+    torch.cuda.synchronize()
+    p1, _, _, s1 = _label_state(pc, opt)
+    assert step.ok() and step.check() is True and step.recaptures == 1 and not step.last_frame_overflowed()
+    assert float(s1) == float(s0) + 1.0 and not torch.equal(p1, p0) and float(step.label_grad.abs().max()) > 0
+    for a in OTHERS:
+        assert torch.equal(getattr(pc, a).detach(), others[a]) and getattr(pc, a).grad is None, f"{a} moved"
+
+
 def test_captured_label_step_two_iterations_per_replay():
     from egogaussian_amd.graph import GraphedTrainStep, pack_label_frame
     dev = _dev()

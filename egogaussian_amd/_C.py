@@ -249,7 +249,8 @@ def _object_motion_struct(object_motion, dev, P, want_grad=False):
     covariances are not turned."""
     if object_motion is None:
         return None, (), None
-    A12, moved, M, sel, mult = object_motion
+    A12, moved, M, sel, mult = object_motion[:5]
+    grad_out = object_motion[5] if len(object_motion) > 5 else None      # a caller-owned float32[21] the pose gradient is written to
     st = _lib.ObjectMotion()
     keep = []
     if M is not None:
@@ -266,7 +267,9 @@ def _object_motion_struct(object_motion, dev, P, want_grad=False):
         st.moved = moved.data_ptr(); keep.append(moved)
     grad = None
     if want_grad and P != 0:
-        grad = torch.empty((21,), device=dev, dtype=torch.float32)
+        if grad_out is not None and (grad_out.dtype != torch.float32 or grad_out.numel() != 21 or grad_out.device != dev or not grad_out.is_contiguous()):
+            raise RuntimeError("object_motion: the pose gradient's buffer is a contiguous float32[21] on the rasterizer's device")
+        grad = torch.empty((21,), device=dev, dtype=torch.float32) if grad_out is None else grad_out
         scratch = torch.empty((max(int(_lib.load().egs_object_motion_scratch_bytes(int(P))), 4),), device=dev, dtype=torch.uint8)
         st.grad, st.scratch = grad.data_ptr(), scratch.data_ptr(); keep.append(scratch)
     return st, tuple(keep), grad
@@ -524,7 +527,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             rot_st, _rot_keep, pose_grad = _object_motion_struct(object_motion, dev, P, motion_grad)
             activation_flags = int(activation_flags) | _lib.ACT_OBJECT_MOTION
             if motion_grad and P == 0:
-                pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32)
+                pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32) if len(object_motion) <= 5 else object_motion[5].zero_()
         else:
             rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
         if P != 0 and opacity_entropy is not None:

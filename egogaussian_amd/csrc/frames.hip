@@ -9,8 +9,8 @@
 //                                          (absent for the label layout; pre-multiplied by the object mask for the object-loss layout)
 //   bits   uint32 [F][n_planes][plane_words]   one bit per pixel, pixel p is bit p % 32 of word p / 32, gate first, then obj_mask;
 //                                          plane_words = ceil(H W / 32) rounded up to 4 WORDS (16 bytes); unused bits are 0
-//   small  float  [F][small_floats]        the frame's floats from the start of `cam` to the end of the last of cam / accum_R / accum_T,
-//                                          as they lie in the packed frame (36, 48 or 60 floats: a multiple of 4, so 16-byte rows)
+//   small  float  [F][small_floats]        the frame's floats from the start of `cam` to the end of the last of cam / accum_R / accum_T / pose_rows,
+//                                          as they lie in the packed frame (36, 48, 60 or -- with the pose_rows word -- 64 floats: a multiple of 4, so 16-byte rows)
 //   table  float  [256]                    byte -> float, filled by the host with uint8 / 255.0 (true division): byte * (1 / 255.f) is NOT
 //                                          that quotient at 126 of the 256 codes, so no reciprocal appears here.  Staged in LDS.
 // A packed frame is a sequence of segments, each starting on a 16-byte boundary and padded with zeros to the next one:
@@ -169,11 +169,12 @@ inline unsigned long long up4(unsigned long long x) { return (x + 3ull) & ~3ull;
 
 // the layout of graph.frame_layout for `flags`, and the store's strides
 int frame_layout_of(int height, int width, int flags, egs_frame_layout* L) {
-    if (height < 1 || width < 1 || !L || (flags & ~31)) return EGS_ERR_ARG;
+    if (height < 1 || width < 1 || !L || (flags & ~63)) return EGS_ERR_ARG;
     if ((size_t)height * (size_t)width >= ((size_t)1 << 31)) return EGS_ERR_RANGE;
     const bool dynamic = flags & EGS_FRAME_DYNAMIC, motion = flags & EGS_FRAME_MOTION, gated = flags & EGS_FRAME_GATED;
-    const bool object_loss = flags & EGS_FRAME_OBJECT_LOSS, label = flags & EGS_FRAME_LABEL_PHASE;
+    const bool object_loss = flags & EGS_FRAME_OBJECT_LOSS, label = flags & EGS_FRAME_LABEL_PHASE, pose_rows = flags & EGS_FRAME_POSE_ROWS;
     if (label && (dynamic || motion || object_loss)) return EGS_ERR_MODE;
+    if (pose_rows && !motion) return EGS_ERR_MODE;                           // the frame word of a pose sequence goes with a pose
     const unsigned long long n_pix = (unsigned long long)height * (unsigned long long)width;
     unsigned long long end = 0;
     L->image_floats = label ? 0 : 3 * n_pix;
@@ -182,6 +183,7 @@ int frame_layout_of(int height, int width, int flags, egs_frame_layout* L) {
     end = up4(end + 35);
     if (dynamic) end = up4(end + 9);
     if (motion) end = up4(end + 12);
+    if (pose_rows) end = up4(end + 4);
     L->small_floats = (int64_t)end - L->small_begin;
     L->gate_begin = -1; L->obj_mask_begin = -1;
     if (gated) { L->gate_begin = (int64_t)end; end = up4(end + n_pix); }

@@ -59,7 +59,7 @@ class EvalPass(CapturedSweep):
 
     def _check_store(self, store):
         lay = store.layout
-        if lay["label_phase"] or lay["object_loss"] or lay["dynamic"] != self.dynamic or lay["motion"] != self.motion:
+        if lay["label_phase"] or lay["object_loss"] or lay.get("pose_rows") or lay["dynamic"] != self.dynamic or lay["motion"] != self.motion:
             raise ValueError(f"EvalPass: a store of layout {lay} does not hold {self._packed} frames{self._options()}")
 
     def _set_static(self, views, H, W, dev):

@@ -6,7 +6,7 @@ one or two bits hold.  A FrameStore keeps F frames of one image size and one fra
 
     img    uint8 [F, image_stride]            the image bytes in the CHW order of `gt` (pre-multiplied by the object mask for object_loss)
     bits   int32 [F, n_planes, plane_words]   one bit per pixel and plane: gate, then obj_mask; pixel p is bit p % 32 of word p // 32
-    small  float32 [F, small_floats]          the camera block, accum_R and accum_T, untouched
+    small  float32 [F, small_floats]          the camera block, accum_R, accum_T and the pose_rows word (int32 bits), untouched
 
 (strides: include/egs_raster.h egs_frame_store_layout) and turns them back into packed frames two ways: `frame(i)`, written in torch on
 whatever device the store is on -- the DEFINITION of decoding, bit for bit what pack_frame gives for the original inputs -- and `decode`, the
@@ -21,9 +21,9 @@ import torch
 
 from . import lib as _lib
 from . import _hip
-from .graph import frame_layout, frame_views, pack_camera
+from .graph import frame_layout, frame_views, pack_camera, pose_word
 
-LAYOUT_OPTIONS = ("dynamic", "motion", "gated", "object_loss", "label_phase")
+LAYOUT_OPTIONS = ("dynamic", "motion", "gated", "object_loss", "label_phase", "pose_rows")
 DEFAULT_RING_CAPACITY = 4096
 
 
@@ -32,10 +32,10 @@ def byte_table():
     return torch.arange(256, dtype=torch.uint8).float() / 255.0
 
 
-def layout_flags(dynamic=False, motion=False, gated=False, object_loss=False, label_phase=False):
+def layout_flags(dynamic=False, motion=False, gated=False, object_loss=False, label_phase=False, pose_rows=False):
     """The EGS_FRAME_* word of a layout."""
     return (_lib.FRAME_DYNAMIC * bool(dynamic) | _lib.FRAME_MOTION * bool(motion) | _lib.FRAME_GATED * bool(gated)
-            | _lib.FRAME_OBJECT_LOSS * bool(object_loss) | _lib.FRAME_LABEL_PHASE * bool(label_phase))
+            | _lib.FRAME_OBJECT_LOSS * bool(object_loss) | _lib.FRAME_LABEL_PHASE * bool(label_phase) | _lib.FRAME_POSE_ROWS * bool(pose_rows))
 
 
 def _check_indices(indices, n_frames, what):
@@ -113,7 +113,7 @@ def _unpack_bits(w, n):
 
 class FrameStore:
     def __init__(self, H, W, n_frames, device="cpu", dynamic=False, motion=False, gated=False, object_loss=False, label_phase=False,
-                 ring_capacity=DEFAULT_RING_CAPACITY):
+                 ring_capacity=DEFAULT_RING_CAPACITY, pose_rows=False):
         """F = n_frames frames of H x W in the layout graph.frame_layout gives for the same options (object_loss: any true value).  The
         arrays start as zeros: an unset frame decodes to a black image, a zero camera, closed gates.  `ring`, `ctl`: the store's own
         FrameRing (ring_capacity entries), what decode() walks unless it is given another; `status`: device int32[1], sticky, the number of
@@ -126,6 +126,10 @@ class FrameStore:
             raise ValueError("FrameStore(label_phase=True) goes with gated only: the label frame is camera[, gate], obj_mask")
         if self.layout["motion"] and not self.layout["dynamic"]:
             raise ValueError("FrameStore(motion=True) goes with dynamic=True, as GraphedTrainStep")
+        if pose_rows:                                                   # (the key exists only in such a store's layout: every other layout is what it was)
+            if not self.layout["motion"]:
+                raise ValueError("FrameStore(pose_rows=True) goes with motion=True: the frame word of a pose sequence")
+            self.layout["pose_rows"] = True
         self.device = torch.device(device)
         n_pix = self.H * self.W
         self.n_pix, self.n_img = n_pix, (0 if label_phase else 3 * n_pix)
@@ -135,7 +139,7 @@ class FrameStore:
         self.image_stride = (self.n_img + 15) & ~15
         self.plane_words = (((n_pix + 31) >> 5) + 3) & ~3
         self.small_begin = self.off["cam"][0]
-        self.small_floats = (max(self.off[n][1] for n in ("cam", "accum_R", "accum_T") if n in self.off) - self.small_begin + 3) & ~3
+        self.small_floats = (max(self.off[n][1] for n in ("cam", "accum_R", "accum_T", "pose_rows") if n in self.off) - self.small_begin + 3) & ~3
         dev = self.device
         self.img = torch.zeros((self.n_frames, self.image_stride), dtype=torch.uint8, device=dev) if self.n_img else None
         self.bits = torch.zeros((self.n_frames, len(self.planes), self.plane_words), dtype=torch.int32, device=dev) if self.planes else None
@@ -180,7 +184,7 @@ class FrameStore:
                              "pass quantize=True to round them to the nearest code")
         return q
 
-    def put(self, i, cam, gt=None, accum_R=None, accum_T=None, gate=None, obj_mask=None, quantize=False, _premasked=False):
+    def put(self, i, cam, gt=None, accum_R=None, accum_T=None, gate=None, obj_mask=None, quantize=False, _premasked=False, pose_rows=None):
         """Stores frame i -- the arguments of graph.pack_frame / pack_label_frame, and frame(i) then equals what those return for them, bit
         for bit.  cam: a camera, or its packed float32[35] block.  gt: uint8 [3,H,W], or float32 with every value exactly k / 255 in float32
         (x == round(x * 255) / 255 bit for bit), else ValueError unless quantize=True (then round(clamp(x, 0, 1) * 255), ties to even, is
@@ -190,7 +194,7 @@ class FrameStore:
         lay = self.layout
         has_mask = lay["object_loss"] or lay["label_phase"]
         for name, given, wanted in (("gt", gt, not lay["label_phase"]), ("accum_R", accum_R, lay["dynamic"]), ("accum_T", accum_T, lay["motion"]),
-                                    ("gate", gate, lay["gated"]), ("obj_mask", obj_mask, has_mask)):
+                                    ("gate", gate, lay["gated"]), ("obj_mask", obj_mask, has_mask), ("pose_rows", pose_rows, lay.get("pose_rows", False))):
             if (given is not None) != wanted:
                 raise ValueError(f"FrameStore.put: this store's layout {'needs' if wanted else 'has no'} {name} ({lay})")
         dev = self.device
@@ -204,6 +208,9 @@ class FrameStore:
             block[rel("accum_R")] = accum_R.detach().reshape(-1).to(dev, torch.float32)
         if accum_T is not None:
             block[rel("accum_T")] = accum_T.detach().reshape(-1, 4)[:3].reshape(-1).to(dev, torch.float32)
+        if pose_rows is not None:                                       # (fixed_row, train_row[, reload]), or the int32[4] word itself
+            word = pose_rows.detach().reshape(-1).to(torch.int32) if torch.is_tensor(pose_rows) else pose_word(pose_rows)
+            block[rel("pose_rows")].view(torch.int32).copy_(word)
         planes = {}
         if gate is not None:
             planes["gate"] = _plane(gate, "gate", self.H, self.W, dev)
@@ -241,9 +248,18 @@ class FrameStore:
                 raise ValueError(f"FrameStore.from_packed: frame {i} has {f.numel()} {f.dtype} elements, the layout {store.layout} at "
                                  f"{W}x{H} has {store.frame_floats} float32")
             seg = lambda name: f[off[name][0]:off[name][1]] if name in off else None
+            word = seg("pose_rows")
             store.put(i, seg("cam"), gt=seg("gt"), accum_R=seg("accum_R"), accum_T=seg("accum_T"), gate=seg("gate"), obj_mask=seg("obj_mask"),
-                      _premasked=True)
+                      _premasked=True, pose_rows=None if word is None else word.view(torch.int32))
         return store
+
+    def set_pose_rows(self, i, rows):
+        """Rewrites frame i's pose_rows word in place: rows = (fixed_row, train_row[, reload]) (a store with pose_rows=True)."""
+        if "pose_rows" not in self.off:
+            raise ValueError(f"FrameStore.set_pose_rows: this store's layout has no pose_rows ({self.layout})")
+        i = _check_indices([i], self.n_frames, "FrameStore.set_pose_rows")[0]
+        b = self.off["pose_rows"][0] - self.small_begin
+        self.small[i, b:b + 4].view(torch.int32).copy_(pose_word(rows), non_blocking=True)
 
     # ---- reading: the definition --------------------------------------------------------------------------------------------------------------
     def frame(self, i):

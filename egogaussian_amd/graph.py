@@ -39,10 +39,12 @@ def pack_camera(cam):
     return torch.cat([cam.world_view_transform.reshape(-1), cam.full_proj_transform.reshape(-1), cam.camera_center.reshape(-1)]).float()
 
 
-def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_loss=False, label_phase=False):
+def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_loss=False, label_phase=False, pose_rows=False):
     """Float offsets of the segments of a packed frame (each starts on a 16-byte boundary): -> ({name: (begin, end)}, size).
     object_loss: an `obj_mask` segment of n_pix floats follows everything else (the other segments keep their offsets).
-    label_phase: the frame of a label step -- no image segment (n_img is not read): camera[, gate], obj_mask."""
+    label_phase: the frame of a label step -- no image segment (n_img is not read): camera[, gate], obj_mask.
+    pose_rows: a 4-word segment `pose_rows` follows accum_T -- the frame word (fixed_row, train_row, reload, 0) of a poses.PoseSequence,
+    int32 carried in the float buffer.  Without it every layout is what it was."""
     up4 = lambda x: (x + 3) & ~3
     off, end = {}, 0
     if not label_phase:                                             # (the label frame has no "gt" key at all: FrameStore tests `name in off`)
@@ -52,6 +54,8 @@ def frame_layout(n_img, n_pix, dynamic=False, gated=False, motion=False, object_
         off["accum_R"] = (end, end + 9); end = up4(end + 9)
     if motion:
         off["accum_T"] = (end, end + 12); end = up4(end + 12)      # the object's accumulated pose as A12 = [A | b], row-major 3x4
+    if pose_rows:
+        off["pose_rows"] = (end, end + 4); end = up4(end + 4)
     if gated:
         off["gate"] = (end, end + n_pix); end = up4(end + n_pix)
     if object_loss or label_phase:
@@ -63,13 +67,17 @@ def frame_views(frame, off, H, W):
     """The named views of ONE packed frame (a flat float32 tensor of the layout `off`): dict(gt [3,H,W], cam [35] -- the storage of a
     _StaticCamera --, accum_R [3,3], accum_T [3,4], gate [H,W], obj_mask [H,W]); None where the layout has no such segment."""
     seg = lambda name, *shape: frame[off[name][0]:off[name][1]].view(*shape) if name in off else None
-    return dict(gt=seg("gt", 3, H, W), cam=seg("cam", 35), accum_R=seg("accum_R", 3, 3), accum_T=seg("accum_T", 3, 4),
-                gate=seg("gate", H, W), obj_mask=seg("obj_mask", H, W))
+    views = dict(gt=seg("gt", 3, H, W), cam=seg("cam", 35), accum_R=seg("accum_R", 3, 3), accum_T=seg("accum_T", 3, 4),
+                 gate=seg("gate", H, W), obj_mask=seg("obj_mask", H, W))
+    if "pose_rows" in off:                                          # the frame word of a pose sequence, as the int32[4] it is
+        views["pose_rows"] = frame[off["pose_rows"][0]:off["pose_rows"][1]].view(torch.int32)
+    return views
 
 
-def dynamic_kwargs(f, which_object, pose=None):
+def dynamic_kwargs(f, which_object, pose=None, pose_grad=None):
     """render()'s keywords of the `fine_all` call shape from the static views `f` of a frame (frame_views): rot_cov with the frame's accum_R
-    and, where the frame carries an accum_T, the object placed by it inside the rasterizer -- with `pose`, a trainable pose on top."""
+    and, where the frame carries an accum_T, the object placed by it inside the rasterizer -- with `pose`, a trainable pose on top.
+    pose_grad (float32[21] on the device; pose_sequence=): the rasterizer's backward leaves dL/dA12, dL/dM9 of the static buffers there."""
     kw = dict(rot_cov=True, accum_R=f["accum_R"], which_object=which_object, during_training=False)
     if f["accum_T"] is not None:
         from .motion import ComposedMotion, ObjectMotion
@@ -77,11 +85,19 @@ def dynamic_kwargs(f, which_object, pose=None):
             # composed INSIDE the capture from the static buffers and the two parameters: autograd carries dL/dA12, dL/dM9 back to them
             kw["object_motion"] = ObjectMotion(f["accum_T"], pose, f["accum_R"])
         else:
-            kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"])      # the static buffers themselves: no launch, follows every copy
+            kw["object_motion"] = ComposedMotion(f["accum_T"], f["accum_R"], grad_out=pose_grad)      # the static buffers themselves: no launch, follows every copy
     return kw
 
 
-def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
+def pose_word(rows):
+    """(fixed_row, train_row[, reload]) -> the frame word of a poses.PoseSequence as a host int32[4]; -1 = no such row."""
+    rows = [int(r) for r in rows]
+    if len(rows) not in (2, 3):
+        raise ValueError("pose_rows: (fixed_row, train_row[, reload])")
+    return torch.tensor(rows + [0] * (4 - len(rows)), dtype=torch.int32)
+
+
+def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None, pose_rows=None):
     """One resident tensor per training frame: the ground-truth image, the camera block and -- for a step captured with
     dynamic=True / gated=True -- the object's accumulated rotation (3x3) and the per-pixel gradient gate (1 - hand mask, [H,W]).
     accum_T (a step captured with motion=True): the object's accumulated pose, 4x4 or 3x4 -- its first three rows travel as 12 floats.
@@ -90,8 +106,16 @@ def pack_frame(cam, gt, accum_R=None, gate=None, accum_T=None, obj_mask=None):
     The background stage's gate, 1 - dilate_k(hand mask | object mask), can be written into the frame afterwards without a tensor of its own:
     fused.interaction_gate(hand, obj, k, out=frame[off["gate"][0]:off["gate"][1]]) with off from frame_layout(..., gated=True).
     GraphedTrainStep(frame) then refreshes every static input of the captured step with ONE device copy."""
-    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None, obj_mask is not None)
+    if pose_rows is not None:
+        # (fixed_row, train_row[, reload]): a step captured with pose_sequence= -- its head kernel WRITES the frame's accum_R / accum_T in
+        # the static buffer, so what travels in those two segments is not read: the identity unless given
+        accum_R = torch.eye(3) if accum_R is None else accum_R
+        accum_T = torch.eye(4) if accum_T is None else accum_T
+    off, size = frame_layout(gt.numel(), gt.shape[-2] * gt.shape[-1], accum_R is not None, gate is not None, accum_T is not None, obj_mask is not None,
+                             pose_rows=pose_rows is not None)
     f = torch.zeros(size, device=gt.device, dtype=torch.float32)
+    if pose_rows is not None:
+        f[off["pose_rows"][0]:off["pose_rows"][1]].view(torch.int32).copy_(pose_word(pose_rows))
     if obj_mask is not None:
         m = obj_mask.to(gt.device, torch.float32).reshape(gt.shape[-2], gt.shape[-1])
         f[off["obj_mask"][0]:off["obj_mask"][1]] = m.reshape(-1)
@@ -217,8 +241,18 @@ class _StaticCamera:
 class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
-                 motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False, frame_store=None, ring_capacity=4096):
-        """frame_store:   a frames.FrameStore of this step's layout (dynamic, motion, gated, object_loss, label_phase as given here, else
+                 motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False, frame_store=None, ring_capacity=4096,
+                 pose_sequence=None):
+        """pose_sequence: (with dynamic=True, motion=True; not with pose=: ValueError) a poses.PoseSequence -- the object stages' pose table on
+                       the device.  Every frame carries the word `pose_rows` = (fixed_row, train_row, reload) (pack_frame(pose_rows=),
+                       PoseSequence.rows); per iteration the capture holds, in order, egs_pose_head (reads the slot's word, WRITES the
+                       slot's accum_T / accum_R -- the buffers the rasterizer reads), the step, whose backward leaves dL/dA12, dL/dM9 in
+                       a static float32[21], and egs_pose_tail (dL/dpose, the pose's own Adam step, the frame's table row, the
+                       accumulated rows after it).  No torch launch for the pose on either side and no optimizer group for it:
+                       the pose's learning rates are PoseSequence.set_lr's device scalars.  A frame with train_row = -1 is a fixed-pose
+                       frame: the same captured step renders it with accum[fixed_row] and leaves the pose and its Adam state alone --
+                       the coarse stage's alternation.  `pose_sequence.dpose` holds dL/dpose of the last trainable frame.
+        frame_store:   a frames.FrameStore of this step's layout (dynamic, motion, gated, object_loss, label_phase as given here, else
                        ValueError): the dataset stays on the device in 8 bits and the captured graph BEGINS with one decode launch that
                        writes the static frames of all `steps_per_replay` iterations from it, by index (include/egs_raster.h
                        egs_frame_decode) -- no frame copy, no host work per replay beyond the launch.  capture(cam, index=i0): `cam` gives
@@ -290,6 +324,8 @@ class GraphedTrainStep:
             if double_buffer:
                 raise ValueError("GraphedTrainStep(frame_store=) does not go with double_buffer: the decode is part of the graph, no copy is left to hide")
             mine = dict(dynamic=bool(dynamic), motion=bool(motion), gated=bool(gated), object_loss=object_loss is not None, label_phase=bool(label_phase))
+            if pose_sequence is not None:
+                mine["pose_rows"] = True
             if frame_store.layout != mine:
                 raise ValueError(f"GraphedTrainStep(frame_store=): the store's layout {frame_store.layout} is not this step's {mine}")
             self._ring_capacity = int(ring_capacity)
@@ -335,6 +371,12 @@ class GraphedTrainStep:
             if id(pose.obj_translation) not in owned or id(pose.obj_rotation_6d) not in owned:
                 raise ValueError("GraphedTrainStep(pose=): obj_translation and obj_rotation_6d must be parameter groups of the optimizer "
                                  "given (its step() inside the capture is what moves them)")
+        self.pose_sequence, self._pose_grads = pose_sequence, None
+        if pose_sequence is not None:
+            if pose is not None:
+                raise ValueError("GraphedTrainStep(pose_sequence=) does not go with pose=: the sequence owns the trainable pose and its Adam state")
+            if not self.motion:
+                raise ValueError("GraphedTrainStep(pose_sequence=) goes with dynamic=True, motion=True (its head writes the frame's accum_T / accum_R)")
         self.object_loss = None if object_loss is None else dict(object_loss)
         if self.object_loss is not None and set(self.object_loss) - {"lambda_image", "lambda_l1_alpha", "lambda_l2_alpha"}:
             raise ValueError("GraphedTrainStep(object_loss=): a dict of lambda_image, lambda_l1_alpha, lambda_l2_alpha")
@@ -403,8 +445,11 @@ class GraphedTrainStep:
         """One training iteration on static frame k."""
         f = self._slots[k]
         kw = dict(self.render_kwargs)
+        seq = self.pose_sequence
+        if seq is not None:
+            seq.head(f["pose_rows"], f["accum_T"], f["accum_R"])     # the frame's pose, composed on the device into the buffers the rasterizer reads
         if self.dynamic:
-            kw.update(dynamic_kwargs(f, self.which_object, self.pose))
+            kw.update(dynamic_kwargs(f, self.which_object, self.pose, None if seq is None else self._pose_grads[k]))
         if self.entropy_reg:
             kw["opacity_entropy"] = self._entropy_weight_dev         # the device scalar itself: the kernels read it at every replay
         out = render(f["cam"], self.pc, self.pipe, self.bg, fused_densify_stats=self.densify_stats, guard=self.guard,
@@ -418,12 +463,15 @@ class GraphedTrainStep:
             loss = l1_ssim_loss(out["render"], f["gt"], self.lam, grad_gate=f["gate"] if self.gated else None, running_sum=self.loss_sum,
                                 defer_value=True, raster_prologue=True, raster_lossgrad=self.loss_grad_in_blend)
         loss.backward(gradient=self._one)                            # a resident 1.0: no fill kernel per iteration
-        self.opt.step()                                              # whatever the backward did not step itself (fuse_optimizer)
+        if seq is not None:
+            # (the overflow word is written by CAPTURED forwards only: an eager warm-up step follows a complete render)
+            seq.tail(f["pose_rows"], self._pose_grads[k], skip=self.guard.overflow if torch.cuda.is_current_stream_capturing() else None)
+        self.opt.step()                                             # whatever the backward did not step itself (fuse_optimizer)
         return loss.detach(), out
 
     def _layout(self, H, W):
         return frame_layout(0 if self.label_phase else 3 * H * W, H * W, self.dynamic, self.gated, self.motion, self.object_loss is not None,
-                            self.label_phase)
+                            self.label_phase, pose_rows=self.pose_sequence is not None)
 
     def _decode_frames(self):
         """frame_store=: the first launch of the captured graph -- every static frame from the store, by the ring; the cursor advances on the device."""
@@ -481,9 +529,10 @@ class GraphedTrainStep:
             setattr(self, name, value)
 
     def capture(self, cam, gt=None, warmup=3, capacity_margin=1.25, accum_R=None, gate=None, capacity_cams=None, capacity=None, accum_T=None,
-                obj_mask=None, index=None):
+                obj_mask=None, index=None, pose_rows=None):
         """Runs `warmup` eager iterations on (cam, gt) -- they are real training steps -- then records (without executing) one
-        more into the graph.  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
+        more into the graph.  pose_rows (pose_sequence=): the (fixed_row, train_row[, reload]) of the frame the warm-up runs on (default:
+        no row at all -- the identity, nothing trained, the table untouched).  capacity_cams: further cameras whose instance counts size the captured capacity (a forward-only
         render each); without them the capacity is `capacity_margin` x the count of `cam` alone, and R varies across views.
         capacity: the instance capacity to capture with, as is (overrides the margin rule; tests use it to provoke an overflow).
         obj_mask (object_loss=): the frame's object mask; `gt` is the frame as loaded, the static buffer stores gt * obj_mask.
@@ -493,8 +542,9 @@ class GraphedTrainStep:
             if (int(cam.image_height), int(cam.image_width)) != (self.frame_store.H, self.frame_store.W):
                 raise ValueError(f"GraphedTrainStep(frame_store=).capture: the camera is {cam.image_width}x{cam.image_height}, the store's frames "
                                  f"{self.frame_store.W}x{self.frame_store.H}")
-            parts = self._store_frame(index, (gt, accum_R, gate, accum_T, obj_mask))
+            parts = self._store_frame(index, (gt, accum_R, gate, accum_T, obj_mask, pose_rows))
             gt, accum_R, gate, accum_T, obj_mask = parts["gt"], parts["accum_R"], parts["gate"], parts["accum_T"], parts["obj_mask"]
+            pose_rows = parts.get("pose_rows")                           # (the stored word itself, an int32[4] tensor)
         elif index is not None:
             raise ValueError("capture(index=) goes with GraphedTrainStep(frame_store=)")
         if label and obj_mask is None and fresh:
@@ -520,6 +570,10 @@ class GraphedTrainStep:
                 for name, value, default in given:
                     if slot[name] is not None:
                         slot[name].copy_(default() if value is None else value)
+                if self.pose_sequence is not None:
+                    slot["pose_rows"].copy_(pose_rows if torch.is_tensor(pose_rows) else pose_word((-1, -1) if pose_rows is None else pose_rows))
+            if self.pose_sequence is not None:
+                self._pose_grads = torch.zeros((self.steps_per_replay, 21), device=dev, dtype=torch.float32)      # dL/dA12, dL/dM9 per captured iteration
             self._frame = self._frames[0]
             first = self._slots[0]                                   # (the single-iteration names)
             self.gt, self.cam, self.accum_R, self.accum_T, self.gate, self.obj_mask = (first[n] for n in ("gt", "cam", "accum_R", "accum_T", "gate", "obj_mask"))
@@ -590,7 +644,7 @@ class GraphedTrainStep:
             return self.capture(cam, None, warmup=warmup, capacity_margin=capacity_margin, obj_mask=self.obj_mask, gate=self.gate)
         return self.capture(cam, gt, warmup=warmup, capacity_margin=capacity_margin, capacity_cams=capacity_cams)
 
-    def __call__(self, cam=None, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None):
+    def __call__(self, cam=None, gt=None, accum_R=None, gate=None, ready=None, accum_T=None, obj_mask=None, pose_rows=None):
         """One training iteration (steps_per_replay of them): copy inputs in, replay.  Returns the (device, static) loss tensor of
         the last iteration (`self.losses` has all).  Either (camera, ground-truth image[, accum_R][, gate]) or packed frames from
         pack_frame(): one for a single-iteration step, a [S, frame] tensor (one copy) or a list of S for steps_per_replay = S.
@@ -640,6 +694,8 @@ class GraphedTrainStep:
                 self.accum_T.copy_(accum_T.reshape(-1, 4)[:3], non_blocking=True)
             if self.gated and gate is not None:
                 self.gate.copy_(gate, non_blocking=True)
+            if self.pose_sequence is not None and pose_rows is not None:
+                self._slots[0]["pose_rows"].copy_(pose_word(pose_rows), non_blocking=True)
         self._before_replay()
         self.graph.replay()
         return self._after_replay()

@@ -90,7 +90,13 @@ class FrameLayout(C.Structure):                  # egs_frame_layout
                                          "image_stride", "plane_words", "n_planes")]
 
 
+class PoseSequence(C.Structure):                 # egs_pose_sequence
+    _fields_ = [("K", C.c_int32)] + [(n, C.c_void_p) for n in ("rel", "valid", "accum", "pose", "exp_avg", "exp_avg_sq", "step", "lr")] + \
+               [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
 FRAME_DYNAMIC, FRAME_MOTION, FRAME_GATED, FRAME_OBJECT_LOSS, FRAME_LABEL_PHASE = 1, 2, 4, 8, 16      # EGS_FRAME_*
+FRAME_POSE_ROWS = 32                             # EGS_FRAME_POSE_ROWS
 ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
@@ -140,6 +146,9 @@ SIGNATURES = {
     "egs_interaction_gate": (C.c_int, [i32, i32, vp, vp, i32, vp, vp]),
     "egs_frame_store_layout": (C.c_int, [i32, i32, i32, C.POINTER(FrameLayout)]),
     "egs_frame_decode": (C.c_int, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "egs_pose_head": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp]),
+    "egs_pose_tail": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp, vp]),
+    "egs_pose_accumulate": (C.c_int, [C.POINTER(PoseSequence), vp]),
 
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),

@@ -59,10 +59,12 @@ class ObjectMotion:
 
 class ComposedMotion:
     """A pose already in the kernels' form: compose() hands back the very tensors it was given (A12 [3,4], M [3,3] or None) -- static
-    device buffers of a captured step (graph.GraphedTrainStep(motion=True)), or a caller's own composition."""
+    device buffers of a captured step (graph.GraphedTrainStep(motion=True)), or a caller's own composition.
+    grad_out: a float32[21] device tensor the rasterizer's backward WRITES dL/dA12 [12], dL/dM9 [9] to -- the pose gradient without
+    autograd, for a consumer that is a kernel itself (poses.PoseSequence.tail)."""
 
-    def __init__(self, A12, M=None):
-        self.A12, self.M = A12, M
+    def __init__(self, A12, M=None, grad_out=None):
+        self.A12, self.M, self.grad_out = A12, M, grad_out
 
     def compose(self, device=None):
         return self.A12, self.M

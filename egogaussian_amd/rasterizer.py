@@ -148,7 +148,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos, geom,
             ctx.num_rendered, binning, img, alpha, rs.debug, ctx.activation_flags, sh_rest if split else None, ctx.densify_stats, ctx.guard,
             ctx.sink, ctx.prologue_scratch, ctx.object_rotation, grad_mask, loss_grad=None if ctx.loss_grad is None else ctx.loss_grad[0],
-            object_loss=None if (ctx.loss_grad is None or len(ctx.loss_grad) <= 3) else ctx.loss_grad[3], object_motion=ctx.object_motion, motion_grad=bool(need[18] or need[19]),
+            object_loss=None if (ctx.loss_grad is None or len(ctx.loss_grad) <= 3) else ctx.loss_grad[3], object_motion=ctx.object_motion,
+            motion_grad=bool(need[18] or need[19] or (ctx.object_motion is not None and len(ctx.object_motion) > 5)),      # (a sixth element: the caller's own float32[21] for the pose gradient)
             opacity_entropy=ctx.opacity_entropy)
         g_A12 = g_M = None
         if ctx.object_motion is not None:

@@ -137,6 +137,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
             cov3D_precomp = pc.get_covariance(scaling_modifier)
     else:
         scales, rotations = pc.get_scaling, pc.get_rotation
+    if motion_arg is not None and getattr(object_motion, "grad_out", None) is not None:
+        motion_arg = motion_arg + (object_motion.grad_out,)      # a sixth element: where the backward leaves dL/dA12, dL/dM9 (motion.ComposedMotion)
 
     shs = colors_precomp = None
     if override_color is not None:

@@ -584,6 +584,49 @@ int egs_frame_store_layout(int height, int width, int flags, egs_frame_layout* l
 int egs_frame_decode(int height, int width, int flags, int n_frames, int n_rows, const uint8_t* img, const uint32_t* bits, const float* small,
                      const float* table, const int32_t* ring, int ring_capacity, int32_t* ctl /*device [2] in/out*/,
                      int32_t* status /*device [1] in/out*/, float* out /*[n_rows][frame_floats]*/, void* stream);
+/* POSE_ROWS (added within ABI 6): a 4-word segment `pose_rows` follows accum_T in the small block (the frame word of the pose sequence
+ * below: int32 carried in the float buffer, copied bit for bit like every float of the block); needs MOTION (else EGS_ERR_MODE);
+ * small_floats is then 64. */
+#define EGS_FRAME_POSE_ROWS   32
+
+/* ---- the object pose sequence on the device (added within ABI 6: new entries only).
+ *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the
+ *      frame's key and rebuild the accumulated sequence (/root/reference/trainers/fine_obj.py:97-126,216-224,
+ *      /root/reference/utils/geometry_utils.py:69-89,152-186).  Here the table lives on the device and two one-workgroup launches do that
+ *      bookkeeping around a rasterizer step, so a captured step can run over dynamic frames with no host work between them.
+ *        rel    float[K][12]  per sorted key the relative pose [R | t], row-major 3x4
+ *        valid  uint8[K]      0: the key has no pose yet (the reference's None entry)
+ *        accum  float[K][12]  [A | b] of T_k ... T_1 over the valid rows; an invalid row repeats its predecessor, a row before any valid one
+ *                             is the identity.  Its rotation block is the accumulated rotation.
+ *        pose   float[9]      obj_translation[3], then obj_rotation_6d as the reference's (3,2) row-major
+ *        exp_avg, exp_avg_sq float[9]; step float[2], lr float[2]: ONE Adam state for the whole sequence, [0] translation, [1] rotation
+ *      frame word: device int32[4] = (fixed_row, train_row, reload, 0), read by the kernels; a row outside [0, K) means "none".
+ *      egs_pose_head   train_row none: A12 / M9 = bit copies of accum[fixed_row] and its rotation block (identity without a fixed row).
+ *                      Else, with reload != 0, first pose <- (t of rel[train_row], first two columns of its R); then R_t = the 6-D map of
+ *                      the pose's rotation (normalise with a 1e-12 floor, Gram-Schmidt, cross product), A = R_t A_f, b = R_t b_f + t,
+ *                      M = R_t R_f with (A_f | b_f) = accum[fixed_row] or the identity.  Writes A12[12], M9[9].
+ *      egs_pose_tail   train_row none, or *skip_flag != 0: nothing at all.  Else from grad21 (dL/dA12[12], dL/dM9[9]): dL/dt = dL/db,
+ *                      dL/dR_t = dL/dA A_f^T + dL/db b_f^T + dL/dM R_f^T, back through the 6-D map -> dpose[9] (written when not NULL);
+ *                      the Adam step of the nine scalars (the arithmetic and coefficient expressions of egs_adam_step_capturable, bit
+ *                      for bit; step[0], step[1] advance by one); rel[train_row] = [R(new rotation) | new t], valid[train_row] = 1;
+ *                      accum[j] recomputed for j >= train_row.
+ *      egs_pose_accumulate  accum[0 .. K) from rel and valid (after host edits of them).
+ *      The small arithmetic runs in float64 and every stored value is rounded to float32 once; the accumulation is a sequential chain
+ *      whose carry is the float32 row just stored, so the tail's suffix and a full accumulation agree bit for bit.  One workgroup of one
+ *      wave each, no atomics; same inputs, same bits.  EGS_ERR_ARG before any device work: K < 1, a NULL member or argument (dpose and
+ *      skip_flag may be NULL).  No allocation, no global state. */
+typedef struct egs_pose_sequence {
+    int32_t K;
+    float* rel; uint8_t* valid; float* accum;          /* device [K][12], [K], [K][12] */
+    float* pose; float* exp_avg; float* exp_avg_sq;    /* device [9] each */
+    float* step; const float* lr;                      /* device [2] each */
+    float beta1, beta2, eps;
+} egs_pose_sequence;
+int egs_pose_head(const egs_pose_sequence* seq, const int32_t* frame_word /*device [4]*/, float* A12 /*device [12] out*/, float* M9 /*device [9] out*/,
+                  void* stream);
+int egs_pose_tail(const egs_pose_sequence* seq, const int32_t* frame_word /*device [4]*/, const float* grad21 /*device [21]*/,
+                  float* dpose /*device [9] out or NULL*/, const uint32_t* skip_flag /*device [1] or NULL*/, void* stream);
+int egs_pose_accumulate(const egs_pose_sequence* seq, void* stream);
 
 /* The same launch carrying, in extra workgroups, what a rasterizer backward of the same frame needs done before its blend
  * kernel: ordering the tiles by the cost the forward recorded, clearing the gradient accumulator (`scratch`) and, with a sink, the

@@ -293,10 +293,11 @@ def _opt(t):
     return None if t is None or t.numel() == 0 else t
 
 
-ACT_LOG_SCALES, ACT_RAW_QUATS, ACT_LOGIT_OPACITY = 1, 2, 4      # include/egs_raster.h: EGS_ACT_*
-ACT_RAW_PARAMETERS = ACT_LOG_SCALES | ACT_RAW_QUATS | ACT_LOGIT_OPACITY
-# include/egs_raster.h: EGS_GRAD_* (which inputs' gradients the caller reads; 0 = all)
-GRAD_MEANS3D, GRAD_MEANS2D, GRAD_SH, GRAD_COLORS, GRAD_OPACITY, GRAD_SCALES, GRAD_ROTATIONS, GRAD_COV3D = 1, 2, 4, 8, 16, 32, 64, 128
+# include/egs_raster.h EGS_ACT_* and EGS_GRAD_* (defined once, in lib.py)
+ACT_LOG_SCALES, ACT_RAW_QUATS, ACT_LOGIT_OPACITY, ACT_RAW_PARAMETERS, ACT_SCALAR_COLOR = (
+    _lib.ACT_LOG_SCALES, _lib.ACT_RAW_QUATS, _lib.ACT_LOGIT_OPACITY, _lib.ACT_RAW_PARAMETERS, _lib.ACT_SCALAR_COLOR)
+GRAD_MEANS3D, GRAD_MEANS2D, GRAD_SH, GRAD_COLORS, GRAD_OPACITY, GRAD_SCALES, GRAD_ROTATIONS, GRAD_COV3D = (
+    _lib.GRAD_MEANS3D, _lib.GRAD_MEANS2D, _lib.GRAD_SH, _lib.GRAD_COLORS, _lib.GRAD_OPACITY, _lib.GRAD_SCALES, _lib.GRAD_ROTATIONS, _lib.GRAD_COV3D)
 COLORS_ONLY_BACKWARD = True        # measurement switch (bench.py label_phase_shape): False withholds the mask, the full backward runs
 
 
@@ -371,44 +372,37 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                 state = torch.empty((gb + ib + bb,), device=dev, dtype=torch.uint8)
                 geom, img, binning = state[:gb], state[gb:gb + ib], state[gb + ib:]
             deferred = cap > 0                                   # no capacity known yet: this call establishes it the waiting way
-        if deferred:
-            i = guard.frames % _DEFER_RING
-            pin = guard._pinned[i]
-            if pin is None or pin.numel() < nb + 2:
-                pin = guard._pinned[i] = torch.empty((max(nb + 2, 4096),), dtype=torch.int32, pin_memory=True)
-            pin[nb] = -1                                         # sentinel: overwritten (0 / 1) by the copy that ends the chain
-            _lib.check(L.egs_forward_enqueue(
-                P, int(degree), M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(opacity), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), _ptr(background), W, H,
-                float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), cap, _ptr(binning), _ptr(img),
-                _ptr(out_color), _ptr(out_depth), _ptr(out_alpha), C.c_void_p(pin.data_ptr()), _ptr(guard.running_max),
-                _ptr(active_count), _ptr(guard.overflow), _ptr(place), rot_arg, _stream(dev), flags))
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))             # behind the frame's last copy (egs_forward_enqueue queued it on this stream)
-            guard._pending.append((pin, P, cap, key, ev))
-            guard.frames += 1
-            R = C.c_int64(cap)                      # layout size, as under capture; the frame's own count is read at the next call
-            rc = 0
-        elif capturing:
-            # hipGraph capture of a whole training step (egogaussian_amd/graph.py): nothing may wait on the host, so the
-            # chain is enqueued against the capacity established by earlier eager calls and R is checked after replays.
-            if cap <= 0 or P == 0:
+        # the run egs_forward and egs_forward_enqueue share (lib.py _FWD_SCENE + _FWD_RENDER up to the counts buffer), and their common tail
+        scene = (P, int(degree), M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(opacity), _ptr(scales), float(scale_modifier),
+                 _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), _ptr(background), W, H,
+                 float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), cap, _ptr(binning), _ptr(img),
+                 _ptr(out_color), _ptr(out_depth), _ptr(out_alpha))
+        tail = (_ptr(place), rot_arg, _stream(dev), flags)
+        if deferred or capturing:
+            # Nothing waits on the host.  Under hipGraph capture of a whole training step (egogaussian_amd/graph.py) the chain is enqueued
+            # against the capacity established by earlier eager calls and R is checked after replays; a deferred eager forward also
+            # copies its counts and overflow word out, for a following forward to read.
+            if capturing and (cap <= 0 or P == 0):
                 raise RuntimeError("rasterize_gaussians under graph capture needs a capacity from an earlier eager call")
-            _lib.check(L.egs_forward_enqueue(
-                P, int(degree), M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(opacity), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), _ptr(background), W, H,
-                float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), cap, _ptr(binning), _ptr(img),
-                _ptr(out_color), _ptr(out_depth), _ptr(out_alpha), None, _ptr(None if guard is None else guard.running_max),
-                _ptr(active_count), _ptr(None if guard is None else guard.overflow), _ptr(place), rot_arg, _stream(dev), flags))
-            R = C.c_int64(cap)                      # layout size; the true count is stats["total_view"] after a sync
+            counts = None
+            if deferred:
+                i = guard.frames % _DEFER_RING
+                pin = guard._pinned[i]
+                if pin is None or pin.numel() < nb + 2:
+                    pin = guard._pinned[i] = torch.empty((max(nb + 2, 4096),), dtype=torch.int32, pin_memory=True)
+                pin[nb] = -1                                     # sentinel: overwritten (0 / 1) by the copy that ends the chain
+                counts = C.c_void_p(pin.data_ptr())
+            _lib.check(L.egs_forward_enqueue(*scene, counts, _ptr(None if guard is None else guard.running_max), _ptr(active_count),
+                                             _ptr(None if guard is None else guard.overflow), *tail))
+            if deferred:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(dev))         # behind the frame's last copy (egs_forward_enqueue queued it on this stream)
+                guard._pending.append((pin, P, cap, key, ev))
+                guard.frames += 1
+            R = C.c_int64(cap)                      # layout size: a deferred frame's own count is read at the next call, a captured one's is stats["total_view"] after a sync
             rc = 0
         else:
-            rc = L.egs_forward(P, int(degree), M, _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(opacity), _ptr(scales),
-                               float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                               _ptr(campos), _ptr(background), W, H, float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-                               _ptr(radii), _ptr(geom), cap, _ptr(binning), _ptr(img), _ptr(out_color), _ptr(out_depth),
-                               _ptr(out_alpha), C.c_void_p(pinned.data_ptr()), C.byref(R), _ptr(active_count), _ptr(place), rot_arg, _stream(dev),
-                               flags)
+            rc = L.egs_forward(*scene, C.c_void_p(pinned.data_ptr()), C.byref(R), _ptr(active_count), *tail)
         if rc == _lib.RETRY_LARGER:
             cap = int(R.value * 1.25) + 65536
             total_off = _buffer_sizes(L, P, W, H, cap)[3]
@@ -484,111 +478,84 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     M = 0 if sh is None else sh.shape[1] + (0 if sh_rest is None else sh_rest.shape[1])
     if opacity_entropy is not None and (object_motion is not None or object_loss is not None):
         raise RuntimeError("opacity_entropy: the term belongs to the static image step (no object_motion, no object_loss)")
-    if COLORS_ONLY_BACKWARD and P != 0 and grad_mask == GRAD_COLORS and colors is not None and sink is None and densify_stats is None and object_rotation is None \
-            and loss_grad is None and object_motion is None and opacity_entropy is None:          # (a loss gradient computed in the blend needs the full path: dL_dout_color is uninitialised then)
-        with _hip.device_ctx(dev):
-            dcolors = torch.empty((P, 3), device=dev, dtype=torch.float32)
-            scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
-            _lib.check(L.egs_backward_adam(
-                P, int(degree), M, int(R), _ptr(background), _ptr(means3D), None, None, _ptr(colors), _ptr(scales),
-                float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), _ptr(g_color), None, None, None, _ptr(dcolors), None, None, None, None, None, None, None,
-                None, None, None, None, None, 1 if prologue_scratch is not None else 0, None, GRAD_COLORS, _ptr(scratch), _stream(dev),
-                (call_flags(debug) & CALL_SYNC)))
-        return None, dcolors, None, None, None, None, None, None
+    # Only the precomputed colours' gradient is wanted: the library's colours-only route (a loss gradient computed in the blend needs the
+    # full path: dL_dout_color is uninitialised then)
+    colors_only = COLORS_ONLY_BACKWARD and P != 0 and grad_mask == GRAD_COLORS and colors is not None and sink is None and densify_stats is None \
+        and object_rotation is None and loss_grad is None and object_motion is None and opacity_entropy is None
     with _hip.device_ctx(dev):
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
         own_cov = cov3D_precomp is None
-        owned = set() if sink is None or P == 0 else sink.check(means3D=means3D, scales=scales, rotations=rotations, sh=sh, sh_rest=sh_rest,
-                                                                own_cov=own_cov, colors=colors)
-        keep = sink is not None and getattr(sink, "keep_grads", False)      # tests: the owned leaves' gradients are written as well
-        fused = lambda leaf: leaf in owned and not keep
-        no_colors = bool(owned and not keep and sh is not None and sh_rest is None and M == 1)      # dcolors would be scratch nobody reads
-        need_m3d_arg = fused(_lib.SINK_MEANS3D) and sh_rest is not None
-        # every gradient array of this backward out of ONE allocation (contiguous views on 256-byte boundaries)
-        (dmeans2D, dcolors, dopacity, dmeans3D, dmeans3D_tmp, dcov3D, dsh, dsh_rest, dscales, drots) = _carve(dev, [
-            (P, 3), None if no_colors else (P, 3), None if fused(_lib.SINK_OPACITY) else (P, 1), None if fused(_lib.SINK_MEANS3D) else (P, 3),
-            (P, 3) if need_m3d_arg else None, None if own_cov else (P, 6),
-            None if (fused(_lib.SINK_SH) or sh is None) else tuple(sh.shape),
-            None if (fused(_lib.SINK_SH_REST) or sh_rest is None) else tuple(sh_rest.shape),
-            None if (fused(_lib.SINK_SCALES) or not own_cov) else (P, 3), None if (fused(_lib.SINK_ROTATIONS) or not own_cov) else (P, 4)])
-        # (split harmonics: the positions' gradient is finished by the spherical-harmonics launch and travels there through this array)
-        dmeans3D_arg = dmeans3D_tmp if need_m3d_arg else dmeans3D
-        if own_cov:
-            dcov3D = e(0, 6)                                 # not produced when the library built the covariance itself
-        if sh is None:
-            dsh = e(0, 0, 3)
-        if not own_cov:                                      # absent inputs get empty gradients (the autograd Function maps them to None)
-            dscales = None if fused(_lib.SINK_SCALES) else e(0, 3)
-            drots = None if fused(_lib.SINK_ROTATIONS) else e(0, 4)
-        pose_grad = None
-        if object_motion is not None:
-            rot_st, _rot_keep, pose_grad = _object_motion_struct(object_motion, dev, P, motion_grad)
-            activation_flags = int(activation_flags) | _lib.ACT_OBJECT_MOTION
-            if motion_grad and P == 0:
-                pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32) if len(object_motion) <= 5 else object_motion[5].zero_()
+        owned, rot_st, pose_grad = set(), None, None
+        if colors_only:
+            dcolors = e(P, 3)
+            dmeans2D = dopacity = dmeans3D = dmeans3D_arg = dcov3D = dsh = dsh_rest = dscales = drots = None
+            sh = sh_rest = g_depth = g_alpha = None              # (not read on this route: passed as NULL, as always)
         else:
-            rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
-        if P != 0 and opacity_entropy is not None:
-            if loss_grad is not None and (g_depth is not None or g_alpha is not None):
-                raise RuntimeError("loss_grad: the loss must depend on the colour output only")
-            scratch = prologue_scratch if prologue_scratch is not None else (scratch if scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8))
-            ent_st = opacity_entropy.struct(P, dev)
-            _lib.check(L.egs_backward_entropy_lossgrad(
-                P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
-                float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), None if loss_grad is None else C.byref(loss_grad), C.byref(ent_st),
-                None if loss_grad is not None else _ptr(g_color), None if loss_grad is not None else _ptr(g_depth),
-                None if loss_grad is not None else _ptr(g_alpha), _ptr(dmeans2D), _ptr(dcolors),
-                _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
-                _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
-                C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
-                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
-            if owned:
-                sink.mark_stepped()
-        elif P != 0 and loss_grad is not None:
-            if g_depth is not None or (g_alpha is not None and object_loss is None):
-                raise RuntimeError("loss_grad: the loss must depend on the colour output only (with object_loss: on colour and alpha)")
-            scratch = prologue_scratch if prologue_scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
-            entry, lg_args = (L.egs_backward_lossgrad, (C.byref(loss_grad),)) if object_loss is None else \
-                (L.egs_backward_object_lossgrad, (C.byref(loss_grad), C.byref(object_loss)))
+            if sink is not None and P != 0:
+                owned = sink.check(means3D=means3D, scales=scales, rotations=rotations, sh=sh, sh_rest=sh_rest, own_cov=own_cov, colors=colors)
+            keep = sink is not None and getattr(sink, "keep_grads", False)      # tests: the owned leaves' gradients are written as well
+            fused = lambda leaf: leaf in owned and not keep
+            no_colors = bool(owned and not keep and sh is not None and sh_rest is None and M == 1)      # dcolors would be scratch nobody reads
+            need_m3d_arg = fused(_lib.SINK_MEANS3D) and sh_rest is not None
+            # every gradient array of this backward out of ONE allocation (contiguous views on 256-byte boundaries)
+            (dmeans2D, dcolors, dopacity, dmeans3D, dmeans3D_tmp, dcov3D, dsh, dsh_rest, dscales, drots) = _carve(dev, [
+                (P, 3), None if no_colors else (P, 3), None if fused(_lib.SINK_OPACITY) else (P, 1), None if fused(_lib.SINK_MEANS3D) else (P, 3),
+                (P, 3) if need_m3d_arg else None, None if own_cov else (P, 6),
+                None if (fused(_lib.SINK_SH) or sh is None) else tuple(sh.shape),
+                None if (fused(_lib.SINK_SH_REST) or sh_rest is None) else tuple(sh_rest.shape),
+                None if (fused(_lib.SINK_SCALES) or not own_cov) else (P, 3), None if (fused(_lib.SINK_ROTATIONS) or not own_cov) else (P, 4)])
+            # (split harmonics: the positions' gradient is finished by the spherical-harmonics launch and travels there through this array)
+            dmeans3D_arg = dmeans3D_tmp if need_m3d_arg else dmeans3D
+            if own_cov:
+                dcov3D = e(0, 6)                                 # not produced when the library built the covariance itself
+            if sh is None:
+                dsh = e(0, 0, 3)
+            if not own_cov:                                      # absent inputs get empty gradients (the autograd Function maps them to None)
+                dscales = None if fused(_lib.SINK_SCALES) else e(0, 3)
+                drots = None if fused(_lib.SINK_ROTATIONS) else e(0, 4)
+            if object_motion is not None:
+                rot_st, _rot_keep, pose_grad = _object_motion_struct(object_motion, dev, P, motion_grad)
+                activation_flags = int(activation_flags) | _lib.ACT_OBJECT_MOTION
+                if motion_grad and P == 0:
+                    pose_grad = torch.zeros((21,), device=dev, dtype=torch.float32) if len(object_motion) <= 5 else object_motion[5].zero_()
+            else:
+                rot_st, _rot_keep = _object_rotation_struct(object_rotation, dev, P)
+        if P != 0:
+            # 1. the entry point and its middle segment (lib.py: the backwards differ in nothing else; egs_backward lacks sink, prologue_done, rot)
+            upstream = (_ptr(g_color), _ptr(g_depth), _ptr(g_alpha))
+            sink_tail = (C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0, _lib.rot_pointer(rot_st))
+            if opacity_entropy is not None:
+                if loss_grad is not None and (g_depth is not None or g_alpha is not None):
+                    raise RuntimeError("loss_grad: the loss must depend on the colour output only")
+                ent_st = opacity_entropy.struct(P, dev)
+                entry = L.egs_backward_entropy_lossgrad
+                middle = (None, C.byref(ent_st)) + upstream if loss_grad is None else (C.byref(loss_grad), C.byref(ent_st), None, None, None)
+            elif loss_grad is not None:
+                if g_depth is not None or (g_alpha is not None and object_loss is None):
+                    raise RuntimeError("loss_grad: the loss must depend on the colour output only (with object_loss: on colour and alpha)")
+                entry, middle = (L.egs_backward_lossgrad, (C.byref(loss_grad),)) if object_loss is None else \
+                    (L.egs_backward_object_lossgrad, (C.byref(loss_grad), C.byref(object_loss)))
+            elif colors_only or owned or prologue_scratch is not None or rot_st is not None:
+                entry, middle = L.egs_backward_adam, upstream
+            else:
+                entry, middle, sink_tail = L.egs_backward, upstream, ()
+            # 2. the scratch buffer: the one a loss backward prepared, else the caller's, else a temporary
+            if prologue_scratch is not None:
+                scratch = prologue_scratch
+            elif scratch is None:
+                scratch = torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
+            # 3. the call (lib.py: _BWD_SCENE, _STATE, middle, _GRADS, _STATS, _BWD_TAIL)
             _lib.check(entry(
                 P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
                 float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), *lg_args, _ptr(dmeans2D), _ptr(dcolors),
-                _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
-                _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
-                C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
-                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                *middle, _ptr(dmeans2D), _ptr(dcolors), _ptr(dopacity), _ptr(dmeans3D_arg), _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest),
+                _ptr(dscales), _ptr(drots), *_stat_ptrs(densify_stats, P, dev), None if colors_only else _ptr(None if guard is None else guard.overflow),
+                *sink_tail, GRAD_COLORS if colors_only else 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
             if owned:
                 sink.mark_stepped()
-        elif P != 0 and (owned or prologue_scratch is not None or rot_st is not None):
-            scratch = prologue_scratch if prologue_scratch is not None else (scratch if scratch is not None else torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8))
-            _lib.check(L.egs_backward_adam(
-                P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
-                float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), _ptr(g_color), _ptr(g_depth), _ptr(g_alpha), _ptr(dmeans2D), _ptr(dcolors),
-                _ptr(dopacity), _ptr(dmeans3D_arg), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
-                _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
-                C.byref(sink.struct) if owned else None, 1 if prologue_scratch is not None else 0,
-                _lib.rot_pointer(rot_st), 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
-            if owned:
-                sink.mark_stepped()
-        elif P != 0:
-            if scratch is None:
-                scratch = torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
-            _lib.check(L.egs_backward(
-                P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
-                float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), int(activation_flags), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), _ptr(g_color), _ptr(g_depth), _ptr(g_alpha), _ptr(dmeans2D), _ptr(dcolors),
-                _ptr(dopacity), _ptr(dmeans3D), None if own_cov else _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest), _ptr(dscales) if own_cov else None,
-                _ptr(drots) if own_cov else None, *_stat_ptrs(densify_stats, P, dev), _ptr(None if guard is None else guard.overflow),
-                0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+    if colors_only:
+        return None, dcolors, None, None, None, None, None, None
     tail = () if object_motion is None else (pose_grad,)
     if sh_rest is not None:
         return (dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dscales, drots, dsh_rest) + tail
@@ -651,9 +618,7 @@ def opacity_entropy_backward(opacity, radii, term, logit=False, active_count=Non
     return g
 
 
-# ---- the label phase (include/egs_raster.h: egs_label_bce_*, egs_backward_label) -----------------------------------------------
-ACT_SCALAR_COLOR = _lib.ACT_SCALAR_COLOR           # colors_precomp is float[P]: one value per Gaussian
-
+# ---- the label phase (include/egs_raster.h: egs_label_bce_*, egs_backward_label; ACT_SCALAR_COLOR: colors_precomp is float[P]) ----
 
 def label_bce_partial_count(H, W):
     return int(_lib.load().egs_label_bce_partial_count(int(H), int(W)))

@@ -33,10 +33,10 @@ GeomLayout geom_layout(int P) {
 }
 BinLayout bin_layout(int P, int64_t R, int W, int H) {
     BinLayout L; size_t off = 0; const size_t n = (size_t)(R > 0 ? R : 0);
-    const size_t gx = (W + EGS_TILE - 1) / EGS_TILE, gy = (H + EGS_TILE - 1) / EGS_TILE;
-    const size_t nblocks = egs_bin_blocks(P > 0 ? P : 0), stride = egs_table_stride((uint32_t)nblocks), tab = gx * gy * stride;
-    const size_t sums = EGS_BIN_GROUPS * egs_table_chunks(gx * gy, (uint32_t)stride);
-    L.o.key_bits = egs_key_bits_for_tiles((int)(gx * gy));
+    const size_t nt = egs_tiles(W, H);
+    const size_t nblocks = egs_bin_blocks(P > 0 ? P : 0), stride = egs_table_stride((uint32_t)nblocks), tab = nt * stride;
+    const size_t sums = EGS_BIN_GROUPS * egs_table_chunks(nt, (uint32_t)stride);
+    L.o.key_bits = egs_key_bits_for_tiles((int)nt);
     L.o.bin_blocks = (int)nblocks;
     L.o.table_stride = (int)stride;
     int ib = 0; while (P > 1 && (((unsigned)(P - 1)) >> ib) != 0) ib++;
@@ -51,13 +51,13 @@ BinLayout bin_layout(int P, int64_t R, int W, int H) {
 }
 ImgLayout img_layout(int W, int H) {
     ImgLayout L; size_t off = 0;
-    const size_t gx = (W + EGS_TILE - 1) / EGS_TILE, gy = (H + EGS_TILE - 1) / EGS_TILE, px = (size_t)W * H;
-    L.o.ranges = off;    off = egs_align(off + gx * gy * sizeof(uint2));
+    const size_t nt = egs_tiles(W, H), px = (size_t)W * H;
+    L.o.ranges = off;    off = egs_align(off + nt * sizeof(uint2));
     L.o.final_T = off;   off = egs_align(off + px * sizeof(float));
     L.o.n_contrib = off; off = egs_align(off + px * sizeof(uint32_t));
-    L.o.quad_work = off; off = egs_align(off + gx * gy * 4 * sizeof(uint32_t));
-    L.o.tile_order = off; off = egs_align(off + (size_t)egs_blocks_for_tiles((int)(gx * gy)) * sizeof(uint32_t));       // EGS_XCDS bands of egs_tiles_per_xcd() slots
-    L.o.quad_pairs = off; off = egs_align(off + gx * gy * 8 * sizeof(uint32_t));                 // pairs [tiles][4], then visits [tiles][4]
+    L.o.quad_work = off; off = egs_align(off + nt * 4 * sizeof(uint32_t));
+    L.o.tile_order = off; off = egs_align(off + (size_t)egs_blocks_for_tiles((int)nt) * sizeof(uint32_t));       // EGS_XCDS bands of egs_tiles_per_xcd() slots
+    L.o.quad_pairs = off; off = egs_align(off + nt * 8 * sizeof(uint32_t));                 // pairs [tiles][4], then visits [tiles][4]
     L.bytes = off; return L;
 }
 EgsGeomPtrs geom_ptrs(void* buf, int P) {
@@ -88,7 +88,7 @@ EgsImgPtrs img_ptrs(void* buf, int W, int H) {
 int check_dims(int P, int W, int H) {
     if (P < 0 || W <= 0 || H <= 0) return EGS_ERR_ARG;
     if (W > 32767 || H > 32767) return EGS_ERR_RANGE;                    // 15-bit pixel coordinates in the record's box (egs_common.h)
-    if ((size_t)((W + EGS_TILE - 1) / EGS_TILE) * (size_t)((H + EGS_TILE - 1) / EGS_TILE) > EGS_MAX_TILES) return EGS_ERR_RANGE;
+    if (egs_tiles(W, H) > EGS_MAX_TILES) return EGS_ERR_RANGE;
     return 0;
 }
 // The three opaque buffers hold 16-byte vectors at 256-byte-aligned offsets (float4 records, uint4 table words, 64-bit pairs): their
@@ -96,7 +96,9 @@ int check_dims(int P, int W, int H) {
 static inline bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 255u) != 0;
 }
-int check_modes(const float* shs, const float* colors, const float* scales, const float* rots, const float* cov, int act) {
+int check_modes(const EgsScene& sc) {
+    const float* shs = sc.shs; const float* colors = sc.colors; const float* scales = sc.scales; const float* rots = sc.rots; const float* cov = sc.cov3D;
+    const int act = sc.act;
     if (act & ~(EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS | EGS_ACT_LOGIT_OPACITY | EGS_ACT_OBJECT_MOTION | EGS_ACT_SCALAR_COLOR)) return EGS_ERR_MODE;
     if ((act & EGS_ACT_SCALAR_COLOR) && !colors) return EGS_ERR_MODE;                               // one value per Gaussian: of colors_precomp
     if ((act & (EGS_ACT_LOG_SCALES | EGS_ACT_RAW_QUATS)) && cov != nullptr) return EGS_ERR_MODE;   // nothing to activate: the covariance is given
@@ -105,6 +107,12 @@ int check_modes(const float* shs, const float* colors, const float* scales, cons
     if ((scales != nullptr) != (rots != nullptr)) return EGS_ERR_MODE;
     if (sr == (cov != nullptr)) return EGS_ERR_MODE;
     return 0;
+}
+// split spherical harmonics: shs_rest goes with shs = the DC block and at least two coefficients
+inline bool split_sh_malformed(const EgsScene& sc) { return sc.shs_rest && (!sc.shs || sc.M < 2); }
+// pointers every rasterizer call with P > 0 needs (the forwards add the opacities: the backwards read them in the record)
+inline bool lacks_pointers(const EgsScene& sc, const EgsCamera& cam, const void* radii, const void* geom) {
+    return !sc.means3D || !cam.view || !cam.proj || !cam.campos || !radii || !geom;
 }
 
 #define EGS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -224,7 +232,7 @@ static size_t placement_sums_offset(size_t nt) { return egs_align((nt * 4 + (siz
 static size_t placement_sums_words(size_t nt) { return (size_t)EGS_BIN_GROUPS * nt; }
 size_t egs_placement_bytes(int width, int height) {
     if (width <= 0 || height <= 0) return 0;
-    const size_t nt = (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+    const size_t nt = egs_tiles(width, height);
     return egs_align(placement_sums_offset(nt) + placement_sums_words(nt) * sizeof(uint32_t));
 }
 // The sums region of a placement buffer must be ZERO when a fused forward starts: egs_placement_init() once per (buffer, image size), the
@@ -232,7 +240,7 @@ size_t egs_placement_bytes(int width, int height) {
 // map of "clean" addresses stood here, which a freed-and-reallocated address could fool).
 int egs_placement_init(void* placement, int width, int height, void* stream) {
     if (!placement || check_dims(0, width, height)) return EGS_ERR_ARG;
-    const size_t nt = (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+    const size_t nt = egs_tiles(width, height);
     EGS_TRY(egs_launch_zero_u32((uint32_t*)((char*)placement + placement_sums_offset(nt)), placement_sums_words(nt), (hipStream_t)stream));
     return 0;
 }
@@ -243,15 +251,15 @@ struct PlacementClearOnError {
     ~PlacementClearOnError() { if (p) (void)egs_placement_init(p, w, h, (void*)s); }
 };
 static void placement_sums(void* placement, int width, int height, uint32_t** sums, uint32_t* words) {
-    const size_t nt = (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+    const size_t nt = egs_tiles(width, height);
     *sums = (uint32_t*)((char*)placement + placement_sums_offset(nt)); *words = (uint32_t)placement_sums_words(nt);
 }
 int egs_order_words(int width, int height) {
     if (width <= 0 || height <= 0) return 0;
-    return egs_blocks_for_tiles(((width + EGS_TILE - 1) / EGS_TILE) * ((height + EGS_TILE - 1) / EGS_TILE));
+    return egs_blocks_for_tiles((int)egs_tiles(width, height));
 }
 static void placement_ptrs(void* placement, int width, int height, EgsImgPtrs& im) {
-    const size_t nt = (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+    const size_t nt = egs_tiles(width, height);
     im.fwd_cost = (uint32_t*)placement; im.fwd_order = placement ? (uint32_t*)placement + nt * 4 : nullptr;
 }
 
@@ -271,9 +279,10 @@ static int obj_rot_args(const egs_object_rotation* rot, const float* scales, Egs
 // With EGS_ACT_OBJECT_MOTION the `rot` argument points to an egs_object_motion (HOST struct): the rotation as above (rot.M9 may be NULL:
 // covariances are not turned) plus the placement of the positions and, optionally, where the pose gradient goes.
 struct MotionHost { EgsMotion k; float* grad; };
-static int obj_motion_args(int act, const egs_object_rotation* rot, const float* scales, int P, EgsObjRot& r, MotionHost& m) {
+static int obj_motion_args(const EgsScene& sc, const egs_object_rotation* rot, EgsObjRot& r, MotionHost& m) {
+    const float* scales = sc.scales; const int P = sc.P;
     m = MotionHost{ EgsMotion{ nullptr, nullptr, nullptr, nullptr }, nullptr };
-    if (!(act & EGS_ACT_OBJECT_MOTION)) return obj_rot_args(rot, scales, r);
+    if (!(sc.act & EGS_ACT_OBJECT_MOTION)) return obj_rot_args(rot, scales, r);
     const egs_object_motion* om = reinterpret_cast<const egs_object_motion*>(rot);
     if (!om) return EGS_ERR_MODE;                                     // the bit without its struct: no such mode
     if (!om->A12 || (om->grad && !om->scratch)) return EGS_ERR_ARG;
@@ -286,6 +295,21 @@ static int obj_motion_args(int act, const egs_object_rotation* rot, const float*
     return 0;
 }
 
+// ---- the forwards: one record for the call ------------------------------------------------------------------------------------------
+// What the two forwards ask of a scene of P > 0 Gaussians before they launch anything, in the order callers have always met it: pointers,
+// modes, spherical-harmonics ranges, then the object rotation / motion (-> kernel arguments).
+static int check_forward_scene(const EgsScene& sc, const EgsCamera& cam, const void* radii, const void* geom, const egs_object_rotation* rot,
+                               EgsObjRot& orot, MotionHost& mh) {
+    if (lacks_pointers(sc, cam, radii, geom) || !sc.opac) return EGS_ERR_ARG;
+    int rc = check_modes(sc); if (rc) return rc;
+    if (sc.shs && (sc.D < 0 || sc.D > EGS_MAX_SH_DEGREE || sc.M < (sc.D + 1) * (sc.D + 1))) return EGS_ERR_RANGE;
+    if (split_sh_malformed(sc)) return EGS_ERR_MODE;
+    return obj_motion_args(sc, rot, orot, mh);
+}
+// The three forwards name their scene and camera parameters alike (include/egs_raster.h): the run each copies into its records
+#define FWD_SCENE { P, sh_degree, sh_coeffs, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp, activation_flags }
+#define FWD_CAMERA { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy }
+
 int egs_forward_geometry(int P, int sh_degree, int sh_coeffs, const float* means3D, const float* shs, const float* shs_rest,
                          const float* colors_precomp, const float* opacities, const float* scales,
                          float scale_modifier, const float* rotations, const float* cov3D_precomp, int activation_flags,
@@ -293,24 +317,18 @@ int egs_forward_geometry(int P, int sh_degree, int sh_coeffs, const float* means
                          float tan_fovx, float tan_fovy, int prefiltered, int32_t* radii, void* geom_buffer,
                          int64_t* num_rendered, const int32_t* active_count, const egs_object_rotation* rot, void* stream, int debug) {
     (void)prefiltered;
+    const EgsScene sc = FWD_SCENE; const EgsCamera cam = FWD_CAMERA;
     int rc = check_dims(P, width, height); if (rc) return rc;
     if (!num_rendered) return EGS_ERR_ARG;
     *num_rendered = 0;
     if (P == 0) return 0;
-    if (!means3D || !opacities || !viewmatrix || !projmatrix || !campos || !radii || !geom_buffer) return EGS_ERR_ARG;
     if (misaligned(geom_buffer)) return EGS_ERR_ARG;
-    rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
-    if (shs && (sh_degree < 0 || sh_degree > EGS_MAX_SH_DEGREE || sh_coeffs < (sh_degree + 1) * (sh_degree + 1))) return EGS_ERR_RANGE;
-    if (shs_rest && (!shs || sh_coeffs < 2)) return EGS_ERR_MODE;
+    EgsObjRot orot; MotionHost mh; rc = check_forward_scene(sc, cam, radii, geom_buffer, rot, orot, mh); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
     EgsGeomPtrs g = geom_ptrs(geom_buffer, P);
-    EgsCamera cam = { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy };
     egs_prof_start(EGS_K_PREPROCESS, s);
-    const bool sh_apart = shs && (sh_coeffs > 1 || shs_rest);         // rows of 12 M bytes: the wave-tiled kernel (preprocess.hip)
-    EGS_TRY(egs_launch_preprocess(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
-                                  rotations, activation_flags, cov3D_precomp, cam, radii, g, nullptr, 0, active_count, nullptr, orot, mh.k, s));
-    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, mh.k, s));
+    EGS_TRY(egs_launch_preprocess(sc, cam, radii, g, nullptr, 0, active_count, nullptr, orot, mh.k, s));
+    if (egs_sh_apart(sc)) EGS_TRY(egs_launch_sh_forward(sc, cam, g, mh.k, s));
     egs_prof_stop(EGS_K_PREPROCESS, s);
     EGS_SYNC_IF_DEBUG(s);
     // R = sum of the per-block instance counts (a few KB device->host; the only host wait of the forward)
@@ -325,52 +343,50 @@ int egs_forward_geometry(int P, int sh_degree, int sh_coeffs, const float* means
     return 0;
 }
 
+// One call of egs_forward / egs_forward_enqueue: the scene, the camera, and everything else the prototypes list (include/egs_raster.h)
+struct ForwardCall {
+    EgsScene sc; EgsCamera cam;
+    const float* background; int32_t* radii; void* geom_buffer; int64_t capacity; void* binning_buffer; void* image_buffer;
+    float* out_color; float* out_depth; float* out_alpha; uint32_t* pinned_host_counts;
+    bool wait_for_count;                 // egs_forward: the host waits for the instance count; egs_forward_enqueue: nothing waits (capturable)
+    uint64_t* running_max; int64_t* num_rendered; const int32_t* active_count; uint32_t* overflow_flag; void* placement;
+    const egs_object_rotation* rot; void* stream; int debug;
+};
 // One-call forward: preprocess, then -- without waiting for R -- the whole binning + blend chain is enqueued against
 // the caller's capacity guess while the host waits only for the copy of the per-block instance counts.  The GPU never
 // idles on the host round trip.  If the guess was too small nothing valid was produced: the true R is returned and the
 // caller finishes with egs_forward_render on a buffer of the right size.
-static int forward_impl(int wait_for_count, int P, int sh_degree, int sh_coeffs, const float* means3D, const float* shs, const float* shs_rest, const float* colors_precomp,
-                const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix, const float* campos,
-                const float* background, int width, int height, float tan_fovx, float tan_fovy, int prefiltered,
-                int32_t* radii, void* geom_buffer, int64_t capacity, void* binning_buffer, void* image_buffer,
-                float* out_color, float* out_depth, float* out_alpha, uint32_t* pinned_host_counts, uint64_t* running_max,
-                int64_t* num_rendered, const int32_t* active_count, uint32_t* overflow_flag, void* placement, const egs_object_rotation* rot,
-                void* stream, int debug) {
-    (void)prefiltered;
+static int forward_impl(const ForwardCall& c) {
+    const EgsScene& sc = c.sc; const EgsCamera& cam = c.cam;
+    const int P = sc.P, width = cam.W, height = cam.H, debug = c.debug;
+    const int64_t capacity = c.capacity;
+    void* const placement = c.placement; uint32_t* const pinned_host_counts = c.pinned_host_counts;
     int rc = check_dims(P, width, height); if (rc) return rc;
-    if (!num_rendered || capacity < 0 || capacity >= (1ll << 31)) return EGS_ERR_ARG;
-    *num_rendered = 0;
-    if (!background || !image_buffer || !out_color || ((out_depth != nullptr) != (out_alpha != nullptr))) return EGS_ERR_ARG;     // (depth and alpha: both or neither, ABI 4)
-    if (misaligned(geom_buffer, binning_buffer, image_buffer)) return EGS_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (P == 0) return egs_forward_render(0, 0, background, width, height, geom_buffer, binning_buffer, image_buffer, out_color,
-                                          out_depth, out_alpha, stream, debug);
-    if (!means3D || !opacities || !viewmatrix || !projmatrix || !campos || !radii || !geom_buffer) return EGS_ERR_ARG;
-    if (wait_for_count && !pinned_host_counts) return EGS_ERR_ARG;
-    if (capacity > 0 && !binning_buffer) return EGS_ERR_ARG;
-    if (!wait_for_count && capacity <= 0) return EGS_ERR_ARG;
-    rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
-    if (shs && (sh_degree < 0 || sh_degree > EGS_MAX_SH_DEGREE || sh_coeffs < (sh_degree + 1) * (sh_degree + 1))) return EGS_ERR_RANGE;
-    if (shs_rest && (!shs || sh_coeffs < 2)) return EGS_ERR_MODE;
-    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
+    if (!c.num_rendered || capacity < 0 || capacity >= (1ll << 31)) return EGS_ERR_ARG;
+    *c.num_rendered = 0;
+    if (!c.background || !c.image_buffer || !c.out_color || ((c.out_depth != nullptr) != (c.out_alpha != nullptr))) return EGS_ERR_ARG;     // (depth and alpha: both or neither, ABI 4)
+    if (misaligned(c.geom_buffer, c.binning_buffer, c.image_buffer)) return EGS_ERR_ARG;
+    hipStream_t s = (hipStream_t)c.stream;
+    if (P == 0) return egs_forward_render(0, 0, c.background, width, height, c.geom_buffer, c.binning_buffer, c.image_buffer, c.out_color,
+                                          c.out_depth, c.out_alpha, c.stream, debug);
+    if (c.wait_for_count && !pinned_host_counts) return EGS_ERR_ARG;
+    if (capacity > 0 && !c.binning_buffer) return EGS_ERR_ARG;
+    if (!c.wait_for_count && capacity <= 0) return EGS_ERR_ARG;
+    EgsObjRot orot; MotionHost mh; rc = check_forward_scene(sc, cam, c.radii, c.geom_buffer, c.rot, orot, mh); if (rc) return rc;
     static thread_local hipEvent_t ev = nullptr;
-    if (wait_for_count && !ev) EGS_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    EgsGeomPtrs g = geom_ptrs(geom_buffer, P);
-    EgsCamera cam = { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy };
+    if (c.wait_for_count && !ev) EGS_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    EgsGeomPtrs g = geom_ptrs(c.geom_buffer, P);
     egs_prof_start(EGS_K_PREPROCESS, s);
-    const bool sh_apart = shs && (sh_coeffs > 1 || shs_rest);         // rows of 12 M bytes: the wave-tiled kernel (preprocess.hip)
     // the speculative bucketing that follows needs its chunk sums cleared: the preprocess launch does that on the side (a launch of
     // its own costs ~4.5 us of GPU time whatever it does)
     EgsBinPtrs b_spec = {};
     size_t n_sums = 0;
     if (capacity > 0) {
-        b_spec = bin_ptrs(binning_buffer, P, capacity, width, height);
-        const size_t nt = (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
-        n_sums = EGS_BIN_GROUPS * egs_table_chunks(nt, egs_table_stride(egs_bin_blocks(P)));
+        b_spec = bin_ptrs(c.binning_buffer, P, capacity, width, height);
+        n_sums = EGS_BIN_GROUPS * egs_table_chunks(egs_tiles(width, height), egs_table_stride(egs_bin_blocks(P)));
     }
     // ... and carries the placement of the forward blend's tiles (backward_prologue.h), computed from the costs the image buffer holds
-    EgsImgPtrs im_spec = img_ptrs(image_buffer, width, height);
+    EgsImgPtrs im_spec = img_ptrs(c.image_buffer, width, height);
     placement_ptrs(placement, width, height, im_spec);
     // With a persistent placement buffer the count pass of the bucketing rides in the preprocess launch (k_preprocess_count) and adds its
     // chunk sums into that buffer's sums region, which is zero between frames (egs_common.h EgsBinPtrs); egs_debug_set_fused_count: A/B switch
@@ -380,44 +396,44 @@ static int forward_impl(int wait_for_count, int P, int sh_degree, int sh_coeffs,
         dirty_guard.p = placement; dirty_guard.w = width; dirty_guard.h = height; dirty_guard.s = s;      // (disarmed once the bucketing chain is enqueued)
         placement_sums(placement, width, height, &b_spec.chunk_sum, &b_spec.zero_after_n);
         b_spec.zero_after = b_spec.chunk_sum;
-        EGS_TRY(egs_launch_preprocess_count(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
-                                            rotations, activation_flags, cov3D_precomp, cam, radii, g, b_spec, active_count, &im_spec, orot, mh.k, cull_on(debug), s));
+        EGS_TRY(egs_launch_preprocess_count(sc, cam, c.radii, g, b_spec, c.active_count, &im_spec, orot, mh.k, cull_on(debug), s));
     } else
-    EGS_TRY(egs_launch_preprocess(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, colors_precomp, opacities, scales, scale_modifier,
-                                  rotations, activation_flags, cov3D_precomp, cam, radii, g, capacity > 0 ? b_spec.chunk_sum : nullptr, n_sums,
-                                  active_count, (capacity > 0 && placement) ? &im_spec : nullptr, orot, mh.k, s));
-    if (sh_apart) EGS_TRY(egs_launch_sh_forward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, g, mh.k, s));
+    EGS_TRY(egs_launch_preprocess(sc, cam, c.radii, g, capacity > 0 ? b_spec.chunk_sum : nullptr, n_sums, c.active_count,
+                                  (capacity > 0 && placement) ? &im_spec : nullptr, orot, mh.k, s));
+    if (egs_sh_apart(sc)) EGS_TRY(egs_launch_sh_forward(sc, cam, g, mh.k, s));
     egs_prof_stop(EGS_K_PREPROCESS, s);
     const size_t nb = ((size_t)P + 255) / 256;
     if (pinned_host_counts) EGS_TRY(hipMemcpyAsync(pinned_host_counts, g.scan_scratch, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (wait_for_count) EGS_TRY(hipEventRecord(ev, s));
+    if (c.wait_for_count) EGS_TRY(hipEventRecord(ev, s));
     if (capacity > 0) {                                              // speculative: sized by the caller's guess
         EgsBinPtrs b = b_spec;
         EgsImgPtrs im = im_spec;
         // the per-tile sort inside the forward blend's launch (render_fwd.hip SORT): egs_launch_binning then makes no sort launch and says what the
         // blend needs; with the sums of a fused count pass to clear, a failure before the blend is enqueued leaves them dirty (dirty_guard)
         EgsSortArgs sort_args = {};
-        EGS_TRY(egs_launch_binning(P, capacity, width, height, g, b, im, running_max, overflow_flag, 1, fuse ? 1 : 0,
+        EGS_TRY(egs_launch_binning(P, capacity, width, height, g, b, im, c.running_max, c.overflow_flag, 1, fuse ? 1 : 0,
                                    !(debug & EGS_CALL_SEPARATE_SORT) ? &sort_args : nullptr, s, debug & ~EGS_CALL_SYNC));      // (speculative chain: never synchronised mid-way)
         egs_prof_start(EGS_K_RENDER_FWD, s);
-        EGS_TRY(egs_launch_render_forward(width, height, background, g, b.point_list, im, out_color, out_depth, out_alpha, placement ? 1 : 0, &sort_args, s));
+        EGS_TRY(egs_launch_render_forward(width, height, c.background, g, b.point_list, im, c.out_color, c.out_depth, c.out_alpha, placement ? 1 : 0, &sort_args, s));
         dirty_guard.p = nullptr;
         egs_prof_stop(EGS_K_RENDER_FWD, s);
         // a caller that checks LATER (egs_forward_enqueue outside a graph: the eager loop without a host wait per forward) also gets the
         // overflow word -- [0] clipped, [1] instances bucketed -- behind the counts, once the chain that writes it has run
-        if (!wait_for_count && pinned_host_counts && overflow_flag)
-            EGS_TRY(hipMemcpyAsync(pinned_host_counts + nb, overflow_flag, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (!c.wait_for_count && pinned_host_counts && c.overflow_flag)
+            EGS_TRY(hipMemcpyAsync(pinned_host_counts + nb, c.overflow_flag, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
-    if (!wait_for_count) { *num_rendered = -1; return 0; }              // graph-capturable: no host wait at all
+    if (!c.wait_for_count) { *c.num_rendered = -1; return 0; }          // graph-capturable: no host wait at all
     EGS_TRY(hipEventSynchronize(ev));
     uint64_t R = 0;
     for (size_t k = 0; k < nb; k++) R += pinned_host_counts[k];
     if (R >= (1ull << 31)) return EGS_ERR_RANGE;
-    *num_rendered = (int64_t)R;
+    *c.num_rendered = (int64_t)R;
     if ((int64_t)R > capacity || capacity == 0) return EGS_RETRY_LARGER;       // caller: egs_forward_render with a buffer for R
     EGS_SYNC_IF_DEBUG(s);
     return 0;
 }
+// ... the run the two one-call forwards share after the scene and the camera
+#define FWD_RENDER background, radii, geom_buffer, capacity, binning_buffer, image_buffer, out_color, out_depth, out_alpha, pinned_host_counts
 
 int egs_forward(int P, int sh_degree, int sh_coeffs, const float* means3D, const float* shs, const float* shs_rest, const float* colors_precomp,
                 const float* opacities, const float* scales, float scale_modifier, const float* rotations,
@@ -426,10 +442,8 @@ int egs_forward(int P, int sh_degree, int sh_coeffs, const float* means3D, const
                 int32_t* radii, void* geom_buffer, int64_t capacity, void* binning_buffer, void* image_buffer,
                 float* out_color, float* out_depth, float* out_alpha, uint32_t* pinned_host_counts, int64_t* num_rendered,
                 const int32_t* active_count, void* placement, const egs_object_rotation* rot, void* stream, int debug) {
-    return forward_impl(1, P, sh_degree, sh_coeffs, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, background, width, height, tan_fovx, tan_fovy, prefiltered,
-                        radii, geom_buffer, capacity, binning_buffer, image_buffer, out_color, out_depth, out_alpha,
-                        pinned_host_counts, nullptr, num_rendered, active_count, nullptr, placement, rot, stream, debug);
+    (void)prefiltered;
+    return forward_impl({ FWD_SCENE, FWD_CAMERA, FWD_RENDER, true, nullptr, num_rendered, active_count, nullptr, placement, rot, stream, debug });
 }
 
 // Same chain with NO host wait: everything is only enqueued, so the call can be captured into a hipGraph.  Overflow of
@@ -443,12 +457,14 @@ int egs_forward_enqueue(int P, int sh_degree, int sh_coeffs, const float* means3
                         int32_t* radii, void* geom_buffer, int64_t capacity, void* binning_buffer, void* image_buffer,
                         float* out_color, float* out_depth, float* out_alpha, uint32_t* pinned_host_counts, uint64_t* running_max,
                         const int32_t* active_count, uint32_t* overflow_flag, void* placement, const egs_object_rotation* rot, void* stream, int flags) {
+    (void)prefiltered;
     int64_t unused = 0;
-    return forward_impl(0, P, sh_degree, sh_coeffs, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, background, width, height, tan_fovx, tan_fovy, prefiltered,
-                        radii, geom_buffer, capacity, binning_buffer, image_buffer, out_color, out_depth, out_alpha,
-                        pinned_host_counts, running_max, &unused, active_count, overflow_flag, placement, rot, stream, flags & ~EGS_CALL_SYNC);      // (nothing may wait: capturable)
+    return forward_impl({ FWD_SCENE, FWD_CAMERA, FWD_RENDER, false, running_max, &unused, active_count, overflow_flag, placement, rot, stream,
+                          flags & ~EGS_CALL_SYNC });                   // (nothing may wait: capturable)
 }
+#undef FWD_RENDER
+#undef FWD_CAMERA
+#undef FWD_SCENE
 
 int64_t egs_sum_counts(int P, const uint32_t* pinned_host_counts) {
     if (P <= 0 || !pinned_host_counts) return 0;
@@ -504,85 +520,90 @@ static int obj_loss_args(const egs_object_loss* o, int channels, int height, int
     return 0;
 }
 
-static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
-                 const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
-                 const float* rotations, const float* cov3D_precomp, int activation_flags, const float* viewmatrix, const float* projmatrix,
-                 const float* campos, int width, int height, float tan_fovx, float tan_fovy, const int32_t* radii,
-                 const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
-                 const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_alpha, float* dL_dmeans2D,
-                 float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest,
-                 float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
-                 const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
-                 void* stream, int debug, const egs_loss_grad* loss_grad = nullptr, const egs_object_loss* obj_loss = nullptr,
-                 const egs_opacity_entropy* entropy = nullptr) {
+// ---- the backwards: one record for the call -------------------------------------------------------------------------------------------
+// One call of any of the five rasterizer backwards (include/egs_raster.h): the scene, the camera, the forward's buffers, the upstream
+// gradients, where the gradients and statistics go, the fused optimizer and the loss terms an entry point may add (NULL: not this route).
+struct BackwardCall {
+    EgsScene sc; EgsCamera cam;
+    const float* background; int64_t R; const int32_t* radii; const void* geom_buffer; const void* binning_buffer; const void* image_buffer;
+    const float* dL_dout_color; const float* dL_dout_depth; const float* dL_dout_alpha;
+    EgsGrads d; EgsStats st;
+    const egs_adam_sink* sink; int prologue_done; const egs_object_rotation* rot; int grad_mask; void* scratch; void* stream; int debug;
+    const egs_loss_grad* loss_grad; const egs_object_loss* obj_loss; const egs_opacity_entropy* entropy;
+};
+static int backward_impl(const BackwardCall& c) {
+    const EgsScene& sc = c.sc; const EgsCamera& cam = c.cam; const EgsGrads& d = c.d; const EgsStats& st = c.st;
+    const int P = sc.P, width = cam.W, height = cam.H, debug = c.debug;
+    const int64_t R = c.R;
+    const egs_adam_sink* sink = c.sink; const egs_opacity_entropy* entropy = c.entropy;
+    const float* dL_dout_color = c.dL_dout_color;
+    hipStream_t s = (hipStream_t)c.stream;
     int rc = check_dims(P, width, height); if (rc) return rc;
-    if (activation_flags & EGS_ACT_SCALAR_COLOR) return EGS_ERR_MODE;  // a scalar colour's gradient is egs_backward_label's: dL_dcolors here is [P,3]
+    if (sc.act & EGS_ACT_SCALAR_COLOR) return EGS_ERR_MODE;           // a scalar colour's gradient is egs_backward_label's: dL_dcolors here is [P,3]
     // the opacity-entropy term (egs_backward_entropy_lossgrad): the static stages' -- no object motion, and the opacities must get their gradient
     if (entropy) {
-        if (!entropy->weight || !entropy->n_vis || (P > 0 && !entropy->scratch) || obj_loss) return EGS_ERR_ARG;
-        if (activation_flags & EGS_ACT_OBJECT_MOTION) return EGS_ERR_MODE;
+        if (!entropy->weight || !entropy->n_vis || (P > 0 && !entropy->scratch) || c.obj_loss) return EGS_ERR_ARG;
+        if (sc.act & EGS_ACT_OBJECT_MOTION) return EGS_ERR_MODE;
     }
-    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(activation_flags, rot, scales, P, orot, mh); if (rc) return rc;
+    EgsObjRot orot; MotionHost mh; rc = obj_motion_args(sc, c.rot, orot, mh); if (rc) return rc;
     // the image loss's gradient computed by the blend itself (egs_backward_lossgrad): colour gradients only, three channels
     EgsLossGradHost lgh = {}; const EgsLossGradHost* lgp = nullptr; EgsObjLossK olk = {};
-    if (obj_loss && !loss_grad) return EGS_ERR_ARG;
-    if (loss_grad) {
-        const egs_loss_grad& q = *loss_grad;
+    if (c.obj_loss && !c.loss_grad) return EGS_ERR_ARG;
+    if (c.loss_grad) {
+        const egs_loss_grad& q = *c.loss_grad;
         if (!q.image || !q.gt || !q.dm_dmu1 || !q.dm_dexx || !q.dm_dexy || !q.upstream_grad) return EGS_ERR_ARG;
-        if (dL_dout_depth || dL_dout_alpha || (grad_mask == EGS_GRAD_COLORS && colors_precomp && !sink && !stat_grad_accum)) return EGS_ERR_MODE;
+        if (c.dL_dout_depth || c.dL_dout_alpha || (c.grad_mask == EGS_GRAD_COLORS && sc.colors && !sink && !st.grad_accum)) return EGS_ERR_MODE;
         lgh = EgsLossGradHost{ q.image, q.gt, q.dm_dmu1, q.dm_dexx, q.dm_dexy, q.gate, q.upstream_grad, nullptr, 1.f - q.lambda_dssim, q.lambda_dssim,
                                q.deferred_partial_sums, q.deferred_partial_sums ? egs_l1_ssim_partial_count(3, height, width) / 2 : 0, q.lambda_dssim,
                                q.deferred_loss, q.deferred_partial_sums ? q.loss_running_sum : nullptr };
         lgp = &lgh;
         if (!dL_dout_color) dL_dout_color = q.image;                 // (never read: the checks below want a pointer)
-        if (obj_loss) {
+        if (c.obj_loss) {
             // the object stages' loss: the image weights carry lambda_image, the blend also forms dL/dalpha (k_render_backward<2, true>)
-            if (q.deferred_partial_sums && !obj_loss->alpha_partial_sums) return EGS_ERR_ARG;
-            rc = obj_loss_args(obj_loss, 3, height, width, q.lambda_dssim, olk); if (rc) return rc;
-            lgh.w_l1_n = obj_loss->lambda_image * (1.f - q.lambda_dssim); lgh.w_ssim_n = obj_loss->lambda_image * q.lambda_dssim;
+            if (q.deferred_partial_sums && !c.obj_loss->alpha_partial_sums) return EGS_ERR_ARG;
+            rc = obj_loss_args(c.obj_loss, 3, height, width, q.lambda_dssim, olk); if (rc) return rc;
+            lgh.w_l1_n = c.obj_loss->lambda_image * (1.f - q.lambda_dssim); lgh.w_ssim_n = c.obj_loss->lambda_image * q.lambda_dssim;
             lgh.obj = &olk;
         }
     }
     if (P == 0) {
-        if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, (hipStream_t)stream));
-        if (entropy) EGS_TRY(egs_launch_entropy_reduce(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, entropy->n_vis, entropy->value, (hipStream_t)stream));
-        if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, (hipStream_t)stream));
+        if (lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, s));
+        if (entropy) EGS_TRY(egs_launch_entropy_reduce(0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, entropy->n_vis, entropy->value, s));
+        if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, s));
         return 0;
     }
     if (R < 0 || R >= (1ll << 31)) return EGS_ERR_RANGE;
-    if (grad_mask & ~EGS_GRAD_MASK_BITS) return EGS_ERR_ARG;
+    if (c.grad_mask & ~EGS_GRAD_MASK_BITS) return EGS_ERR_ARG;
     // Only the precomputed colours' gradient is wanted (the reference's label call): a blend that sums w dL/dC alone, no preprocess backward
-    const bool colors_only = grad_mask == EGS_GRAD_COLORS && colors_precomp && !sink && !stat_grad_accum;
-    if (!background || !means3D || !viewmatrix || !projmatrix || !campos || !radii || !geom_buffer || !image_buffer ||
-        !dL_dout_color || (!dL_dmeans2D && !colors_only) || !scratch)
+    const bool colors_only = c.grad_mask == EGS_GRAD_COLORS && sc.colors && !sink && !st.grad_accum;
+    if (!c.background || lacks_pointers(sc, cam, c.radii, c.geom_buffer) || !c.image_buffer || !dL_dout_color || (!d.means2D && !colors_only) || !c.scratch)
         return EGS_ERR_ARG;
-    if (misaligned(geom_buffer, binning_buffer, image_buffer) || ((uintptr_t)scratch & 15u)) return EGS_ERR_ARG;
+    if (misaligned(c.geom_buffer, c.binning_buffer, c.image_buffer) || ((uintptr_t)c.scratch & 15u)) return EGS_ERR_ARG;
+    EgsGeomPtrs g = geom_ptrs(const_cast<void*>(c.geom_buffer), P);
+    float* grad_acc = (float*)c.scratch;
     if (colors_only) {
         if (entropy) return EGS_ERR_MODE;                             // (no opacity gradient on this path)
-        if (!dL_dcolors || (R > 0 && !binning_buffer)) return EGS_ERR_ARG;
-        rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
-        hipStream_t s = (hipStream_t)stream;
-        EgsGeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
-        float* grad_acc = (float*)scratch;
-        if (R == 0) return (int)egs_launch_zero_u32((uint32_t*)dL_dcolors, (size_t)P * 3, s);
-        EgsBinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), P, R, width, height);
-        EgsImgPtrs im = img_ptrs(const_cast<void*>(image_buffer), width, height);
-        if (!prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, nullptr, s));
+        if (!d.colors || (R > 0 && !c.binning_buffer)) return EGS_ERR_ARG;
+        rc = check_modes(sc); if (rc) return rc;
+        if (R == 0) return (int)egs_launch_zero_u32((uint32_t*)d.colors, (size_t)P * 3, s);
+        EgsBinPtrs b = bin_ptrs(const_cast<void*>(c.binning_buffer), P, R, width, height);
+        EgsImgPtrs im = img_ptrs(const_cast<void*>(c.image_buffer), width, height);
+        if (!c.prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, nullptr, s));
         egs_prof_start(EGS_K_RENDER_BWD, s);
-        EGS_TRY(egs_launch_render_backward(P, width, height, background, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 1, nullptr, s));
+        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 1, nullptr, s));
         egs_prof_stop(EGS_K_RENDER_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
         egs_prof_start(EGS_K_PREPROCESS_BWD, s);
-        EGS_TRY(egs_launch_colors_from_acc(P, grad_acc, g.clamped, radii, dL_dcolors, s));
+        EGS_TRY(egs_launch_colors_from_acc(P, grad_acc, g.clamped, c.radii, d.colors, s));
         if (mh.grad) EGS_TRY(egs_launch_zero_u32((uint32_t*)mh.grad, EGS_MOTION_SUMS, s));       // (the positions carry no gradient on this path)
         egs_prof_stop(EGS_K_PREPROCESS_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
         return 0;
     }
     // leaves a fused optimizer owns: their gradient arrays are optional
-    const bool sh_apart = shs && (sh_coeffs > 1 || shs_rest);
+    const bool sh_apart = egs_sh_apart(sc);
     bool own[EGS_SINK_LEAVES] = { false, false, false, false, false, false };
-    const bool sh_sink_ok = sh_apart && egs_sh_backward_can_sink(sh_coeffs, shs, shs_rest);      // the split M = 16 kernel steps dc / rest / positions
+    const bool sh_sink_ok = sh_apart && egs_sh_backward_can_sink(sc.M, sc.shs, sc.shs_rest);      // the split M = 16 kernel steps dc / rest / positions
     if (sink) {
         if (!sink->coef) return EGS_ERR_ARG;
         for (int l = 0; l < EGS_SINK_LEAVES; l++) {
@@ -590,36 +611,33 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
             own[l] = f.param != nullptr;
             if (own[l] && (!f.exp_avg || !f.exp_avg_sq || !f.lr || !f.step)) return EGS_ERR_ARG;
         }
-        if ((own[EGS_SINK_SCALES] || own[EGS_SINK_ROTATIONS]) && cov3D_precomp) return EGS_ERR_MODE;
-        if (own[EGS_SINK_SH] && (!shs || (sh_apart && !sh_sink_ok))) return EGS_ERR_MODE;
-        if (own[EGS_SINK_SH_REST] && (!sh_sink_ok || sink->leaf[EGS_SINK_SH_REST].param != shs_rest)) return EGS_ERR_MODE;
-        if (own[EGS_SINK_MEANS3D] && sh_apart && (!sh_sink_ok || !dL_dmeans3D)) return EGS_ERR_MODE;
-        if (sh_apart && (own[EGS_SINK_SH] || own[EGS_SINK_SH_REST]) && ((dL_dsh != nullptr) != (dL_dsh_rest != nullptr))) return EGS_ERR_ARG;
-        if ((own[EGS_SINK_MEANS3D] && sink->leaf[EGS_SINK_MEANS3D].param != means3D) || (own[EGS_SINK_SCALES] && sink->leaf[EGS_SINK_SCALES].param != scales) ||
-            (own[EGS_SINK_ROTATIONS] && sink->leaf[EGS_SINK_ROTATIONS].param != rotations) || (own[EGS_SINK_SH] && sink->leaf[EGS_SINK_SH].param != shs))
+        if ((own[EGS_SINK_SCALES] || own[EGS_SINK_ROTATIONS]) && sc.cov3D) return EGS_ERR_MODE;
+        if (own[EGS_SINK_SH] && (!sc.shs || (sh_apart && !sh_sink_ok))) return EGS_ERR_MODE;
+        if (own[EGS_SINK_SH_REST] && (!sh_sink_ok || sink->leaf[EGS_SINK_SH_REST].param != sc.shs_rest)) return EGS_ERR_MODE;
+        if (own[EGS_SINK_MEANS3D] && sh_apart && (!sh_sink_ok || !d.means3D)) return EGS_ERR_MODE;
+        if (sh_apart && (own[EGS_SINK_SH] || own[EGS_SINK_SH_REST]) && ((d.sh != nullptr) != (d.sh_rest != nullptr))) return EGS_ERR_ARG;
+        if ((own[EGS_SINK_MEANS3D] && sink->leaf[EGS_SINK_MEANS3D].param != sc.means3D) || (own[EGS_SINK_SCALES] && sink->leaf[EGS_SINK_SCALES].param != sc.scales) ||
+            (own[EGS_SINK_ROTATIONS] && sink->leaf[EGS_SINK_ROTATIONS].param != sc.rots) || (own[EGS_SINK_SH] && sink->leaf[EGS_SINK_SH].param != sc.shs))
             return EGS_ERR_ARG;
     }
-    if ((!dL_dcolors && (colors_precomp || sh_apart)) || (!dL_dopacity && !own[EGS_SINK_OPACITY]) || (!dL_dmeans3D && !own[EGS_SINK_MEANS3D]))
+    if ((!d.colors && (sc.colors || sh_apart)) || (!d.opacity && !own[EGS_SINK_OPACITY]) || (!d.means3D && !own[EGS_SINK_MEANS3D]))
         return EGS_ERR_ARG;
-    if (R > 0 && !binning_buffer) return EGS_ERR_ARG;
-    rc = check_modes(shs, colors_precomp, scales, rotations, cov3D_precomp, activation_flags); if (rc) return rc;
-    if (shs && !dL_dsh && !own[EGS_SINK_SH]) return EGS_ERR_ARG;
-    if (sh_apart && !dL_dsh && !(own[EGS_SINK_SH] && (own[EGS_SINK_SH_REST] || !shs_rest))) return EGS_ERR_ARG;
-    if (shs_rest && (!shs || sh_coeffs < 2)) return EGS_ERR_MODE;
-    if (!shs_rest && dL_dsh_rest) return EGS_ERR_ARG;
-    if (shs_rest && !dL_dsh_rest && !own[EGS_SINK_SH_REST]) return EGS_ERR_ARG;
-    if ((stat_grad_accum != nullptr) != (stat_denom != nullptr) || (stat_max_radii && !stat_grad_accum)) return EGS_ERR_ARG;
-    if (!cov3D_precomp && ((!dL_dscales && !own[EGS_SINK_SCALES]) || (!dL_drotations && !own[EGS_SINK_ROTATIONS]))) return EGS_ERR_ARG;
-    if (cov3D_precomp && !dL_dcov3D) return EGS_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    EgsGeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
-    EgsBinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), P, R, width, height);
-    EgsImgPtrs im = img_ptrs(const_cast<void*>(image_buffer), width, height);
-    float* grad_acc = (float*)scratch;
+    if (R > 0 && !c.binning_buffer) return EGS_ERR_ARG;
+    rc = check_modes(sc); if (rc) return rc;
+    if (sc.shs && !d.sh && !own[EGS_SINK_SH]) return EGS_ERR_ARG;
+    if (sh_apart && !d.sh && !(own[EGS_SINK_SH] && (own[EGS_SINK_SH_REST] || !sc.shs_rest))) return EGS_ERR_ARG;
+    if (split_sh_malformed(sc)) return EGS_ERR_MODE;
+    if (!sc.shs_rest && d.sh_rest) return EGS_ERR_ARG;
+    if (sc.shs_rest && !d.sh_rest && !own[EGS_SINK_SH_REST]) return EGS_ERR_ARG;
+    if ((st.grad_accum != nullptr) != (st.denom != nullptr) || (st.max_radii && !st.grad_accum)) return EGS_ERR_ARG;
+    if (!sc.cov3D && ((!d.scales && !own[EGS_SINK_SCALES]) || (!d.rotations && !own[EGS_SINK_ROTATIONS]))) return EGS_ERR_ARG;
+    if (sc.cov3D && !d.cov3D) return EGS_ERR_ARG;
+    EgsBinPtrs b = bin_ptrs(const_cast<void*>(c.binning_buffer), P, R, width, height);
+    EgsImgPtrs im = img_ptrs(const_cast<void*>(c.image_buffer), width, height);
     EgsSink ks = {}, ks_sh = {}; EgsAdamTick tick = {};
     bool pp_sinks = false, sh_sinks = false;
     if (sink) {
-        sink_to_kernel_args(sink, skip_flag, ks, tick);
+        sink_to_kernel_args(sink, st.skip_flag, ks, tick);
         ks_sh = ks;
         for (int l = 0; l < EGS_SINK_LEAVES; l++) {                    // who finishes which gradient: the spherical-harmonics launch, or the one before it
             const bool by_sh = sh_apart && (l == EGS_SINK_SH || l == EGS_SINK_SH_REST || l == EGS_SINK_MEANS3D);
@@ -628,34 +646,27 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
         }
     }
     // the accumulator is cleared by a kernel, not a memset node (see egs_launch_zero_f4): fused into the blend's prologue
-    if (R == 0 && !prologue_done) {
+    if (R == 0 && !c.prologue_done) {
         EGS_TRY(egs_launch_zero_f4((float4*)grad_acc, egs_acc_floats((size_t)P) / 4, s));
         if (sink) EGS_TRY(egs_launch_adam_tick(tick, s));
     }
     if (R == 0 && lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, s));
     if (R > 0) {
-        const uint32_t* point_list = b.point_list;
-        if (!prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, sink ? &tick : nullptr, s));
+        if (!c.prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, sink ? &tick : nullptr, s));
         egs_prof_start(EGS_K_RENDER_BWD, s);                         // (the stage is the blend kernel alone)
-        EGS_TRY(egs_launch_render_backward(P, width, height, background, g, point_list, im, dL_dout_color, dL_dout_depth, dL_dout_alpha, grad_acc, 0, lgp, s));
+        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, c.dL_dout_depth, c.dL_dout_alpha, grad_acc, 0, lgp, s));
         egs_prof_stop(EGS_K_RENDER_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
     }
     egs_prof_start(EGS_K_PREPROCESS_BWD, s);
-    EgsCamera cam = { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy };
     // the entropy term: n_vis and the value from the records and radii of this frame, then the instantiation that adds the rows' shares
     EgsEntropy ek = {};
     if (entropy) {
-        EGS_TRY(egs_launch_entropy_reduce(P, nullptr, g.rec, 0, radii, nullptr, nullptr, entropy->scratch, entropy->n_vis, entropy->value, s));
+        EGS_TRY(egs_launch_entropy_reduce(P, nullptr, g.rec, 0, c.radii, nullptr, nullptr, entropy->scratch, entropy->n_vis, entropy->value, s));
         ek = EgsEntropy{ entropy->n_vis, entropy->weight, entropy->upstream };
     }
-    EGS_TRY(egs_launch_preprocess_backward(P, sh_degree, sh_coeffs, means3D, sh_apart ? nullptr : shs, scales, scale_modifier, rotations,
-                                           cov3D_precomp, activation_flags, cam, radii, g, grad_acc, colors_precomp != nullptr, dL_dmeans2D,
-                                           dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, sh_apart ? nullptr : dL_dsh, dL_dscales,
-                                           dL_drotations, stat_grad_accum, stat_denom, stat_max_radii, skip_flag, pp_sinks ? &ks : nullptr, orot, mh.k,
-                                           sh_apart ? 1 : 0, s, entropy ? &ek : nullptr));
-    if (sh_apart) EGS_TRY(egs_launch_sh_backward(P, sh_degree, sh_coeffs, means3D, shs, shs_rest, cam, radii, g, dL_dcolors, dL_dsh,
-                                                 dL_dsh_rest, dL_dmeans3D, sh_sinks ? &ks_sh : nullptr, mh.k, s));
+    EGS_TRY(egs_launch_preprocess_backward(sc, cam, c.radii, g, grad_acc, d, st, pp_sinks ? &ks : nullptr, orot, mh.k, s, entropy ? &ek : nullptr));
+    if (sh_apart) EGS_TRY(egs_launch_sh_backward(sc, cam, c.radii, g, d, sh_sinks ? &ks_sh : nullptr, mh.k, s));
     // the pose gradient: the lines the launch that finished the positions' gradient wrote (one per 64 rows from the spherical-harmonics
     // launch, per 256 otherwise), and the rotation lines of the preprocess backward, added up by one workgroup
     if (mh.grad) EGS_TRY(egs_launch_motion_finish(mh.k.pose_partial, (int)(sh_apart ? egs_motion_pose_lines_max(P) : egs_motion_rot_lines(P)),
@@ -664,6 +675,14 @@ static int backward_impl(int P, int sh_degree, int sh_coeffs, int64_t R, const f
     EGS_SYNC_IF_DEBUG(s);
     return 0;
 }
+
+// The five backwards name their shared parameters alike (include/egs_raster.h): the runs each copies into its call record.  Between
+// BWD_SCENE and BWD_OUTPUTS stands what an entry point has of its own -- upstream gradients, or the loss whose gradient the blend forms.
+#define BWD_SCENE { P, sh_degree, sh_coeffs, means3D, shs, shs_rest, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp, activation_flags }, \
+                  { viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy }, background, R, radii, geom_buffer, binning_buffer, image_buffer
+#define BWD_OUTPUTS { dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations }, \
+                    { stat_grad_accum, stat_denom, stat_max_radii, skip_flag }
+#define BWD_SINK_TAIL sink, prologue_done, rot, grad_mask, scratch, stream, debug
 
 int egs_backward(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
                  const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
@@ -676,11 +695,8 @@ int egs_backward(int P, int sh_degree, int sh_coeffs, int64_t R, const float* ba
                  const uint32_t* skip_flag, int grad_mask, void* scratch, void* stream, int debug) {
     if (grad_mask == EGS_GRAD_COLORS && colors_precomp && !stat_grad_accum) { if (!dL_dcolors) return P == 0 ? 0 : EGS_ERR_ARG; }
     else if (!dL_dcolors || !dL_dopacity || !dL_dmeans3D) return P == 0 ? 0 : EGS_ERR_ARG;
-    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
-                         binning_buffer, image_buffer, dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
-                         skip_flag, nullptr, 0, nullptr, grad_mask, scratch, stream, debug);
+    return backward_impl({ BWD_SCENE, dL_dout_color, dL_dout_depth, dL_dout_alpha, BWD_OUTPUTS, nullptr, 0, nullptr, grad_mask, scratch, stream, debug,
+                           nullptr, nullptr, nullptr });
 }
 
 int egs_backward_adam(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
@@ -693,11 +709,7 @@ int egs_backward_adam(int P, int sh_degree, int sh_coeffs, int64_t R, const floa
                       float* dL_dscales, float* dL_drotations, float* stat_grad_accum, float* stat_denom, float* stat_max_radii,
                       const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
                       void* stream, int debug) {
-    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
-                         binning_buffer, image_buffer, dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
-                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug);
+    return backward_impl({ BWD_SCENE, dL_dout_color, dL_dout_depth, dL_dout_alpha, BWD_OUTPUTS, BWD_SINK_TAIL, nullptr, nullptr, nullptr });
 }
 
 int egs_backward_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
@@ -710,11 +722,7 @@ int egs_backward_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const 
                           const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
                           void* stream, int debug) {
     if (!loss_grad) return EGS_ERR_ARG;
-    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
-                         binning_buffer, image_buffer, nullptr, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
-                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad);
+    return backward_impl({ BWD_SCENE, nullptr, nullptr, nullptr, BWD_OUTPUTS, BWD_SINK_TAIL, loss_grad, nullptr, nullptr });
 }
 
 int egs_backward_entropy_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R, const float* background, const float* means3D,
@@ -729,11 +737,7 @@ int egs_backward_entropy_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R
                           void* stream, int debug) {
     if (!entropy) return EGS_ERR_ARG;
     if (loss_grad && (dL_dout_color || dL_dout_depth || dL_dout_alpha)) return EGS_ERR_MODE;      // (the blend forms the image gradient itself)
-    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
-                         binning_buffer, image_buffer, dL_dout_color, dL_dout_depth, dL_dout_alpha, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
-                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad, nullptr, entropy);
+    return backward_impl({ BWD_SCENE, dL_dout_color, dL_dout_depth, dL_dout_alpha, BWD_OUTPUTS, BWD_SINK_TAIL, loss_grad, nullptr, entropy });
 }
 
 // egs_backward_prologue (HOST struct) -> the side jobs a loss backward launch carries
@@ -741,7 +745,7 @@ static int prologue_args(const egs_backward_prologue* side, EgsPrologueArgs& pa)
     int rc = check_dims(side->P, side->width, side->height); if (rc) return rc;
     if (side->P <= 0 || !side->image_buffer || !side->scratch) return EGS_ERR_ARG;
     EgsImgPtrs im = img_ptrs(side->image_buffer, side->width, side->height);
-    pa.n_tiles = ((side->width + EGS_TILE - 1) / EGS_TILE) * ((side->height + EGS_TILE - 1) / EGS_TILE);
+    pa.n_tiles = (int)egs_tiles(side->width, side->height);
     pa.quad_work = im.quad_work; pa.tile_order = im.tile_order;
     if (side->geom_buffer && misaligned(side->geom_buffer)) return EGS_ERR_ARG;
     egs_prologue_acc(pa, (float*)side->scratch, (size_t)side->P,
@@ -820,17 +824,16 @@ int egs_backward_object_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R,
                           const uint32_t* skip_flag, const egs_adam_sink* sink, int prologue_done, const egs_object_rotation* rot, int grad_mask, void* scratch,
                           void* stream, int debug) {
     if (!loss_grad || !obj) return EGS_ERR_ARG;
-    return backward_impl(P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
-                         cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii, geom_buffer,
-                         binning_buffer, image_buffer, nullptr, nullptr, nullptr, dL_dmeans2D, dL_dcolors, dL_dopacity,
-                         dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscales, dL_drotations, stat_grad_accum, stat_denom, stat_max_radii,
-                         skip_flag, sink, prologue_done, rot, grad_mask, scratch, stream, debug, loss_grad, obj);
+    return backward_impl({ BWD_SCENE, nullptr, nullptr, nullptr, BWD_OUTPUTS, BWD_SINK_TAIL, loss_grad, obj, nullptr });
 }
+#undef BWD_SINK_TAIL
+#undef BWD_OUTPUTS
+#undef BWD_SCENE
 
 // ---- the label phase (include/egs_raster.h; label_loss.hip, render_bwd.hip k_render_backward<3>) ----
 size_t egs_label_bce_partial_count(int height, int width) {
     if (height <= 0 || width <= 0) return 0;
-    return (size_t)4 * (size_t)((width + EGS_TILE - 1) / EGS_TILE) * (size_t)((height + EGS_TILE - 1) / EGS_TILE);
+    return (size_t)4 * egs_tiles(width, height);
 }
 int egs_label_bce_forward(int height, int width, const float* img, const float* obj_mask, float* partial_sums, float* loss, float* loss_running_sum,
                           void* stream) {

@@ -161,35 +161,39 @@ struct EgsCamera {
     const float* view; const float* proj; const float* campos;
     int W, H; float tanfovx, tanfovy;
 };
-// `act`: activation flags of the raw-parameter mode (include/egs_raster.h: EGS_ACT_*)
+static inline size_t egs_tiles(int W, int H) { return (size_t)((W + EGS_TILE - 1) / EGS_TILE) * (size_t)((H + EGS_TILE - 1) / EGS_TILE); }
+// What a call says about the Gaussians (HOST record; the kernels keep their loose parameters): the sizes, the parameter arrays in whichever
+// mode the caller chose, the activation flags of the raw-parameter mode (include/egs_raster.h: EGS_ACT_*).  The backwards leave `opac` NULL:
+// their kernels read the activated opacity in the record.
+struct EgsScene {
+    int P, D, M;                       // Gaussians, SH degree, SH coefficients per channel in `shs` (+ `shs_rest`)
+    const float* means3D; const float* shs; const float* shs_rest; const float* colors; const float* opac;
+    const float* scales; float mod; const float* rots; const float* cov3D; int act;
+};
+// Spherical harmonics as launches of their own (M > 1 coefficients, or DC / rest given as two arrays; rows of 12 M bytes: the wave-tiled
+// kernels of preprocess.hip).  The preprocess kernels are then given shs = NULL: the forward leaves the record's colour open, the backward
+// leaves dL/dSH and the view-direction part of dL/dmean3D to egs_launch_sh_backward (which must run after it).
+static inline bool egs_sh_apart(const EgsScene& sc) { return sc.shs && (sc.M > 1 || sc.shs_rest); }
+// Where a backward writes (HOST record; members may be NULL as include/egs_raster.h says), and the densification statistics it updates
+struct EgsGrads { float* means2D; float* colors; float* opacity; float* means3D; float* cov3D; float* sh; float* sh_rest; float* scales; float* rotations; };
+struct EgsStats { float* grad_accum; float* denom; float* max_radii; const uint32_t* skip_flag; };
 // zero_words / zero_n: an unrelated region this launch also clears (the bucketing's chunk sums of the same frame; may be NULL)
-hipError_t egs_launch_preprocess(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
-                                 const float* opac, const float* scales, float mod, const float* rots, int act,
-                                 const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
+hipError_t egs_launch_preprocess(const EgsScene& sc, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
                                  const int32_t* active_count, const EgsImgPtrs* place /*NULL, or: also order im.fwd_cost into im.fwd_order*/,
                                  EgsObjRot rot, EgsMotion mot, hipStream_t s);
-hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* means3D, const float* shs,
-                                          const float* scales, float mod, const float* rots, const float* cov3D, int act,
-                                          EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const float* grad_acc,
-                                          int colors_given, float* dmeans2D, float* dcolors, float* dopac,
-                                          float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
-                                          float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
-                                          const EgsSink* sink /*NULL: gradients only*/, EgsObjRot rot, EgsMotion mot,
-                                          int motion_finished_later /*egs_launch_sh_backward follows and finishes the positions' gradient*/, hipStream_t s,
-                                          const struct EgsEntropy* ent = nullptr /*opacity_entropy.h: the entropy term's share of dL/dopacity is added before the sigmoid chain (no motion)*/);
+hipError_t egs_launch_preprocess_backward(const EgsScene& sc, EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const float* grad_acc,
+                                          const EgsGrads& d, const EgsStats& st, const EgsSink* sink /*NULL: gradients only*/, EgsObjRot rot, EgsMotion mot,
+                                          hipStream_t s, const struct EgsEntropy* ent = nullptr /*opacity_entropy.h: the entropy term's share of dL/dopacity is added before the sigmoid chain (no motion)*/);
 // The opacity-entropy reduction (entropy.hip): per-workgroup lines in `scratch`, then one finish workgroup -> *n_vis, *value (may be NULL).
 // rec != NULL: the activated opacities a rasterizer forward parked in its records (opac, logit, active_count, activated are not read).
 hipError_t egs_launch_entropy_reduce(int P, const float* opac, const float4* rec, int logit, const int32_t* radii, const int32_t* active_count,
                                      float* activated, void* scratch, uint32_t* n_vis, float* value, hipStream_t s);
-// Spherical harmonics as separate launches (M > 1 coefficients, or DC / rest given as two arrays: sh_rest != NULL).  The
-// preprocess launchers are then called with shs = NULL: the forward leaves the record's colour open, the backward leaves
-// dL/dSH and the view-direction part of dL/dmean3D to egs_launch_sh_backward (which must run after it).
-hipError_t egs_launch_sh_forward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                 EgsGeomPtrs g, EgsMotion mot, hipStream_t s);
-// sink (may be NULL; only with egs_sh_backward_can_sink): the Adam step of features_dc / features_rest / positions taken by this launch
-hipError_t egs_launch_sh_backward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                  const int32_t* radii, EgsGeomPtrs g, const float* dcolors, float* dsh_a, float* dsh_rest,
-                                  float* dmeans3D, const EgsSink* sink, EgsMotion mot, hipStream_t s);
+// The spherical-harmonics launches of a scene with egs_sh_apart().
+hipError_t egs_launch_sh_forward(const EgsScene& sc, EgsCamera cam, EgsGeomPtrs g, EgsMotion mot, hipStream_t s);
+// reads d.colors, writes d.sh, d.sh_rest, d.means3D; sink (may be NULL; only with egs_sh_backward_can_sink): the Adam step of features_dc /
+// features_rest / positions taken by this launch
+hipError_t egs_launch_sh_backward(const EgsScene& sc, EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const EgsGrads& d, const EgsSink* sink,
+                                  EgsMotion mot, hipStream_t s);
 bool egs_sh_backward_can_sink(int M, const float* sh_a, const float* sh_rest);      // the M = 16 split-array kernel will run
 hipError_t egs_launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
@@ -211,9 +215,7 @@ hipError_t egs_launch_binning(int P, int64_t R, int W, int H, EgsGeomPtrs g, Egs
 // k_preprocess + the count pass of the tile bucketing in ONE launch (preprocess.hip); b.chunk_sum must be ZERO (see EgsBinPtrs).
 // -> false when the launch geometry does not allow it (fewer than four groups per round: very large images)
 bool egs_can_fuse_count(int P, int W, int H, int cull);
-hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
-                                       const float* opac, const float* scales, float mod, const float* rots, int act,
-                                       const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
+hipError_t egs_launch_preprocess_count(const EgsScene& sc, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
                                        const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, int cull, hipStream_t s);
 // placed: im.fwd_order holds this frame's placement (the preprocess launch carried the ordering job); else the static mapping
 // sort (may be NULL, or table_scanned == NULL in it): the blend sorts every tile's bucket itself first (egs_launch_binning made no sort launch)

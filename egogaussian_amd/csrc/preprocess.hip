@@ -1371,25 +1371,29 @@ hipError_t egs_launch_zero_f4(float4* p, size_t n4, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t egs_launch_preprocess(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
-                                 const float* opac, const float* scales, float mod, const float* rots, int act,
-                                 const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
+// The leading arguments of the preprocess kernels, forward and backward, in the order all of them declare: written once.  `shs` is what the
+// kernel is given (NULL when the spherical harmonics run as launches of their own, and for the backward of precomputed colours).
+#define PP_SCENE sc.P, sc.D, sc.M, sc.means3D, shs
+#define PP_SHAPE_CAM sc.scales, sc.mod, sc.rots, sc.cov3D, sc.act, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.tanfovx, cam.tanfovy, radii
+// k_preprocess's loose parameters up to the region it clears; member for member the EgsPreArgs of k_preprocess_count up to active_count
+#define PP_ARGS PP_SCENE, sc.colors, sc.opac, PP_SHAPE_CAM, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot
+
+hipError_t egs_launch_preprocess(const EgsScene& sc, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
                                  const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, hipStream_t s) {
+    const int P = sc.P;
     if (P == 0) return hipSuccess;
     if (!zero_words) zero_n = 0;
+    const float* shs = egs_sh_apart(sc) ? nullptr : sc.shs;
     EgsPrologueArgs pa = {};
-#define PP_ARGS P, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.tanfovx, \
-                cam.tanfovy, radii, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot, zero_words, zero_n, active_count
     if (place) {
-        pa.n_tiles = ((cam.W + EGS_TILE - 1) / EGS_TILE) * ((cam.H + EGS_TILE - 1) / EGS_TILE);
+        pa.n_tiles = (int)egs_tiles(cam.W, cam.H);
         pa.quad_work = place->fwd_cost; pa.tile_order = place->fwd_order;
-        if (mot.A) hipLaunchKernelGGL((k_preprocess<true, true>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess<true, false>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<true, true>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<true, false>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
     } else {
-        if (mot.A) hipLaunchKernelGGL((k_preprocess<false, true>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess<false, false>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, pa, rot, mot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<false, true>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<false, false>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
     }
-#undef PP_ARGS
     return hipGetLastError();
 }
 
@@ -1402,13 +1406,12 @@ bool egs_can_fuse_count(int P, int W, int H, int cull) {
     if (!multi && bin_groups_per_block((unsigned)P, q.nblocks) > (unsigned)q.gpr) return false;
     return q.gpr >= 4 && q.gpr % 4 == 0 && q.lds >= sizeof(EgsOrderLds);
 }
-hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D, const float* shs, const float* colors,
-                                       const float* opac, const float* scales, float mod, const float* rots, int act,
-                                       const float* cov3D, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
+hipError_t egs_launch_preprocess_count(const EgsScene& sc, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, EgsBinPtrs b,
                                        const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, int cull, hipStream_t s) {
+    const int P = sc.P;
     const EgsBinGeometry q = egs_bin_geometry(P, cam.W, cam.H, cull);
-    EgsPreArgs a = { P, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.tanfovx, cam.tanfovy,
-                     radii, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot, active_count };
+    const float* shs = egs_sh_apart(sc) ? nullptr : sc.shs;
+    EgsPreArgs a = { PP_ARGS, active_count };
     EgsCountArgs c = { q.gpr, q.gx, q.n_tiles, q.nblocks, q.cull, q.use_map, b.table, q.stride, b.chunk_sum };
     EgsPrologueArgs pa = {};
     const unsigned grid = ((q.nblocks + 7) / 8) * 8;
@@ -1431,22 +1434,19 @@ hipError_t egs_launch_preprocess_count(int P, int D, int M, const float* means3D
     return hipGetLastError();
 }
 
-hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* means3D, const float* shs,
-                                          const float* scales, float mod, const float* rots, const float* cov3D, int act,
-                                          EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const float* grad_acc,
-                                          int colors_given, float* dmeans2D, float* dcolors, float* dopac,
-                                          float* dmeans3D, float* dcov3D, float* dsh, float* dscales, float* drots,
-                                          float* stat_grad_accum, float* stat_denom, float* stat_max_radii, const uint32_t* skip_flag,
-                                          const EgsSink* sink, EgsObjRot rot, EgsMotion mot, int motion_finished_later, hipStream_t s,
+// With split or M > 1 harmonics egs_launch_sh_backward follows and finishes the positions' gradient (the <.., 1> instantiations under motion).
+hipError_t egs_launch_preprocess_backward(const EgsScene& sc, EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const float* grad_acc,
+                                          const EgsGrads& d, const EgsStats& st, const EgsSink* sink, EgsObjRot rot, EgsMotion mot, hipStream_t s,
                                           const EgsEntropy* ent) {
+    const int P = sc.P;
     if (P == 0) return hipSuccess;
     if (ent && mot.A) return hipErrorInvalidValue;                   // (the entropy instantiations exist without object motion: the static stages)
     EgsSink none = {};
     const EgsNoEntropy no_ent = {};
-#define PPB_ARGS P, D, M, means3D, colors_given ? nullptr : shs, scales, mod, rots, cov3D, act, cam.view, cam.proj, cam.campos, cam.W, \
-                 cam.H, cam.tanfovx, cam.tanfovy, radii, g.clamped, g.rec, grad_acc, dmeans2D, dcolors, dopac, dmeans3D, \
-                 dcov3D, colors_given ? nullptr : dsh, cov3D ? nullptr : dscales, cov3D ? nullptr : drots, \
-                 stat_grad_accum, stat_denom, stat_max_radii, skip_flag
+    const bool motion_finished_later = egs_sh_apart(sc), own_sh = !sc.colors && !motion_finished_later;
+    const float* shs = own_sh ? sc.shs : nullptr;
+#define PPB_ARGS PP_SCENE, PP_SHAPE_CAM, g.clamped, g.rec, grad_acc, d.means2D, d.colors, d.opacity, d.means3D, d.cov3D, own_sh ? d.sh : nullptr, \
+                 sc.cov3D ? nullptr : d.scales, sc.cov3D ? nullptr : d.rotations, st.grad_accum, st.denom, st.max_radii, st.skip_flag
     const dim3 grid((P + 255) / 256), block(256);
     if (ent) {
         if (sink) hipLaunchKernelGGL((k_preprocess_backward<true, 0, true>), grid, block, 0, s, PPB_ARGS, *sink, rot, mot, *ent);
@@ -1462,6 +1462,9 @@ hipError_t egs_launch_preprocess_backward(int P, int D, int M, const float* mean
         else hipLaunchKernelGGL((k_preprocess_backward<false, 2>), grid, block, 0, s, PPB_ARGS, none, rot, mot, no_ent);
     }
 #undef PPB_ARGS
+#undef PP_ARGS
+#undef PP_SHAPE_CAM
+#undef PP_SCENE
     return hipGetLastError();
 }
 
@@ -1472,11 +1475,12 @@ static bool sh16_fast(int M, const void* a, const void* b, const void* c, const 
     return M == 16 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
 }
 
-hipError_t egs_launch_sh_forward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                 EgsGeomPtrs g, EgsMotion mot, hipStream_t s) {
+hipError_t egs_launch_sh_forward(const EgsScene& sc, EgsCamera cam, EgsGeomPtrs g, EgsMotion mot, hipStream_t s) {
+    const int P = sc.P, D = sc.D, M = sc.M;
+    const float* sh_a = sc.shs; const float* sh_rest = sc.shs_rest;
     if (P == 0) return hipSuccess;
     const dim3 grid((P + 63) / 64), block(64);
-#define SHF_ARGS means3D, cam.campos, sh_a, sh_rest, g.visible, g.rec, g.clamped, mot
+#define SHF_ARGS sc.means3D, cam.campos, sh_a, sh_rest, g.visible, g.rec, g.clamped, mot
     if (sh16_fast(M, sh_a, sh_rest, nullptr, nullptr)) {
         const size_t lds16 = sh_rest ? (SH16_REST_WORDS + 192) * sizeof(float) : 64 * 13 * sizeof(float4);
         if (sh_rest) {
@@ -1495,20 +1499,21 @@ hipError_t egs_launch_sh_forward(int P, int D, int M, const float* means3D, cons
     return hipGetLastError();
 }
 
-hipError_t egs_launch_sh_backward(int P, int D, int M, const float* means3D, const float* sh_a, const float* sh_rest, EgsCamera cam,
-                                  const int32_t* radii, EgsGeomPtrs g, const float* dcolors, float* dsh_a, float* dsh_rest,
-                                  float* dmeans3D, const EgsSink* sink, EgsMotion mot, hipStream_t s) {
+hipError_t egs_launch_sh_backward(const EgsScene& sc, EgsCamera cam, const int32_t* radii, EgsGeomPtrs g, const EgsGrads& d, const EgsSink* sink,
+                                  EgsMotion mot, hipStream_t s) {
+    const int P = sc.P, D = sc.D, M = sc.M;
+    const float* sh_a = sc.shs; const float* sh_rest = sc.shs_rest;
     if (P == 0) return hipSuccess;
     const dim3 grid((P + 63) / 64), block(64);
     EgsSink none = {};
-#define SHB_ARGS means3D, cam.campos, sh_a, sh_rest, radii, g.clamped, dcolors, dsh_a, dsh_rest, dmeans3D
+#define SHB_ARGS sc.means3D, cam.campos, sh_a, sh_rest, radii, g.clamped, d.colors, d.sh, d.sh_rest, d.means3D
     const size_t lds_split = (SH16_REST_WORDS + 192) * sizeof(float), lds_cat = 64 * 13 * sizeof(float4);
     if (sink) {                                                       // (the caller checked egs_sh_backward_can_sink)
         if (mot.A) hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, true, true>), grid, block, lds_split, s, P, D, SHB_ARGS, *sink, mot);
         else hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, true, false>), grid, block, lds_split, s, P, D, SHB_ARGS, *sink, mot);
         return hipGetLastError();
     }
-    if (sh16_fast(M, sh_a, sh_rest, dsh_a, dsh_rest)) {
+    if (sh16_fast(M, sh_a, sh_rest, d.sh, d.sh_rest)) {
         if (sh_rest) {
             if (mot.A) hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, false, true>), grid, block, lds_split, s, P, D, SHB_ARGS, none, mot);
             else hipLaunchKernelGGL((k_sh16_backward<SH16_SPLIT, false, false>), grid, block, lds_split, s, P, D, SHB_ARGS, none, mot);

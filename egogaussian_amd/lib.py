@@ -46,7 +46,11 @@ class ObjectMotion(C.Structure):                 # egs_object_motion; goes where
     _fields_ = [("rot", ObjectRotation), ("A12", C.c_void_p), ("moved", C.c_void_p), ("grad", C.c_void_p), ("scratch", C.c_void_p)]
 
 
-ACT_OBJECT_MOTION = 8                            # EGS_ACT_OBJECT_MOTION
+# include/egs_raster.h EGS_ACT_*: activation flags of the raw-parameter mode (_C re-exports them)
+ACT_LOG_SCALES, ACT_RAW_QUATS, ACT_LOGIT_OPACITY, ACT_OBJECT_MOTION, ACT_SCALAR_COLOR = 1, 2, 4, 8, 16
+ACT_RAW_PARAMETERS = ACT_LOG_SCALES | ACT_RAW_QUATS | ACT_LOGIT_OPACITY
+# include/egs_raster.h EGS_GRAD_*: which inputs' gradients the caller of a backward reads (0 = all)
+GRAD_MEANS3D, GRAD_MEANS2D, GRAD_SH, GRAD_COLORS, GRAD_OPACITY, GRAD_SCALES, GRAD_ROTATIONS, GRAD_COV3D = 1, 2, 4, 8, 16, 32, 64, 128
 
 
 def rot_pointer(st):
@@ -97,8 +101,31 @@ class PoseSequence(C.Structure):                 # egs_pose_sequence
 
 FRAME_DYNAMIC, FRAME_MOTION, FRAME_GATED, FRAME_OBJECT_LOSS, FRAME_LABEL_PHASE = 1, 2, 4, 8, 16      # EGS_FRAME_*
 FRAME_POSE_ROWS = 32                             # EGS_FRAME_POSE_ROWS
-ACT_SCALAR_COLOR = 16                            # EGS_ACT_SCALAR_COLOR
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
+
+# ---- the long rasterizer entry points: their parameter lists are runs of the same few segments (include/egs_raster.h) ----------------
+_ROT = C.POINTER(ObjectRotation)
+# scene prefix of the forwards: P, sh_degree, sh_coeffs, means3D, shs, shs_rest, colors_precomp, opacities, scales, scale_modifier, rotations,
+# cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos
+_FWD_SCENE = [i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp]
+_FWD_VIEW = [i32, i32, f32, f32, i32]                            # width, height, tan_fovx, tan_fovy, prefiltered
+# background + view, then radii, geom_buffer, capacity, binning_buffer, image_buffer, out_color, out_depth, out_alpha, pinned_host_counts
+_FWD_RENDER = [vp] + _FWD_VIEW + [vp, vp, i64, vp, vp, vp, vp, vp, vp]
+_FWD_TAIL = [_ROT, vp, i32]                                      # rot, stream, flags
+# scene prefix of the backwards: P, sh_degree, sh_coeffs, R, background, means3D, shs, shs_rest, colors_precomp, scales, scale_modifier, rotations,
+# cov3D_precomp, activation_flags, viewmatrix, projmatrix, campos, width, height, tan_fovx, tan_fovy, radii
+_BWD_SCENE = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, vp]
+_STATE = [vp, vp, vp]                                            # geom_buffer, binning_buffer, image_buffer
+_UPSTREAM = [vp, vp, vp]                                         # dL_dout_color, dL_dout_depth, dL_dout_alpha
+_GRADS = [vp] * 9                                                # dL_d{means2D, colors, opacity, means3D, cov3D, sh, sh_rest, scales, rotations}
+_STATS = [vp, vp, vp, vp]                                        # stat_grad_accum, stat_denom, stat_max_radii, skip_flag
+_BWD_TAIL = [C.POINTER(AdamSink), i32, _ROT, i32, vp, vp, i32]   # sink, prologue_done, rot, grad_mask, scratch, stream, flags
+
+
+def _backward(middle, tail=_BWD_TAIL):
+    """A backward differs from the others in its middle segment only (egs_backward, the oldest, also lacks sink, prologue_done and rot)."""
+    return (C.c_int, _BWD_SCENE + _STATE + middle + _GRADS + _STATS + tail)
+
 
 # name -> (restype, argtypes); every symbol include/egs_raster.h declares
 SIGNATURES = {
@@ -114,20 +141,15 @@ SIGNATURES = {
     "egs_get_geom_layout": (C.c_int, [i32, C.POINTER(GeomLayout)]),
     "egs_get_binning_layout": (C.c_int, [i32, i64, i32, i32, C.POINTER(BinningLayout)]),
     "egs_get_image_layout": (C.c_int, [i32, i32, C.POINTER(ImageLayout)]),
-    "egs_forward_geometry": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                                       i32, vp, vp, C.POINTER(i64), vp, C.POINTER(ObjectRotation), vp, i32]),
-    "egs_forward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, i64,
-                               vp, vp, vp, vp, vp, vp, C.POINTER(i64), vp, vp, C.POINTER(ObjectRotation), vp, i32]),
-    "egs_forward_enqueue": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp,
-                                       i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectRotation), vp, i32]),
+    "egs_forward_geometry": (C.c_int, _FWD_SCENE + _FWD_VIEW + [vp, vp, C.POINTER(i64), vp] + _FWD_TAIL),     # radii, geom_buffer, num_rendered, active_count
+    "egs_forward": (C.c_int, _FWD_SCENE + _FWD_RENDER + [C.POINTER(i64), vp, vp] + _FWD_TAIL),                 # num_rendered, active_count, placement
+    "egs_forward_enqueue": (C.c_int, _FWD_SCENE + _FWD_RENDER + [vp, vp, vp, vp] + _FWD_TAIL),                 # running_max, active_count, overflow_flag, placement
     "egs_placement_bytes": (C.c_size_t, [i32, i32]),
     "egs_placement_init": (C.c_int, [vp, i32, i32, vp]),
     "egs_sum_counts": (C.c_int64, [i32, vp]),
     "egs_forward_render": (C.c_int, [i32, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32]),
-    "egs_backward": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32]),
-    "egs_backward_adam": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_backward": _backward(_UPSTREAM, _BWD_TAIL[3:]),
+    "egs_backward_adam": _backward(_UPSTREAM),
     "egs_mark_visible": (C.c_int, [i32, vp, vp, vp, vp, vp]),
     "egs_cov3d_forward": (C.c_int, [i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "egs_cov3d_dm_scratch_floats": (C.c_size_t, [i32]),
@@ -153,16 +175,12 @@ SIGNATURES = {
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_forward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
-    "egs_backward_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                                        vp, vp, vp, vp, C.POINTER(LossGrad), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                        C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_backward_lossgrad": _backward([C.POINTER(LossGrad)]),
     "egs_object_loss_forward": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss), vp]),
     "egs_object_loss_forward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss), C.POINTER(BackwardPrologue), vp]),
     "egs_object_loss_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectLoss),
                                               C.POINTER(BackwardPrologue), vp]),
-    "egs_backward_object_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                                               vp, vp, vp, vp, C.POINTER(LossGrad), C.POINTER(ObjectLoss), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                               C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_backward_object_lossgrad": _backward([C.POINTER(LossGrad), C.POINTER(ObjectLoss)]),
     "egs_label_bce_partial_count": (C.c_size_t, [i32, i32]),
     "egs_label_bce_forward": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp]),
     "egs_label_bce_backward": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -171,9 +189,7 @@ SIGNATURES = {
     "egs_opacity_entropy_scratch_bytes": (C.c_size_t, [i32]),
     "egs_opacity_entropy_forward": (C.c_int, [i32, vp, i32, vp, vp, vp, C.POINTER(OpacityEntropy), vp]),
     "egs_opacity_entropy_backward": (C.c_int, [i32, vp, i32, vp, vp, C.POINTER(OpacityEntropy), vp, vp]),
-    "egs_backward_entropy_lossgrad": (C.c_int, [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32,
-                                                vp, vp, vp, vp, C.POINTER(LossGrad), C.POINTER(OpacityEntropy), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                vp, vp, vp, vp, vp, vp, C.POINTER(AdamSink), i32, C.POINTER(ObjectRotation), i32, vp, vp, i32]),
+    "egs_backward_entropy_lossgrad": _backward([C.POINTER(LossGrad), C.POINTER(OpacityEntropy)] + _UPSTREAM),
     "egs_adam_step": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "egs_adam_workgroups": (C.c_int64, [i64]),
     "egs_adam_step_capturable": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp]),

@@ -115,12 +115,12 @@ def _frame(N, H, W, seed, smul=2.0, hot=False):
     return sc, make_camera(3, H, W, device=DEV), torch.rand(3, H, W, generator=g).to(DEV), torch.tensor([0.1, 0.2, 0.3], device=DEV)
 
 
-def _backward_once(sc, cam, gt, bg, entropy, stats=False, lossgrad=True):
+def _backward_once(sc, cam, gt, bg, entropy, stats=False, lossgrad=True, **model):
     """One render + image loss + backward of a fresh model -> (gradients by leaf, screen-space gradient, radii, the term's value tensor, statistics)."""
     from egogaussian_amd.scene_synth import SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import l1_ssim_loss
-    pc = SynthGaussians(sc, device=DEV)
+    pc = SynthGaussians(sc, device=DEV, **model)
     kw = {} if entropy is None else {"opacity_entropy": entropy}
     out = render(cam, pc, Pipe, bg, fused_densify_stats=stats, **kw)
     l1_ssim_loss(out["render"], gt, 0.2, raster_prologue=True, raster_lossgrad=lossgrad).backward()
@@ -243,6 +243,34 @@ def test_render_option_adds_the_standalone_term_to_the_opacity_gradient(lossgrad
         from egogaussian_amd.renderer import render
         out = render(cam, SynthGaussians(sc, device=DEV, requires_grad=False), Pipe, bg, opacity_entropy=W_ENT)
     assert _equal_bits(out["opacity_entropy"], term.value)
+
+
+def test_render_option_on_a_model_that_hands_over_a_covariance():
+    """The same through the covariance route (no raw-parameter hooks: torch builds cov3D_precomp and activates the opacity, the library is
+    handed both): the term's share joins dL/d(activated opacity) and autograd carries it through the sigmoid.  `_opacity.grad` against the plain
+    render's of the same route plus the stand-alone gradient w.r.t. the activated opacity times s (1 - s), 2e-6 max-norm relative (the bar
+    above); the value bit-identical to the stand-alone reduction over the same activated opacities; the other leaves as above."""
+    from egogaussian_amd import _C
+    N, H, W = 2000, 96, 128
+    sc, cam, gt, bg = _frame(N, H, W, 3)
+    plain, _, radii, none, _, _ = _backward_once(sc, cam, gt, bg, None, fused=False)
+    ent, _, radii_e, value, _, pc = _backward_once(sc, cam, gt, bg, W_ENT, fused=False)
+    assert none is None and torch.equal(radii, radii_e)
+    assert pc.get_raw_parameters() is None, "the model must take the covariance route"
+    act = pc.get_opacity.detach().reshape(-1).contiguous()
+    term = _C.EntropyTerm(W_ENT, torch.device(DEV))
+    _C.opacity_entropy_forward(act, radii, term, logit=False)
+    g_ent = _C.opacity_entropy_backward(act, radii, term, logit=False) * (act * (1.0 - act))
+    torch.cuda.synchronize()
+    want = plain["_opacity"].reshape(-1).double() + g_ent.double()
+    err = float((ent["_opacity"].reshape(-1).double() - want).abs().max() / want.abs().max())
+    print(f"\n  render(opacity_entropy={W_ENT}), covariance given: _opacity.grad vs plain + stand-alone {err:.1e}; value {float(value):.6f}")
+    assert err < 2e-6 and _equal_bits(value, term.value)
+    assert float(g_ent.abs().max() / plain["_opacity"].abs().max()) > 1e-3, "the term must be visible in the gradient it joins"
+    assert float(ent["_opacity"].reshape(-1)[radii <= 0].abs().max()) == 0.0
+    for a in LEAVES:
+        if a != "_opacity":
+            assert float((plain[a] - ent[a]).abs().max()) <= 1e-5 * float(plain[a].abs().max()), a
 
 
 def _geom_of(sc, cam, bg):

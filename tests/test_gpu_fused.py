@@ -320,33 +320,52 @@ def test_graphed_train_step_matches_eager():
             assert float(diff.max()) < 0.02, "graph-replayed parameters drifted from the eager ones"
 
 
-@pytest.mark.parametrize("gated", [False, True], ids=["plain", "hand-mask gate"])
-def test_loss_gradient_inside_the_blend_matches_the_loss_backward_launch(gated):
+@pytest.mark.parametrize("gated,model", [(False, {}), (True, {}), (False, dict(sh_degree=3)), (False, dict(fused=False))],
+                         ids=["plain", "hand-mask gate", "split-16 harmonics", "covariance given"])
+def test_loss_gradient_inside_the_blend_matches_the_loss_backward_launch(gated, model):
     """ABI 5 (egs_backward_lossgrad): with raster_lossgrad=True the image loss has NO backward launch -- the rasterizer's backward blend
     computes dL/dimage for its tile from the maps the loss forward left (bit-identical per pixel: checked with the -DEGS_LG_CHECK build,
     profiles/), the loss forward carries the blend's preparation, and the deferred loss value is assembled by one wave of the blend.  Every
     parameter gradient, the loss value and the running sum must be what the separate launch gives (gradients up to the order of the
-    accumulator atomics)."""
+    accumulator atomics).  model: how the scene reaches the rasterizer -- raw parameters and one coefficient; the two stored harmonics arrays
+    (16 coefficients, the split kernels); a covariance computed outside (no raw-parameter hooks)."""
     import math
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import l1_ssim_loss
     N, H, W = 20000, 135, 250                                           # (a ragged image: partial tiles on both edges)
-    teacher = make_scene(N, H, W, 0); teacher["log_scale"] += math.log(2.0)
+    teacher = make_scene(N, H, W, 0, sh_degree=model.get("sh_degree", 0)); teacher["log_scale"] += math.log(2.0)
     cam = make_camera(7, H, W, device=DEV)
     bg = torch.tensor([0.1, 0.2, 0.3], device=DEV)
     with torch.no_grad():
-        gt = render(cam, SynthGaussians(teacher, device=DEV, requires_grad=False), Pipe, bg)["render"].clone()
+        gt = render(cam, SynthGaussians(teacher, device=DEV, requires_grad=False, **model), Pipe, bg)["render"].clone()
     gate = (torch.rand((H, W), generator=torch.Generator().manual_seed(3)) < 0.8).float().to(DEV) if gated else None
     res = []
-    for mode in (False, True, True):
-        pc = SynthGaussians(perturb_student(teacher), device=DEV)
+    # the plain case once more with the backward made to work in a caller's scratch buffer instead of the one the loss forward prepared (the
+    # C wrapper called with prologue_scratch=None, scratch=own: it then runs the blend's preparation itself and leaves the accumulator in `own`)
+    from egogaussian_amd import _C, lib
+    own = torch.zeros((lib.load().egs_backward_scratch_bytes(N),), dtype=torch.uint8, device=DEV)
+    wrapped = _C.rasterize_gaussians_backward
+
+    def in_own_scratch(*a, **k):
+        a = list(a)
+        assert a[29] is not None and k.get("loss_grad") is not None, "the call is expected to be the lossgrad route with a prepared scratch"
+        a[29] = None
+        return wrapped(*a, scratch=own, **k)
+    for mode in (False, True, True) + (("own scratch",) if not gated and not model else ()):
+        pc = SynthGaussians(perturb_student(teacher), device=DEV, **model)
         run = torch.full((1,), 0.25, device=DEV)
         out = render(cam, pc, Pipe, bg)
-        loss = l1_ssim_loss(out["render"], gt, 0.2, grad_gate=gate, running_sum=run, defer_value=True, raster_prologue=True, raster_lossgrad=mode)
-        loss.backward()
+        loss = l1_ssim_loss(out["render"], gt, 0.2, grad_gate=gate, running_sum=run, defer_value=True, raster_prologue=True, raster_lossgrad=bool(mode))
+        if mode == "own scratch":
+            _C.rasterize_gaussians_backward = in_own_scratch
+        try:
+            loss.backward()
+        finally:
+            _C.rasterize_gaussians_backward = wrapped
         torch.cuda.synchronize()
         res.append(([p.grad.clone() for p in pc.parameters() if p.grad is not None], float(loss.detach()), float(run)))
+    assert gated or model or bool(own.any()), "the caller's scratch buffer was not the one worked in"
     ref = res[0]
     assert len(ref[0]) >= 5 and math.isfinite(ref[1]) and ref[1] > 0
     for got in res[1:]:

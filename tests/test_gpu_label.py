@@ -16,14 +16,14 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
 
-def _colors_only(g, out, grads, dev):
+def _colors_only(g, out, grads, dev, scratch=None):
     from egogaussian_amd import _C
     R, color, depth, alpha, radii, geom, binning, img = out
     e = torch.empty(0, device=dev)
     res = _C.rasterize_gaussians_backward(g["bg"], g["means3D"], radii, g["colors_precomp"], g.get("scales", e), g.get("rotations", e),
                                           g["scale_modifier"], g.get("cov3D_precomp", e), g["viewmatrix"], g["projmatrix"], g["tanfovx"],
                                           g["tanfovy"], grads[0].to(dev), e, e, e, g["sh_degree"], g["campos"], geom, R, binning, img, alpha, False,
-                                          grad_mask=_C.GRAD_COLORS)
+                                          grad_mask=_C.GRAD_COLORS, scratch=scratch)
     assert all(r is None for i, r in enumerate(res) if i != 1), "the colours-only backward produces dL_dcolors and nothing else"
     return res[1]
 
@@ -41,7 +41,12 @@ def test_colors_only_backward_vs_oracle_and_full_backward(N, H, W, seed, mode, s
         g, out = hip_forward(d, dev)
         dc = _colors_only(g, out, grads, dev)
         full = hip_backward(g, out, grads, dev)[1]
+        # a caller's scratch buffer: this route works in it too, and leaves the blend's accumulator there
+        from egogaussian_amd import lib
+        own = torch.zeros((lib.load().egs_backward_scratch_bytes(N),), dtype=torch.uint8, device=dev)
+        dc_own = _colors_only(g, out, grads, dev, scratch=own)
     torch.cuda.synchronize()
+    assert rel_err(dc_own.cpu().numpy(), full.cpu().numpy()) < 2e-6 and bool(own.any()), "the caller's scratch buffer was not the one worked in"
     e_or = rel_err(dc.cpu().numpy(), gb["dL_dcolor"])
     e_full = rel_err(dc.cpu().numpy(), full.cpu().numpy())
     print(f"\n[{N}@{W}x{H} {mode}] colours-only dL/dcolors: vs oracle {e_or:.1e}, vs the full backward {e_full:.1e}")

@@ -404,15 +404,18 @@ def test_trainable_pose_gradients_reach_the_six_d_parameters():
     Tf = _pose(0.25, (0.3, -0.2, 0.25)).to(DEV)                          # the accumulated pose; the trainable one sits on top of it
     t0, r6 = [0.15, -0.08, 0.1], (_rot((0.2, 0.4, 1.0), 0.18)[:, :2] + 0.03).tolist()
     moved = motion.exact_mask(is_obj, 1)
-    # inside
-    pa = adapter.attach(_model(0), optimizer=False)
-    toma = Move(t0, r6, DEV)
-    pa.trainable_object_move = toma
-    calls = pa.build_covariance_from_scaling_rotation_w_rot.calls
-    out = render(cam, pa, Pipe, bg, rot_cov=True, which_object=1, during_training=True, object_motion=motion.ObjectMotion(Tf, toma))
-    l1_ssim_loss(out["render"], gt, 0.2).backward()
-    torch.cuda.synchronize()
-    assert pa.build_covariance_from_scaling_rotation_w_rot.calls == calls and int((out["radii"] > 0).sum()) > 1000
+    # inside: the loss's gradient handed over as a tensor, and formed by the blend itself (egs_backward_lossgrad writes the pose gradient too)
+    def inside(**loss_kw):
+        pa = adapter.attach(_model(0), optimizer=False)
+        tom = Move(t0, r6, DEV)
+        pa.trainable_object_move = tom
+        calls = pa.build_covariance_from_scaling_rotation_w_rot.calls
+        out = render(cam, pa, Pipe, bg, rot_cov=True, which_object=1, during_training=True, object_motion=motion.ObjectMotion(Tf, tom))
+        l1_ssim_loss(out["render"], gt, 0.2, **loss_kw).backward()
+        torch.cuda.synchronize()
+        assert pa.build_covariance_from_scaling_rotation_w_rot.calls == calls and int((out["radii"] > 0).sum()) > 1000
+        return tom
+    toma, toma_blend = inside(), inside(raster_prologue=True, raster_lossgrad=True)
     # all torch, twice
     res = []
     for rep in range(2):
@@ -451,11 +454,13 @@ def test_trainable_pose_gradients_reach_the_six_d_parameters():
         return torch.cat([torch.cat([Rt @ Tf64[:3, :3], (Rt @ Tf64[:3, 3] + t)[:, None]], 1).reshape(-1), (Rt @ Tf64[:3, :3]).reshape(-1)])
     Jt, Jr = torch.autograd.functional.jacobian(composed, (toma.obj_translation.detach().double().cpu(), toma.obj_rotation_6d.detach().double().cpu()))
     for name, J in (("obj_translation", Jt), ("obj_rotation_6d", Jr)):
-        a, x1, x2 = (_f64(getattr(m, name).grad) for m in (toma, b1, b2))
+        a, ab, x1, x2 = (_f64(getattr(m, name).grad) for m in (toma, toma_blend, b1, b2))
         derived = (J.abs() * e21.view(21, *([1] * (J.dim() - 1)))).sum(0).numpy()
-        print(f"{name}: inside vs torch max {np.abs(a - x1).max():.3e}; spread of two torch runs max {np.abs(x1 - x2).max():.3e}; |grad| max {np.abs(x1).max():.3e}; derived max {derived.max():.3e}")
+        print(f"{name}: inside vs torch max {np.abs(a - x1).max():.3e}, with the loss gradient formed in the blend {np.abs(ab - x1).max():.3e}; "
+              f"spread of two torch runs max {np.abs(x1 - x2).max():.3e}; |grad| max {np.abs(x1).max():.3e}; derived max {derived.max():.3e}")
         assert np.abs(x1).max() > 0
         assert np.all(np.abs(a - x1) <= 4 * np.abs(x1 - x2) + derived), name
+        assert np.all(np.abs(ab - x1) <= 4 * np.abs(x1 - x2) + derived), name + " (loss gradient formed in the blend)"
 
 
 # ---- 7. fused Adam under motion ----------------------------------------------------------------------------------------------------

@@ -194,19 +194,29 @@ def test_gradients_formed_in_the_blend_match_the_backward_launch(N, H, W, gated)
     """raster_lossgrad=True: no loss-backward launch, the blend (k_render_backward<2, true>) forms dL/dimage and dL/dalpha itself.  Loss, running
     sum and terms are equal; every parameter gradient is within 2e-5 of its array's maximum (the order of the accumulator atomics) -- the bar
     of test_loss_gradient_inside_the_blend_matches_the_loss_backward_launch."""
+    _blend_against_launch(N, H, W, gated)
+
+
+def test_gradients_formed_in_the_blend_with_split_harmonics():
+    """The same on a model of 16 coefficients handed over as its two stored arrays: the spherical-harmonics launches follow the preprocess
+    backward of the object stages' route (5 leaves + features_rest)."""
+    _blend_against_launch(3000, 48, 80, False, sh_degree=3)
+
+
+def _blend_against_launch(N, H, W, gated, **model):
     from egogaussian_amd.scene_synth import make_scene, make_camera, perturb_student, SynthGaussians, Pipe
     from egogaussian_amd.renderer import render
     from egogaussian_amd.fused import object_stage_loss
-    teacher = make_scene(N, H, W, 0); teacher["log_scale"] += math.log(2.0)
+    teacher = make_scene(N, H, W, 0, sh_degree=model.get("sh_degree", 0)); teacher["log_scale"] += math.log(2.0)
     cam = make_camera(7, H, W, device=DEV)
     bg = torch.zeros(3, device=DEV)
     with torch.no_grad():
-        gt = render(cam, SynthGaussians(teacher, device=DEV, requires_grad=False), Pipe, bg)["render"].clone()
+        gt = render(cam, SynthGaussians(teacher, device=DEV, requires_grad=False, **model), Pipe, bg)["render"].clone()
     mask = _box_mask(H, W)
     gate = (torch.rand((H, W), generator=torch.Generator().manual_seed(3)) < 0.8).float().to(DEV) if gated else None
     res = []
     for mode in (False, True, True):
-        pc = SynthGaussians(perturb_student(teacher), device=DEV)
+        pc = SynthGaussians(perturb_student(teacher), device=DEV, **model)
         run, terms = torch.full((1,), 0.25, device=DEV), torch.zeros(3, device=DEV)
         out = render(cam, pc, Pipe, bg)
         loss = object_stage_loss(out["render"], out["alpha"], gt, mask, LAM, grad_gate=gate, running_sum=run, terms=terms, defer_value=True,
@@ -215,7 +225,7 @@ def test_gradients_formed_in_the_blend_match_the_backward_launch(N, H, W, gated)
         torch.cuda.synchronize()
         res.append(([p.grad.clone() for p in pc.parameters() if p.grad is not None], float(loss.detach()), float(run), terms.cpu()))
     ref = res[0]
-    assert len(ref[0]) >= 5 and math.isfinite(ref[1]) and ref[1] > 0 and float(ref[3][1]) > 0 and float(ref[3][2]) > 0
+    assert len(ref[0]) >= (6 if model.get("sh_degree") else 5) and math.isfinite(ref[1]) and ref[1] > 0 and float(ref[3][1]) > 0 and float(ref[3][2]) > 0
     for got in res[1:]:
         assert got[1] == ref[1] and got[2] == ref[2] and torch.equal(got[3], ref[3]) and abs(ref[2] - 0.25 - ref[1]) < 1e-6
         assert len(got[0]) == len(ref[0])

@@ -138,6 +138,23 @@ def forward_fuses_count(P, W, H, debug=0):
     return bool(_lib.load().egs_forward_fuses_count(int(P), int(W), int(H), call_flags(debug)))
 
 
+SORT_IN_BLEND, SORT_SECOND_INSTANTIATION, SORT_BALLOT_RANK = _lib.SORT_IN_BLEND, _lib.SORT_SECOND_INSTANTIATION, _lib.SORT_BALLOT_RANK
+
+
+def sort_plan(P, W, H, capacity=None, debug=0, retried=False):
+    """Which launches sort the tile lists of a forward of this size with these flags: SORT_* bits (include/egs_raster.h
+    egs_forward_sort_plan; host arithmetic, no device work).  capacity: what the binning buffer is laid out for -- stats["capacity"] right
+    after a forward; None: the current device's capacity hint, which is what the NEXT forward is enqueued against.
+    retried: the answer for the second attempt of a forward whose capacity was too small (egs_forward_render, which honours CALL_SYNC); a
+    forward that fits runs the speculative chain, which never synchronises mid-way and does not see that bit."""
+    if capacity is None:
+        capacity = _capacity_hint.get(torch.cuda.current_device(), 0)
+    flags = call_flags(debug)
+    if not retried:
+        flags &= ~CALL_SYNC
+    return int(_lib.load().egs_forward_sort_plan(int(P), int(capacity), int(W), int(H), flags))
+
+
 def last_instance_count(device=None, P=None):
     """R (rectangle instances) of the most recent EAGER forward on `device`, summed from the page-locked per-workgroup counts
     that call copied out.  Captured forwards skip the copy; they are checked through set_running_max / stats["total_view"]."""

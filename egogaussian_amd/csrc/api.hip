@@ -189,9 +189,13 @@ int egs_debug_set_lossgrad(const float* img, const float* gt, const float* m0, c
 // Per-call flags (include/egs_raster.h EGS_CALL_*, ABI 6): what used to be process-wide switches (egs_debug_set_tile_culling / _fused_count /
 // _sort_in_blend / egs_debug_force_ballot_rank through ABI 5) travels in the last argument of the call it applies to; the library keeps none of it.
 static inline bool fused_count_on(int flags) { return !(flags & EGS_CALL_SEPARATE_COUNT); }
-static inline bool sort_in_blend_on(int flags) { return !(flags & (EGS_CALL_SEPARATE_SORT | EGS_CALL_SYNC)); }     // (SYNC checks after every launch: keep them apart)
 static inline int cull_on(int flags) { return (flags & EGS_CALL_KEEP_ALL_INSTANCES) ? 0 : 1; }
 int egs_forward_fuses_count(int P, int width, int height, int flags) { return (fused_count_on(flags) && egs_can_fuse_count(P, width, height, cull_on(flags))) ? 1 : 0; }
+// (the rule itself: binning.hip egs_sort_plan, which egs_launch_binning acts on)
+int egs_forward_sort_plan(int P, int64_t capacity, int width, int height, int flags) {
+    if (P <= 0 || capacity <= 0 || width <= 0 || height <= 0) return 0;
+    return egs_sort_plan(P, capacity, (int)egs_tiles(width, height), flags);
+}
 
 const char* egs_error_string(int code) {
     switch (code) {
@@ -412,7 +416,7 @@ static int forward_impl(const ForwardCall& c) {
         // blend needs; with the sums of a fused count pass to clear, a failure before the blend is enqueued leaves them dirty (dirty_guard)
         EgsSortArgs sort_args = {};
         EGS_TRY(egs_launch_binning(P, capacity, width, height, g, b, im, c.running_max, c.overflow_flag, 1, fuse ? 1 : 0,
-                                   !(debug & EGS_CALL_SEPARATE_SORT) ? &sort_args : nullptr, s, debug & ~EGS_CALL_SYNC));      // (speculative chain: never synchronised mid-way)
+                                   &sort_args, s, debug & ~EGS_CALL_SYNC));      // (speculative chain: never synchronised mid-way, so SYNC does not move its sort plan either)
         egs_prof_start(EGS_K_RENDER_FWD, s);
         EGS_TRY(egs_launch_render_forward(width, height, c.background, g, b.point_list, im, c.out_color, c.out_depth, c.out_alpha, placement ? 1 : 0, &sort_args, s));
         dirty_guard.p = nullptr;
@@ -487,7 +491,7 @@ int egs_forward_render(int P, int64_t R, const float* background, int width, int
     EgsBinPtrs b = bin_ptrs(binning_buffer, P, R, width, height);
     EgsImgPtrs im = img_ptrs(image_buffer, width, height);
     EgsSortArgs sort_args = {};
-    EGS_TRY(egs_launch_binning(P, R, width, height, g, b, im, nullptr, nullptr, 0, 0, sort_in_blend_on(debug) ? &sort_args : nullptr, s, debug));
+    EGS_TRY(egs_launch_binning(P, R, width, height, g, b, im, nullptr, nullptr, 0, 0, &sort_args, s, debug));
     const uint32_t* point_list = b.point_list;
     egs_prof_start(EGS_K_RENDER_FWD, s);
     EGS_TRY(egs_launch_render_forward(width, height, background, g, point_list, im, out_color, out_depth, out_alpha, 0, &sort_args, s));

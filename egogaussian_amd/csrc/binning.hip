@@ -350,9 +350,26 @@ EgsBinGeometry egs_bin_geometry(int P, int W, int H, int cull) {
     return q;
 }
 
+// The launch plan of the per-tile sort, decided on the host from sizes and flags alone (include/egs_raster.h EGS_SORT_*).
+// A launch costs ~4.5 us of GPU time even when every workgroup returns at once.  When the buffer holds on average at most 2048
+// instances per tile (R is the capacity: >= 1.25 x the rectangle count, itself ~1.5 x what survives culling) no tile is expected
+// to need the second instantiation, so it is not launched (`solo`); a tile that does exceed TS_SMALL_CAP is still sorted, by the first
+// one's slab and global-memory paths.  A solo sort can run inside the forward blend's launch, unless the call keeps them apart
+// (EGS_CALL_SEPARATE_SORT; EGS_CALL_SYNC, which checks after every launch).  The ranker is what the call REQUESTS: the device's one-time
+// verdict on the LDS lane order (k_check_lds_atomic_order) can still replace the atomic ranker by the ballot one.
+int egs_sort_plan(int P, int64_t R64, int n_tiles, int call_flags) {
+    if (P <= 0 || R64 <= 0 || n_tiles <= 0) return 0;
+    const int solo = (uint64_t)R64 <= 2048ull * (uint64_t)n_tiles ? 1 : 0;
+    int plan = 0;
+    if (solo && !(call_flags & (EGS_CALL_SEPARATE_SORT | EGS_CALL_SYNC))) plan |= EGS_SORT_IN_BLEND;
+    if (!solo) plan |= EGS_SORT_SECOND_INSTANTIATION;
+    if (call_flags & EGS_CALL_BALLOT_RANK) plan |= EGS_SORT_BALLOT_RANK;
+    return plan;
+}
+
 // counted: the table and the chunk sums of this frame are in place already (preprocess.hip's k_preprocess_count walked the rectangles)
-// sort_in_blend (may be NULL): filled with what the forward blend needs to sort its tiles itself -- then no sort launch is made here
-// (table_scanned == NULL in it: not taken, e.g. a second sort instantiation would be needed)
+// sort_in_blend (may be NULL: the caller's blend cannot sort): filled with what the forward blend needs to sort its tiles itself when the
+// plan says so -- then no sort launch is made here (table_scanned == NULL in it: not taken, e.g. a second sort instantiation would be needed)
 hipError_t egs_launch_binning(int P, int64_t R64, int W, int H, EgsGeomPtrs g, EgsBinPtrs b, EgsImgPtrs im,
                               uint64_t* running_max, uint32_t* overflow_flag, int sums_zeroed, int counted, EgsSortArgs* sort_in_blend, hipStream_t s, int call_flags) {
     const int debug = call_flags & EGS_CALL_SYNC;
@@ -408,16 +425,13 @@ hipError_t egs_launch_binning(int P, int64_t R64, int W, int H, EgsGeomPtrs g, E
         fast = bad == 0 ? 1 : 0;
         lds_rank_ok.store(fast);
     }
-    if (call_flags & EGS_CALL_BALLOT_RANK) fast = 0;
+    const int plan = egs_sort_plan(P, R64, n_tiles, call_flags);
+    if (plan & EGS_SORT_BALLOT_RANK) fast = 0;
     const int ip = (index_bits + TS_DBITS - 1) / TS_DBITS;
-    // A launch costs ~4.5 us of GPU time even when every workgroup returns at once.  When the buffer holds on average at most 2048
-    // instances per tile (R is the capacity: >= 1.25 x the rectangle count, itself ~1.5 x what survives culling) no tile is expected
-    // to need the second instantiation, so it is not launched; a tile that does exceed 2048 is still sorted, by the first one's
-    // global-memory path.
-    const int solo = (uint64_t)R <= 2048ull * (uint64_t)n_tiles ? 1 : 0;
+    const int solo = (plan & EGS_SORT_SECOND_INSTANTIATION) ? 0 : 1;
     EgsSortArgs sa = { n_tiles, stride, b.table, b.total, running_max, overflow_flag, solo, R, ip, b.pairs, b.scratch, b.point_list, im.ranges,
                        b.zero_after, b.zero_after_n };
-    if (sort_in_blend && solo) {
+    if (sort_in_blend && (plan & EGS_SORT_IN_BLEND)) {
         // the forward blend sorts every tile itself (render_fwd.hip SORT instantiations): no sort launch.  What the launch carries besides the
         // sort -- the overflow word, the running maximum, clearing the chunk sums -- travels in `sort_out` to that launch.
         sa.rank_atomic = fast;

@@ -208,6 +208,9 @@ struct EgsSortArgs {
     uint32_t R /* capacity */; int index_passes; uint64_t* pairs; uint64_t* scratch; uint32_t* point_list; uint2* ranges;
     uint32_t* zero_after; uint32_t zero_after_n; int rank_atomic /* launcher -> launcher: the LDS lane-order property holds (wave_digit_rank) */;
 };
+// Which launches sort the tile lists of a frame (binning.hip): EGS_SORT_* bits of include/egs_raster.h, 0 when nothing is bucketed.  Host arithmetic only;
+// egs_launch_binning acts on this very answer and egs_forward_sort_plan (api.hip) exports it.
+int egs_sort_plan(int P, int64_t R, int n_tiles, int call_flags /* EGS_CALL_* */);
 // counted: b.table and b.chunk_sum were filled by egs_launch_preprocess_count (the count pass is not launched)
 // sort_in_blend (may be NULL): see binning.hip
 hipError_t egs_launch_binning(int P, int64_t R, int W, int H, EgsGeomPtrs g, EgsBinPtrs b, EgsImgPtrs im,

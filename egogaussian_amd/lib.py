@@ -12,6 +12,8 @@ ABI_VERSION = 6
 RETRY_LARGER = -100
 # per-call flags (include/egs_raster.h EGS_CALL_*, ABI 6): bits of the `debug` / `flags` word of the forwards
 CALL_SYNC, CALL_KEEP_ALL_INSTANCES, CALL_SEPARATE_COUNT, CALL_SEPARATE_SORT, CALL_BALLOT_RANK = 1, 2, 4, 8, 16
+# egs_forward_sort_plan's answer (EGS_SORT_*)
+SORT_IN_BLEND, SORT_SECOND_INSTANTIATION, SORT_BALLOT_RANK = 1, 2, 4
 
 vp, f32, i32, i64 = C.c_void_p, C.c_float, C.c_int, C.c_int64
 
@@ -205,6 +207,7 @@ SIGNATURES = {
     "egs_knn3_grid_scratch_bytes": (C.c_size_t, [i32]),
     "egs_knn3_grid": (C.c_int, [i32, vp, vp, vp, vp]),
     "egs_forward_fuses_count": (C.c_int, [i32, i32, i32, i32]),
+    "egs_forward_sort_plan": (C.c_int, [i32, i64, i32, i32, i32]),
     "egs_profile_begin": (C.c_int, [i32]),
     "egs_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "egs_profile_stage_name": (C.c_char_p, [i32]),

@@ -904,6 +904,26 @@ int egs_knn3_grid(int N, const float* points /*[N,3]*/, float* mean_dist2 /*[N] 
  * preprocess launch (1) or not (0: very large images, or EGS_CALL_SEPARATE_COUNT). */
 int egs_forward_fuses_count(int P, int width, int height, int flags);
 
+/* ---- which launches sort the tile lists of a forward (added within ABI 6: new entries only).
+ * The per-tile sort has two instantiations (four waves for lists of up to 1 792 instances, eight waves beyond) and two launch sites (launches
+ * of its own, or inside the forward blend's launch).  Which of them a frame gets is host arithmetic on the model size, the CAPACITY the
+ * binning buffer was laid out for (not the frame's instance count), the image size and the call's EGS_CALL_* flags; this entry returns the
+ * decision the library acts on -- the same function decides inside the forward -- as a set of EGS_SORT_* bits, 0 when nothing is bucketed
+ * (P == 0 or capacity == 0).  It launches no device work and needs no device.
+ *   EGS_SORT_IN_BLEND              the forward blend's workgroups sort their own tile; no sort launch.  Only when the second instantiation is not
+ *                                  needed (capacity <= 2048 x tiles) and the call has neither EGS_CALL_SEPARATE_SORT nor EGS_CALL_SYNC
+ *   EGS_SORT_SECOND_INSTANTIATION  capacity > 2048 x tiles: the eight-wave instantiation is launched behind the four-wave one and takes the
+ *                                  lists beyond 1 792; without it the four-wave instantiation sorts every list itself
+ *   EGS_SORT_BALLOT_RANK           the call asks for the ballot-based ranker (EGS_CALL_BALLOT_RANK)
+ * `flags` are read as the sort sees them: egs_forward_render passes the call's word on unchanged; egs_forward and egs_forward_enqueue never
+ * synchronise inside their chain and mask EGS_CALL_SYNC out first, so for those two that bit does not keep the sort out of the blend.
+ * NOT part of the answer: the one-time device check of the LDS lane order (the second item of process-wide state listed at the top).  A device
+ * that fails it ranks with ballots whatever the call requests; EGS_SORT_BALLOT_RANK clear means "not requested", not "atomic ranker ran". */
+#define EGS_SORT_IN_BLEND              0x1
+#define EGS_SORT_SECOND_INSTANTIATION  0x2
+#define EGS_SORT_BALLOT_RANK           0x4
+int egs_forward_sort_plan(int P, int64_t capacity, int width, int height, int flags);
+
 /* ---- optional per-stage timing with HIP events on the caller's stream (bench / profiling aid) ------
  * The only process-wide state in the library; off by default.  egs_profile_begin allocates an event pool and
  * turns recording on; every stage launched afterwards is bracketed by two events on its stream;

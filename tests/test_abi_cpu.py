@@ -59,6 +59,30 @@ def test_sizes_and_layouts():
     # ABI 6: a per-call flag, not a process-wide switch -- the answer for one call's flags says nothing about the next call's
     assert fuses(500000, 960, 540, lib.CALL_SEPARATE_COUNT) == 0 and fuses(500000, 960, 540) == 1
     assert fuses(500000, 960, 540, lib.CALL_KEEP_ALL_INSTANCES | lib.CALL_SYNC | lib.CALL_SEPARATE_SORT | lib.CALL_BALLOT_RANK) == 1
+    # which launches sort the tile lists (added within ABI 6): host arithmetic on the CAPACITY, the tile count and the call's flags
+    plan = lambda P, cap, W, H, flags=0: L.egs_forward_sort_plan(P, cap, W, H, flags)
+    IN_BLEND, SECOND, BALLOT = lib.SORT_IN_BLEND, lib.SORT_SECOND_INSTANTIATION, lib.SORT_BALLOT_RANK
+    hdr = open(os.path.join(ROOT, "include", "egs_raster.h")).read()
+    assert [int(re.search(rf"#define\s+EGS_SORT_{n}\s+0x([0-9a-f]+)", hdr).group(1), 16) for n in ("IN_BLEND", "SECOND_INSTANTIATION", "BALLOT_RANK")] == [IN_BLEND, SECOND, BALLOT]
+    assert plan(500000, 2040 * 2048, 960, 540) == IN_BLEND and plan(500000, 2040 * 2048 + 1, 960, 540) == SECOND      # 2040 tiles: `solo` up to 2048 per tile
+    assert plan(3000, 32768, 64, 64) == IN_BLEND and plan(3000, 32769, 64, 64) == SECOND                               # 16 tiles
+    assert plan(3000, 32768, 49, 64) == IN_BLEND and plan(3000, 32768, 48, 64) == SECOND                               # ragged image: 16 tiles / 12 tiles
+    assert plan(3000, 32768, 64, 64, lib.CALL_SEPARATE_SORT) == 0 and plan(3000, 32768, 64, 64, lib.CALL_SYNC) == 0   # kept out of the blend
+    assert plan(3000, 32768, 64, 64, lib.CALL_BALLOT_RANK) == IN_BLEND | BALLOT and plan(3000, 32769, 64, 64, lib.CALL_BALLOT_RANK) == SECOND | BALLOT
+    assert plan(3000, 32768, 64, 64, lib.CALL_KEEP_ALL_INSTANCES | lib.CALL_SEPARATE_COUNT) == IN_BLEND                # not the sort's flags
+    assert plan(3000, 32769, 64, 64, lib.CALL_SEPARATE_SORT | lib.CALL_SYNC) == SECOND
+    assert plan(0, 32768, 64, 64) == 0 and plan(0, 32769, 64, 64, lib.CALL_BALLOT_RANK) == 0 and plan(3000, 0, 64, 64) == 0
+    # the Python wrapper: the module's default flags are ORed in; a forward that fits its capacity never sees CALL_SYNC (its chain is not
+    # synchronised mid-way), the retry of one that did not fit does
+    from egogaussian_amd import _C
+    assert _C.sort_plan(3000, 64, 64, 32768) == IN_BLEND and _C.sort_plan(3000, 64, 64, 32769, debug=_C.CALL_BALLOT_RANK) == SECOND | BALLOT
+    assert _C.sort_plan(3000, 64, 64, 32768, debug=True) == IN_BLEND and _C.sort_plan(3000, 64, 64, 32768, debug=True, retried=True) == 0
+    old = _C.set_sort_in_blend(False)
+    try:
+        assert _C.sort_plan(3000, 64, 64, 32768) == 0
+    finally:
+        _C.set_sort_in_blend(old)
+    assert _C.sort_plan(3000, 64, 64, 32768) == IN_BLEND
     # ... and the library exports no setter of process-wide behaviour any more
     for gone in ("egs_debug_set_tile_culling", "egs_debug_set_fused_count", "egs_debug_set_sort_in_blend", "egs_debug_force_ballot_rank", "egs_debug_set_lossgrad"):
         assert not hasattr(L, gone), gone

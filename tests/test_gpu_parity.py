@@ -66,6 +66,44 @@ def oracle_forward(d, nthreads=8):
     return o, o.forward(**d)
 
 
+class pinned_capacity:
+    """Run a block with the capacity hint of the current device set to `value`; the previous hint comes back afterwards.  Which sort
+    instantiation and which launch site a frame gets is decided from the capacity, and the hint of a process otherwise only grows with
+    the tests that ran before: a test that claims a path pins the capacity and asks the library which plan its call got (sort_plan_of)."""
+
+    def __init__(self, value):
+        self.value = int(value)
+
+    def __enter__(self):
+        from egogaussian_amd import _C
+        self.key = torch.cuda.current_device()
+        self.had, self.old = self.key in _C._capacity_hint, _C._capacity_hint.get(self.key)
+        _C.set_capacity_hint(self.value)
+        return self
+
+    def __exit__(self, *exc):
+        from egogaussian_amd import _C
+        if self.had:
+            _C._capacity_hint[self.key] = self.old
+        else:
+            _C._capacity_hint.pop(self.key, None)
+
+
+def sort_plan_of(N, W, H, want_capacity, retries_before, debug=0):
+    """The sort plan of the forward that has just run (SORT_* bits), after checking that it ran against the pinned capacity without a retry."""
+    from egogaussian_amd import _C
+    assert _C.stats["retries"] == retries_before, "the pinned capacity was too small: the forward was retried"
+    assert _C.stats["capacity"] == want_capacity, (_C.stats["capacity"], want_capacity)
+    return _C.sort_plan(N, W, H, _C.stats["capacity"], debug=debug)
+
+
+def sort_regimes_of(st, capacity):
+    """{(instantiation, regime): number of tiles} of an oracle state under the plan of `capacity` (tests/sort_regimes.py, the CPU model)."""
+    import collections
+    from tests import sort_regimes as sr
+    return collections.Counter((i.inst, i.regime) for i in sr.regime_of_tiles(st, capacity, 0).values())
+
+
 def float64_oracle(d, grads, nthreads=8):
     """The same frame and upstream gradients through the oracle in float64 -> (state, gradients)."""
     from oracle.oracle import Oracle
@@ -333,10 +371,15 @@ def sort_inside_the_forward_blend_changes_nothing(d, cull):
     N, H, W = int(d["means3D"].shape[0]), d["image_height"], d["image_width"]
     res = {}
     with tile_culling(cull):
-        hip_forward(d, dev)
+        R = hip_forward(d, dev)[1][0]
+        n_tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        assert 0 < R <= 2048 * n_tiles, "this frame can never be sorted inside the blend: its instance count needs the second instantiation"
         for inside in (False, True, True):
-            with sort_in_blend(inside):
+            with sort_in_blend(inside), pinned_capacity(R):
+                retries = _C.stats["retries"]
                 g, out = hip_forward(d, dev)
+                plan = sort_plan_of(N, W, H, R, retries)
+            assert plan == (_C.SORT_IN_BLEND if inside else 0), f"plan {plan:#x} with sort_in_blend({inside}): the two launch sites are not the ones being compared"
             iv = _C.image_views(out[7], W, H); bv = _C.binning_views(out[6], N, out[0], W, H, _C.stats["capacity"])
             rng = iv["ranges"].cpu().numpy().view(np.uint32).astype(np.int64)
             n_list = int((rng[:, 1] - rng[:, 0]).sum())
@@ -529,7 +572,11 @@ def test_depth_ties_keep_index_order():
     cam = make_camera(0, 64, 64)
     d.update(viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, campos=cam.camera_center)
     o, st = oracle_forward(d)
-    g, out = hip_forward(d, dev)
+    assert set(sort_regimes_of(st, st["R"])) == {(4, "equal")}, "every tile is meant to take the index-digit passes of the four-wave instantiation"
+    with pinned_capacity(st["R"]):
+        retries = _C.stats["retries"]
+        g, out = hip_forward(d, dev)
+        assert sort_plan_of(3000, 64, 64, st["R"], retries) == _C.SORT_IN_BLEND
     bv = _C.binning_views(out[6], 3000, out[0], 64, 64, _C.stats["capacity"])
     assert out[0] == st["R"] and st["R"] > 3000
     assert np.array_equal(bv["point_list"].cpu().numpy().view(np.uint32), st["point_list"])
@@ -560,7 +607,12 @@ def test_clustered_depths_take_the_sorts_fallback_and_still_match(layout):
     cam = make_camera(0, H, W)
     d.update(viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, campos=cam.camera_center)
     o, st = oracle_forward(d)
-    g, out = hip_forward(d, dev)
+    regimes = sort_regimes_of(st, st["R"])
+    assert set(regimes) == {(4, "digits+ties")}, f"every tile is meant to take the digit-by-digit passes of the four-wave instantiation: {dict(regimes)}"
+    with pinned_capacity(st["R"]):
+        retries = _C.stats["retries"]
+        g, out = hip_forward(d, dev)
+        assert sort_plan_of(N, W, H, st["R"], retries) == _C.SORT_IN_BLEND
     bv = _C.binning_views(out[6], N, out[0], W, H, _C.stats["capacity"])
     assert out[0] == st["R"] and st["R"] > 2 * N
     assert np.array_equal(bv["point_list"].cpu().numpy().view(np.uint32), st["point_list"])
@@ -593,7 +645,14 @@ def test_tiles_beyond_the_register_capacity_are_sorted_in_depth_slabs(layout):
     o, st = oracle_forward(d)
     lens = (st["ranges"][:, 1] - st["ranges"][:, 0])
     assert lens.max() > 4096 and (layout == "uniform") == (lens.mean() > 2048), (int(lens.max()), float(lens.mean()))
-    g_, out = hip_forward(d, dev)
+    # the path the layout names, from the CPU model of the dispatch under the pinned capacity, and the plan the library reports for the call
+    regimes = sort_regimes_of(st, st["R"])
+    want = {"uniform": (8, "slabs"), "one-dense-tile": (4, "slabs"), "dense-and-tied": (4, "global")}[layout]
+    assert regimes[want] >= 1 and {i for i, _ in regimes} == ({8} if layout == "uniform" else {4}), dict(regimes)
+    with pinned_capacity(st["R"]):
+        retries = _C.stats["retries"]
+        g_, out = hip_forward(d, dev)
+        assert sort_plan_of(N, W, H, st["R"], retries) == (_C.SORT_SECOND_INSTANTIATION if layout == "uniform" else _C.SORT_IN_BLEND)
     bv = _C.binning_views(out[6], N, out[0], W, H, _C.stats["capacity"]); iv = _C.image_views(out[7], W, H)
     assert out[0] == st["R"]
     assert np.array_equal(iv["ranges"].cpu().numpy().view(np.uint32), st["ranges"])
@@ -624,7 +683,14 @@ def test_tiles_just_over_the_small_sorts_register_capacity(layout):
     lens = (st["ranges"][:, 1] - st["ranges"][:, 0])
     assert ((lens > 1792) & (lens <= 2048)).any(), sorted(lens.tolist())[-8:]
     assert (layout == "every-tile") == (lens.mean() > 2048), float(lens.mean())      # > 2048 on average: both instantiations are launched
-    g_, out = hip_forward(d, dev)
+    from tests import sort_regimes as sr
+    just_over = [i for i in sr.regime_of_tiles(st, st["R"], 0).values() if 1792 < i.n <= 2048]
+    want = (8, "one-pass") if layout == "every-tile" else (4, "slabs")
+    assert just_over and all((i.inst, i.regime) == want for i in just_over), just_over
+    with pinned_capacity(st["R"]):
+        retries = _C.stats["retries"]
+        g_, out = hip_forward(d, dev)
+        assert sort_plan_of(N, W, H, st["R"], retries) == (_C.SORT_SECOND_INSTANTIATION if layout == "every-tile" else _C.SORT_IN_BLEND)
     bv = _C.binning_views(out[6], N, out[0], W, H, _C.stats["capacity"]); iv = _C.image_views(out[7], W, H)
     assert out[0] == st["R"]
     assert np.array_equal(iv["ranges"].cpu().numpy().view(np.uint32), st["ranges"])
@@ -646,21 +712,31 @@ def test_ready_to_pin_harness_runs_against_the_hip_path(tmp_path):
 
 
 def test_ballot_rank_fallback_sorts_identically():
-    """The per-tile sort has two rankers (LDS-atomic, verified on the device at first use; ballot-based fallback)."""
+    """The per-tile sort has two rankers (LDS-atomic, verified on the device at first use; ballot-based fallback).  A ranker is only called
+    by the digit passes: the generic scene (every tile sorted in one pass of buckets and comparisons) shows that the flag changes nothing
+    there; the second scene holds tiles with all depths equal, with a pile of distinct depths and with a pile of tied depths
+    (tests/sort_regimes.py), where the ranker this test names does the sorting."""
     from egogaussian_amd import _C, lib
+    from tests import sort_regimes as sr
     dev = _dev()
+    sc, st_r = sr.oracle_state("solo-registers")
+    assert sr.reach(sc, st_r, "blend", ballot=True) >= {f"4-solo/blend/{r}" for r in ("equal", "digits", "digits+ties")}      # (outside the model's guard band)
     d = make_inputs(6000, 96, 128, 9, 0, "sh_cov", scale_mul=3.0)
-    o, st = oracle_forward(d)
-    res = []
-    for force in (0, 1):
-        old = _C.force_ballot_rank(force)                            # (the default of calls that do not say: EGS_CALL_BALLOT_RANK in their flags word)
-        try:
-            g, out = hip_forward(d, dev)
-        finally:
-            _C.force_ballot_rank(old)
-        bv = _C.binning_views(out[6], 6000, out[0], 128, 96, _C.stats["capacity"])
-        res.append(bv["point_list"].cpu().numpy().view(np.uint32).copy())
-    assert np.array_equal(res[0], st["point_list"]) and np.array_equal(res[1], st["point_list"])
+    for d, st in ((d, oracle_forward(d)[1]), (sc.d, st_r)):
+        N, H, W = int(st["P"]), d["image_height"], d["image_width"]
+        res = []
+        for force in (0, 1):
+            old = _C.force_ballot_rank(force)                            # (the default of calls that do not say: EGS_CALL_BALLOT_RANK in their flags word)
+            try:
+                with pinned_capacity(st["R"]):
+                    retries = _C.stats["retries"]
+                    g, out = hip_forward(d, dev)
+                    assert sort_plan_of(N, W, H, st["R"], retries) == _C.SORT_IN_BLEND | (_C.SORT_BALLOT_RANK if force else 0)
+            finally:
+                _C.force_ballot_rank(old)
+            bv = _C.binning_views(out[6], N, out[0], W, H, _C.stats["capacity"])
+            res.append(bv["point_list"].cpu().numpy().view(np.uint32)[:st["R"]].copy())
+        assert np.array_equal(res[0], st["point_list"]) and np.array_equal(res[1], st["point_list"])
 
 
 def test_mark_visible_matches_oracle():

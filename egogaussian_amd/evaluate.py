@@ -9,8 +9,10 @@ writes the frame's row -- squared 8-bit error, SSIM sum, the forward's overflow 
 once, after the last frame.  A frame whose row says the captured instance capacity clipped it is rendered again eagerly (the eager forward
 sizes its buffers itself) and measured by the same kernel: an evaluation is never silently clipped.
 
-LPIPS, the reference's third figure, is not covered: it needs VGG weights this package does not ship.
-losses.eval_metrics is the torch statement of the per-frame definition.
+LPIPS, the reference's third figure, joins the same replay when the caller hands over the VGG weights (EvalPass(lpips=lpips.LPIPS(...));
+this package ships none): the metric kernel's quantised images and the frame's gate go through csrc/lpips.hip inside the captured body, the
+frame's six float64 figures land at a cursor of their own, and the sweep's one host read fetches both row arrays together.
+losses.eval_metrics and lpips.lpips_vgg are the torch statements of the per-frame definitions.
 """
 import numpy as np
 import torch
@@ -33,22 +35,32 @@ def decode_rows(rows, n_elements):
     return dict(sse=sse, ssim_sum=ssim_sum, ssim=ssim_sum / float(n_elements), psnr=psnr, clipped=r[:, 2] != 0, instances=r[:, 3].copy())
 
 
+def decode_lpips_rows(rows):
+    """rows: float64[F, 6] (include/egs_raster.h egs_lpips_forward), on any device -> dict of numpy arrays lpips_taps [F,5], lpips [F]."""
+    r = np.ascontiguousarray(rows.detach().cpu().numpy()).reshape(-1, fused.LPIPS_ROW_WORDS)
+    return dict(lpips_taps=r[:, :5].copy(), lpips=r[:, 5].copy())
+
+
 class EvalPass(CapturedSweep):
     _what, _statement = "evaluation pass", "losses.eval_metrics"
     _packed = "graph.pack_frame(cam, gt[, accum_R][, gate][, accum_T])"
     _replaced = ("sse", "ssim_sum", "ssim", "psnr")
 
-    def __init__(self, pc, bg, pipe=Pipe, dynamic=False, motion=False, which_object=1, graphed=True, keep_images=False):
+    def __init__(self, pc, bg, pipe=Pipe, dynamic=False, motion=False, which_object=1, graphed=True, keep_images=False, lpips=None):
         """dynamic / motion / which_object: as graph.GraphedTrainStep -- the render is called exactly as its captured step calls it
         (rot_cov=True, accum_R from the frame; with motion the object is placed by the frame's accum_T inside the rasterizer).
         graphed=False: the same calls, eagerly, frame by frame (no capture, no capacity to outgrow).
         keep_images: run() also returns the quantised renders, uint8[F,3,H,W] on the device -- what goes into the PNGs.
+        lpips: an lpips.LPIPS -- run() also returns the frames' LPIPS (of the quantised, gated images), computed inside the same body.
         A capacity.CapacityGaussians model is followed through its live row count like every render()."""
         if motion and not dynamic:
             raise ValueError("EvalPass(motion=True) goes with dynamic=True (the pose's rotation turns the covariances)")
         super().__init__(pc, bg, graphed)
         self.pipe, self.keep_images = pipe, bool(keep_images)
         self.dynamic, self.motion, self.which_object = bool(dynamic), bool(motion), which_object
+        self.lpips = lpips
+        if lpips is not None:
+            self._replaced = EvalPass._replaced + ("lpips", "lpips_taps")
 
     # ---- what the shared sweep asks for ----------------------------------------------------------------------------------------------
     def _options(self):
@@ -71,14 +83,37 @@ class EvalPass(CapturedSweep):
         with torch.no_grad():
             out = render(self._cam, self.pc, self.pipe, self.bg, color_only=True, **({"guard": guard} if guard is not None else {}),
                          **(dynamic_kwargs(self._f, self.which_object) if self.dynamic else {}))
-            return out, fused.eval_metrics(out["render"], self._gt, keep=self._gate, rows=rows, cursor=cursor,
-                                           overflow=None if guard is None else guard.overflow, out8=self.keep_images)
+            res = fused.eval_metrics(out["render"], self._gt, keep=self._gate, rows=rows, cursor=cursor,
+                                     overflow=None if guard is None else guard.overflow, out8=self.keep_images or self.lpips is not None)
+            if self.lpips is not None:
+                lp_rows, lp_cursor = (None, None) if rows is None else self._partner(rows)
+                self.lpips(res["q_image"], res["q_gt"], keep=self._gate, rows=lp_rows, cursor=lp_cursor)
+            return out, res
 
     def _new_rows(self, n, dev):
-        return fused.eval_rows(n, dev)
+        rows, cursor = fused.eval_rows(n, dev)
+        if self.lpips is not None:
+            rows.lpips_partner = fused.lpips_rows(n, dev)                      # the row array carries its LPIPS (rows, cursor): one lifetime
+        return rows, cursor
+
+    @staticmethod
+    def _partner(rows):
+        """The LPIPS (rows, cursor) that _new_rows gave this row array (or the array `rows` is a slice of), else None."""
+        return getattr(rows if rows._base is None else rows._base, "lpips_partner", None)
+
+    def _read_rows(self, rows):
+        """Still ONE read: the LPIPS rows travel as six more int64 words of each row."""
+        lp = self._partner(rows)
+        if lp is None:
+            return super()._read_rows(rows)
+        self.host_reads += 1
+        return torch.cat([rows, lp[0][:rows.shape[0]].view(torch.int64)], 1).cpu()
 
     def _decode(self, rows):
-        return decode_rows(rows, self._shape[0] * self._shape[1] * self._shape[2])
+        fig = decode_rows(rows[:, :fused.EVAL_ROW_WORDS].contiguous(), self._shape[0] * self._shape[1] * self._shape[2])
+        if rows.shape[1] > fused.EVAL_ROW_WORDS:
+            fig.update(decode_lpips_rows(rows[:, fused.EVAL_ROW_WORDS:].contiguous().view(torch.float64)))
+        return fig
 
     def _new_out(self, n, dev):
         return torch.empty((n,) + self._shape, dtype=torch.uint8, device=dev) if self.keep_images else None
@@ -93,10 +128,16 @@ class EvalPass(CapturedSweep):
         (a captured pass is specific to one, like a captured step).  capacity: the instance capacity to capture with, as is (default:
         capacity_margin x the first frame's count; frames that outgrow it are rendered again eagerly).
         -> dict(psnr, ssim: float64[F]; sse: int64[F]; mean_psnr, mean_ssim: the plain means; rerendered: indices of the frames rendered
-        again; instances: int64[F], the captured forwards' instance counts (0 for eager frames)[; images: uint8[F,3,H,W] on the device])."""
+        again; instances: int64[F], the captured forwards' instance counts (0 for eager frames)[; images: uint8[F,3,H,W] on the device]
+        [; lpips: float64[F], lpips_taps: float64[F,5], mean_lpips -- with lpips=])."""
+        if self.lpips is not None and self.graph is not None:
+            for t in self._partner(self._rows):                                # the captured rows' partner starts again at row 0, as they do
+                t.zero_()
         fig, again, images = self._sweep(frames, cam, capacity, capacity_margin)
         out = dict(psnr=fig["psnr"], ssim=fig["ssim"], sse=fig["sse"], mean_psnr=float(np.mean(fig["psnr"])), mean_ssim=float(np.mean(fig["ssim"])),
                    rerendered=again, instances=fig["instances"])
         if images is not None:
             out["images"] = images
+        if self.lpips is not None:
+            out.update(lpips=fig["lpips"], lpips_taps=fig["lpips_taps"], mean_lpips=float(np.mean(fig["lpips"])))
         return out

@@ -580,6 +580,14 @@ def eval_metrics(image, gt, keep=None, rows=None, cursor=None, overflow=None, ou
     return dict(rows=rows, cursor=cursor, q_image=q_img, q_gt=q_gt)
 
 
+LPIPS_ROW_WORDS = 6     # a row of include/egs_raster.h egs_lpips_forward as float64 words: tap_1 .. tap_5, their sum
+
+
+def lpips_rows(capacity, device):
+    """(rows float64[capacity, 6] zeroed, cursor int32[1] = 0) for lpips.LPIPS: the caller-owned result array and the device-side frame index."""
+    return torch.zeros((int(capacity), LPIPS_ROW_WORDS), dtype=torch.float64, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+
+
 MASK_ROW_WORDS = 6      # include/egs_raster.h egs_mask_row as int64 words: predicted, target, intersection, kept, clipped, instances
 
 

@@ -101,6 +101,10 @@ class PoseSequence(C.Structure):                 # egs_pose_sequence
                [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
 
 
+class LpipsWeights(C.Structure):               # egs_lpips_weights
+    _fields_ = [("conv_w", C.c_void_p * 13), ("conv_b", C.c_void_p * 13), ("lin", C.c_void_p * 5)]
+
+
 FRAME_DYNAMIC, FRAME_MOTION, FRAME_GATED, FRAME_OBJECT_LOSS, FRAME_LABEL_PHASE = 1, 2, 4, 8, 16      # EGS_FRAME_*
 FRAME_POSE_ROWS = 32                             # EGS_FRAME_POSE_ROWS
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
@@ -165,6 +169,10 @@ SIGNATURES = {
     "egs_l1_ssim_pair_forward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egs_eval_metrics_partial_bytes": (C.c_size_t, [i32, i32, i32]),
     "egs_eval_metrics": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+    "egs_lpips_workspace_bytes": (C.c_size_t, [i32, i32]),
+    "egs_lpips_tap_offsets": (C.c_int, [i32, i32, C.POINTER(i64)]),
+    "egs_lpips_forward": (C.c_int, [i32, i32, vp, vp, vp, C.POINTER(LpipsWeights), vp, vp, i32, vp, vp]),
+    "egs_conv3x3_relu_nhwc": (C.c_int, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "egs_label_mask_partial_bytes": (C.c_size_t, [i32, i32]),
     "egs_label_mask": (C.c_int, [i32, i32, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
     "egs_interaction_gate": (C.c_int, [i32, i32, vp, vp, i32, vp, vp]),

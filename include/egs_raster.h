@@ -534,6 +534,47 @@ int egs_label_mask(int height, int width, const float* img /*[3,H,W]*/, float th
 int egs_interaction_gate(int height, int width, const float* a /*[H,W] or NULL*/, const float* b /*[H,W] or NULL*/, int k,
                          float* gate /*[H,W] out*/, void* stream);
 
+/* ---- LPIPS (VGG-16) of two 8-bit images: the evaluation pass's third figure (added within ABI 6: new entries only).
+ *      The definition (the Python package's lpips.lpips_vgg is its torch statement; it is written from the published definition and is NOT
+ *      pinned against the lpipsPyTorch package the reference imports):
+ *          u = kept ? byte / 255 : 0   (kept = keep >= 0.5; NULL: every pixel)      z = (u - mean) / std, NOT mapped to [-1, 1] first,
+ *              mean = (-.030, -.088, -.188), std = (.458, .448, .450)
+ *          the 13 3x3 convolutions of VGG-16's `features` (stride 1, zero padding 1 -- zero in z-scored space --, bias, ReLU) in blocks of
+ *              2, 2, 3, 3, 3 with a 2x2 / stride 2 / floor maximum pool between the blocks; a tap after each block's last ReLU, before the pool
+ *          n = f / (sqrt(sum_c f^2) + 1e-10)  (eps OUTSIDE the root)     tap_k = mean over pixels of sum_c lin_k[c] (n_x - n_y)^2
+ *          lpips = tap_1 + ... + tap_5
+ *      Activations are float32 NHWC, the two images a batch of 2.  Convolutions run on the matrix pipe with f32 inputs and f32
+ *      accumulation (v_mfma_f32_32x32x2_f32: exact f32 products).  Weights come from the caller -- none are shipped --, each convolution's
+ *      repacked K-major: packed_w[(tap * Cin + c) * Cout + o] = w[o][c][tap / 3][tap % 3], tap = 3 ky + kx; the first layer's Cin padded
+ *      3 -> 4 with zeros.
+ *
+ *      egs_lpips_forward: q_x, q_y device uint8[3,H,W] planar (what egs_eval_metrics writes as q_img / q_gt), keep device float[H,W] or
+ *      NULL.  workspace: egs_lpips_workspace_bytes(H, W) device bytes, 256-byte aligned, owned by the caller (the library allocates nothing);
+ *      it keeps all five tap maps (122 H W floats per image) next to the scratch of the other layers: 412 H W floats = 0.85 GB at 960 x 540.
+ *      egs_lpips_tap_offsets gives the byte offsets of the five tap maps in it, float[2, H >> k, W >> k, C_k], C = 64, 128, 256, 512, 512.
+ *      20 launches on `stream`: the input, 13 convolutions, five tap kernels (channel norms, weighted squared difference, one float64
+ *      partial per workgroup, and the pooled map of the next block) and ONE wave that adds each tap's partials in a fixed order in float64,
+ *      writes rows[cursor[0]] = (tap_1 .. tap_5, lpips) as double[6] and stores cursor[0] + 1 -- the conventions of egs_eval_metrics:
+ *      cursor[0] outside [0, capacity) writes nothing and still advances.  No float atomics: the row is bit-identical run to run, and an
+ *      identical pair gives exact zeros.  EGS_ERR_ARG before any device work: H or W < 16 (a pool would have no output), a NULL pointer
+ *      other than keep, a misaligned workspace or weight array (16 bytes), capacity < 0.  H or W > 8192: EGS_ERR_RANGE (workspace_bytes: 0).
+ *
+ *      egs_conv3x3_relu_nhwc: one layer of the chain by itself, out[n,H,W,Cout] = relu(conv3x3(in[n,H,W,Cin]) + bias); H, W >= 1 (maps
+ *      smaller than a tile are masked, never read outside).  Cin = 4 or a multiple of 16, Cout a multiple of 64, in != out, 16-byte
+ *      aligned arrays (else EGS_ERR_ARG); H, W > 32767, Cin, Cout > 4096, n > 65535: EGS_ERR_RANGE. */
+typedef struct egs_lpips_weights {
+    const float* conv_w[13];         /* device, packed [9 Cin, Cout] (above) */
+    const float* conv_b[13];         /* device [Cout] */
+    const float* lin[5];             /* device [C_k]: the linear heads' weights */
+} egs_lpips_weights;
+size_t egs_lpips_workspace_bytes(int height, int width);
+int egs_lpips_tap_offsets(int height, int width, int64_t* offsets /*host [5] out*/);
+int egs_lpips_forward(int height, int width, const uint8_t* q_x /*[3,H,W]*/, const uint8_t* q_y /*[3,H,W]*/,
+                      const float* keep /*[H,W] or NULL: all kept*/, const egs_lpips_weights* weights, void* workspace,
+                      void* rows /*double[capacity][6]*/, int capacity, int32_t* cursor /*device [1] in/out*/, void* stream);
+int egs_conv3x3_relu_nhwc(int n, int height, int width, int cin, int cout, const float* in /*[n,H,W,Cin]*/,
+                          const float* packed_w /*[9 Cin, Cout]*/, const float* bias /*[Cout]*/, float* out /*[n,H,W,Cout]*/, void* stream);
+
 /* ---- the 8-bit frame store (added within ABI 6: new entries only).
  *      The reference's images come from 8-bit files (utils/general_utils.py: uint8 -> float / 255) and its masks are binarised to {0, 1}; a
  *      packed float32 frame of the captured steps (camera, image, accumulated pose, gate, object mask) therefore says in 16 - 20 bytes per

@@ -2,6 +2,7 @@
 //   egs_pose_head        the frame's pose in the rasterizer's form, A12 = [A | b] and M9, from the table and the trainable pose
 //   egs_pose_tail        dL/dA12, dL/dM9 -> dL/dpose, the pose's Adam step, the frame's table row, the accumulated rows from it on
 //   egs_pose_accumulate  the accumulated rows from scratch
+//   egs_pose_interpolate stage 4: the rows of the held-out dynamic frames, one wave per gap (its own section below)
 // Replaces what the object stages do on the host around every dynamic iteration (/root/reference/trainers/fine_obj.py:97-126,216-224: the
 // `.data` reload, get_obj_trans_rot, get_accum_T_seq / get_accum_R_seq over all keys) and the dozen tiny torch launches each way of
 // motion.ObjectMotion.compose() inside a captured step.  egogaussian_amd/poses.py holds the torch statement of every formula here.
@@ -77,9 +78,8 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ __forceinline__ void rot6_forward(const float* r6, Rot6& s, double* R /*[9] row-major*/) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) { s.a1[i] = (double)r6[2 * i]; s.a2[i] = (double)r6[2 * i + 1]; }
+// s.a1, s.a2 given: the rest of s, and R
+__device__ __forceinline__ void rot6_from(Rot6& s, double* R /*[9] row-major*/) {
     s.n1 = fmax(sqrt(dot3(s.a1, s.a1)), POSE_NORM_FLOOR);
 #pragma unroll
     for (int i = 0; i < 3; i++) s.b1[i] = s.a1[i] / s.n1;
@@ -93,6 +93,12 @@ __device__ __forceinline__ void rot6_forward(const float* r6, Rot6& s, double* R
     cross3(s.b1, s.b2, b3);
 #pragma unroll
     for (int i = 0; i < 3; i++) { R[3 * i] = s.b1[i]; R[3 * i + 1] = s.b2[i]; R[3 * i + 2] = b3[i]; }
+}
+
+__device__ __forceinline__ void rot6_forward(const float* r6, Rot6& s, double* R /*[9] row-major*/) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { s.a1[i] = (double)r6[2 * i]; s.a2[i] = (double)r6[2 * i + 1]; }
+    rot6_from(s, R);
 }
 
 // y = x / max(|x|, floor) backwards: through the norm only while it is above the floor (torch's clamp_min)
@@ -292,6 +298,131 @@ __global__ __launch_bounds__(EGS_WAVE) void k_pose_tail(PoseSeq q, const int32_t
 
 __global__ __launch_bounds__(EGS_WAVE) void k_pose_accumulate(PoseSeq q) { accumulate_from(q, 0, nullptr, threadIdx.x == 0); }
 
+// ---- stage 4: the poses of the held-out frames inside the dynamic phases (/root/reference/trainers/interpolate_pose.py:28-63) --------------
+// A gap is n consecutive rows of the NEW table that end at a key of the OLD one; all n receive the pose M whose n-th power the reference
+// fits to the key's pose T by `iters` steps of plain gradient descent from the identity: loss = mean over the 16 entries of (M^n - T)^2,
+// M = [R(r6) | t].  What the later stages consume is the END POINT of that descent (for a short gap and a small motion it has not
+// converged), so the descent itself runs here: one wave per gap, the parameters in float64 registers from the first iteration to the
+// last, no memory traffic inside the loop.
+// The wave.  All factors are the same matrix, so dL/dM = sum over k = 1 .. n of (M^(k-1))^T G (M^(n-k))^T with G = dL/dM^n.  Lane k - 1
+// forms term k from powers it builds itself: the running square M, M^2, M^4 .. is the same in every lane and each lane multiplies the
+// squares its two exponents select (at most five each, n <= 32).  The bottom row of every factor is (0 0 0 1): only the top three rows
+// of G reach the top three rows of a term, so a term is twelve numbers.  They are summed over the wave by an xor butterfly -- a + b
+// and b + a are the same double, so every lane ends with the same twelve sums, in an order that depends on nothing but n -- and every
+// lane takes the same step.  No LDS, no barrier.
+// M^n itself is the product of the squares n's bits select, not the reference's left-to-right chain: in float64 the two differ in the
+// sixteenth place.
+#define POSE_GAP_MAX 32
+
+// A <- A o S where bit `b` of e is set (per lane)
+__device__ __forceinline__ void power_step(Affine& A, const Affine& S, int e, int b) {
+    if ((e >> b) & 1) A = affine_mul(A, S);
+}
+
+// M^a, M^b per lane and M^n (n uniform) from one run of squarings; exponents in [0, 32]
+__device__ __forceinline__ void affine_powers(const Affine& M, int a, int b, int n, Affine& A, Affine& B, Affine& P) {
+    Affine S = M;
+    A = affine_identity(); B = affine_identity(); P = affine_identity();
+#pragma unroll
+    for (int bit = 0; bit < 6; bit++) {
+        if (bit < 5) { power_step(A, S, a, bit); power_step(B, S, b, bit); }
+        power_step(P, S, n, bit);
+        if (bit < 5) S = affine_mul(S, S);
+    }
+}
+
+__device__ __forceinline__ Affine affine_from(const double* R, const double* t) {
+    Affine M;
+#pragma unroll
+    for (int i = 0; i < 3; i++) { M.a[4 * i] = R[3 * i]; M.a[4 * i + 1] = R[3 * i + 1]; M.a[4 * i + 2] = R[3 * i + 2]; M.a[4 * i + 3] = t[i]; }
+    return M;
+}
+
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+    for (int m = 1; m < EGS_WAVE; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+__global__ __launch_bounds__(EGS_WAVE) void k_pose_interpolate(const float* __restrict__ from_rel, int K_from, float* __restrict__ to_rel,
+                                                               uint8_t* __restrict__ to_valid, int K_to, const int32_t* __restrict__ gaps, int G,
+                                                               int iters, float lr_f, float* __restrict__ residual, int32_t* __restrict__ status) {
+    const int lane = (int)threadIdx.x;
+    // every wave reads ALL the words first: one bad gap and no wave writes anything
+    int bad = 0;
+    for (int g = lane; g < G; g += EGS_WAVE) {
+        const int first = gaps[3 * (size_t)g], n = gaps[3 * (size_t)g + 1], old_row = gaps[3 * (size_t)g + 2];
+        bad |= n < 2 || n > POSE_GAP_MAX || first < 0 || first > K_to - n || old_row < 0 || old_row >= K_from;
+    }
+    bad = __any(bad);
+    if (blockIdx.x == 0 && lane == 0) *status = bad ? 1 : 0;
+    if (bad) return;
+    const int first = gaps[3 * (size_t)blockIdx.x], n = gaps[3 * (size_t)blockIdx.x + 1], old_row = gaps[3 * (size_t)blockIdx.x + 2];
+    const Affine T = affine_load(from_rel + 12 * (size_t)old_row);
+    const bool member = lane < n;                                   // lane l forms term k = l + 1: exponents l and n - 1 - l
+    const int ea = member ? lane : 0, eb = member ? n - 1 - lane : 0;
+    const double lr = (double)lr_f;
+    double t[3] = { 0.0, 0.0, 0.0 }, R[9];
+    Rot6 s;
+#pragma unroll
+    for (int i = 0; i < 3; i++) { s.a1[i] = i == 0 ? 1.0 : 0.0; s.a2[i] = i == 1 ? 1.0 : 0.0; }
+#pragma unroll 1
+    for (int it = 0; it < iters; it++) {
+        rot6_from(s, R);
+        const Affine M = affine_from(R, t);
+        Affine A, B, P;
+        affine_powers(M, ea, eb, n, A, B, P);
+        // G = dL/dP over the top three rows = 2 (P - T) / 16; the reference's early exit on the float32 product: isclose(rtol 1e-7, atol 1e-9)
+        double Gm[12];
+        bool met = true;
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            Gm[k] = (P.a[k] - T.a[k]) * 0.125;
+            met = met && fabs((double)(float)P.a[k] - T.a[k]) <= 1e-9 + 1e-7 * fabs(T.a[k]);
+        }
+        // the term: X = A_R^T G [3x4], Y = X B^T restricted to the top three rows -- columns 0 .. 2 dL/dR, column 3 dL/dt
+        double X[12], Y[12];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int l = 0; l < 4; l++) X[4 * i + l] = fma(A.a[8 + i], Gm[8 + l], fma(A.a[4 + i], Gm[4 + l], A.a[i] * Gm[l]));
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                Y[4 * i + j] = fma(X[4 * i + 3], B.a[4 * j + 3], fma(X[4 * i + 2], B.a[4 * j + 2], fma(X[4 * i + 1], B.a[4 * j + 1], X[4 * i] * B.a[4 * j])));
+            Y[4 * i + 3] = X[4 * i + 3];
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) Y[k] = wave_sum_all(member ? Y[k] : 0.0);
+        double GR[9], g6[6];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) GR[3 * i + j] = Y[4 * i + j];
+        rot6_backward(s, GR, g6);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            t[i] = t[i] - lr * Y[4 * i + 3];
+            s.a1[i] = s.a1[i] - lr * g6[2 * i];
+            s.a2[i] = s.a2[i] - lr * g6[2 * i + 1];
+        }
+        if (met) break;                                             // (tested on the product before the step, left after it: the reference's order)
+    }
+    rot6_from(s, R);
+    const Affine M = affine_from(R, t);
+    Affine A, B, P;
+    affine_powers(M, 0, 0, n, A, B, P);
+    double r = 0.0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) { const double d = fabs(P.a[k] - T.a[k]); r = (d > r || d != d) ? d : r; }      // (a NaN stays one)
+    if (member) {
+        affine_store(to_rel + 12 * (size_t)(first + lane), M);
+        to_valid[first + lane] = 1;
+    }
+    if (lane == 0) residual[blockIdx.x] = (float)r;
+}
+
 bool pose_seq_args(const egs_pose_sequence* s, PoseSeq& q) {
     if (!s || s->K < 1 || !s->rel || !s->valid || !s->accum || !s->pose || !s->exp_avg || !s->exp_avg_sq || !s->step || !s->lr) return false;
     q.K = s->K; q.rel = s->rel; q.valid = s->valid; q.accum = s->accum; q.pose = s->pose; q.m = s->exp_avg; q.v = s->exp_avg_sq;
@@ -322,6 +453,22 @@ int egs_pose_accumulate(const egs_pose_sequence* seq, void* stream) {
     if (!pose_seq_args(seq, q)) return EGS_ERR_ARG;
     hipLaunchKernelGGL(k_pose_accumulate, dim3(1), dim3(EGS_WAVE), 0, (hipStream_t)stream, q);
     return (int)hipGetLastError();
+}
+
+int egs_pose_interpolate(const egs_pose_sequence* from, const egs_pose_sequence* to, const int32_t* gaps, int n_gaps, int iters, float lr,
+                         float* residual, int32_t* status, void* stream) {
+    PoseSeq qf, qt;
+    if (!pose_seq_args(from, qf) || !pose_seq_args(to, qt) || !gaps || !residual || !status || n_gaps < 1 || iters < 0) return EGS_ERR_ARG;
+    if (n_gaps > 65535) return EGS_ERR_RANGE;
+    hipLaunchKernelGGL(k_pose_interpolate, dim3(n_gaps), dim3(EGS_WAVE), 0, (hipStream_t)stream, (const float*)qf.rel, qf.K, qt.rel, qt.valid, qt.K,
+                       gaps, n_gaps, iters, lr, residual, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    int32_t refused = 0;                                            // the words live on the device: the verdict on them is read back
+    e = hipMemcpyAsync(&refused, status, sizeof(refused), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return refused ? EGS_ERR_RANGE : 0;
 }
 
 }  // extern "C"

@@ -181,6 +181,7 @@ SIGNATURES = {
     "egs_pose_head": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp]),
     "egs_pose_tail": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp, vp]),
     "egs_pose_accumulate": (C.c_int, [C.POINTER(PoseSequence), vp]),
+    "egs_pose_interpolate": (C.c_int, [C.POINTER(PoseSequence), C.POINTER(PoseSequence), vp, i32, i32, f32, vp, vp, vp]),
 
     "egs_l1_ssim_pair_backward": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),
     "egs_l1_ssim_backward_ex": (C.c_int, [i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BackwardPrologue), vp]),

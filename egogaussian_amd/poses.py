@@ -11,6 +11,10 @@ earlier keys, stores the result under the frame's key and rebuilds the accumulat
     the torch mirror   rot6d_to_matrix, compose_from_rows, accumulate, tail_step: the same formulas as tensor expressions on any device
                        and in any float type -- the CPU tests' subject, the GPU tests' float32 yardstick and float64 anchor; the role
                        losses.py and motion.py play for their kernels.
+    stage 4            PoseSequence.interpolated(): the table with a row for every held-out frame inside the dynamic phases
+                       (/root/reference/trainers/interpolate_pose.py) -- interpolation_plan is the reference's bookkeeping on ints,
+                       egs_pose_interpolate runs its 1500-step descent for every gap in one launch, decompose_transform is that descent's
+                       torch statement with the gradient written out.
 
 Rows.  A frame is described to the kernels by the word (fixed_row, train_row, reload, 0) of int32, read from DEVICE memory: fixed_row is
 the table row whose accumulated pose lies under the frame (-1: the identity), train_row the row the trainable pose is stored to (-1: a
@@ -87,7 +91,12 @@ def pose_gradient(accum, pose, grad21, fixed_row):
     gA12, gM = grad21[:12].reshape(3, 4), grad21[12:21].reshape(3, 3)
     gA, gb = gA12[:, :3], gA12[:, 3]
     G = gA @ A.t() + gb[:, None] * b[None, :] + gM @ A.t()
-    r6 = pose[3:9].reshape(3, 2)
+    return torch.cat([gb, rot6d_backward(pose[3:9], G)])
+
+
+def rot6d_backward(r6, G):
+    """dL/dr6 [6] (r6's row-major layout) from G = dL/dR [3,3] of R = rot6d_to_matrix(r6), written out."""
+    r6 = r6.reshape(3, 2)
     a1, a2 = r6[:, 0], r6[:, 1]
     n1 = a1.norm().clamp_min(NORM_FLOOR)
     b1 = a1 / n1
@@ -107,7 +116,7 @@ def pose_gradient(accum, pose, grad21, fixed_row):
     ga2 = gu + gd * b1
     g1 = g1 + gd * a2 - d * gu
     ga1 = back(b1, n1, g1)
-    return torch.cat([gb, torch.stack((ga1, ga2), dim=-1).reshape(6)])
+    return torch.stack((ga1, ga2), dim=-1).reshape(6)
 
 
 def tail_step(accum, rel, valid, pose, exp_avg, exp_avg_sq, step, lr, grad21, fixed_row, train_row, betas=BETAS, eps=EPS):
@@ -131,6 +140,116 @@ def tail_step(accum, rel, valid, pose, exp_avg, exp_avg_sq, step, lr, grad21, fi
     valid2[train_row] = 1
     return dict(dpose=g, pose=p, exp_avg=m, exp_avg_sq=v, step=new_step, rel=rel2, valid=valid2,
                 accum=accumulate(rel2, valid2, start=train_row, accum=accum))
+
+
+# ---- stage 4: the poses of the held-out dynamic frames (/root/reference/trainers/interpolate_pose.py) -----------------------------------
+GAP_MIN, GAP_MAX = 2, 32
+DESCENT_ITERS, DESCENT_LR = 1500, 0.01      # decompose_transform's epochs and SGD lr
+RESIDUAL_FACTOR = 3.0                       # x the float32 mirror's figure: the factor of the float32 yardsticks in tests/anchors.py
+RESIDUAL_FLOOR = 2.0 * 2.0 ** -23           # ... and never below two float32 ulps of 1: a float32 product can hit T exactly
+
+
+def _gap_length(n):
+    n = int(n)
+    if n < GAP_MIN or n > GAP_MAX:
+        raise ValueError(f"pose interpolation: a gap of {n} frames is outside [{GAP_MIN}, {GAP_MAX}] -- below 2 there is nothing to split; the "
+                         "reference's descent (lr 0.01 on the mean over 16 entries) has step x curvature of about 0.00125 n^2, which reaches "
+                         "2 at n = 40: from 40 frames on it diverges (final loss 1.7 at 40, NaN at 48) and there is no behaviour to reproduce; "
+                         "33 to 39 is not characterised")
+    return n
+
+
+def _homogeneous(R, t):
+    M = torch.eye(4, dtype=R.dtype, device=R.device)
+    M[:3, :3], M[:3, 3] = R, t
+    return M
+
+
+def _chain(M, n):
+    """[M, M M, ..., M^n] as the reference builds its product: left to right, n factors."""
+    out = [M]
+    for _ in range(1, n):
+        out.append(out[-1] @ M)
+    return out
+
+
+def descent_gradient(t, r6, T, n):
+    """(P = M^n, dL/dt [3], dL/dr6 [6]) of L = mean over the 16 entries of (M^n - T)^2, M = [R(r6) | t; 0 0 0 1], written out: all n
+    factors are the same matrix, so dL/dM = sum_k (M^(k-1))^T G (M^(n-k))^T with G = 2 (P - T) / 16; its rotation block goes back through
+    the 6-D map (rot6d_backward), its last column is dL/dt."""
+    M = _homogeneous(rot6d_to_matrix(r6), t)
+    powers = _chain(M, n)
+    P = powers[-1]
+    S = torch.stack([torch.eye(4, dtype=M.dtype, device=M.device)] + powers[:-1])          # S[j] = M^j, j = 0 .. n - 1
+    dM = (S.transpose(1, 2) @ ((P - T) * (2.0 / 16.0)) @ S.flip(0).transpose(1, 2)).sum(0)
+    return P, dM[:3, 3], rot6d_backward(r6, dM[:3, :3])
+
+
+def decompose_transform(T, n, dtype=torch.float32, iters=DESCENT_ITERS, lr=DESCENT_LR):
+    """The reference's decompose_transform (interpolate_pose.py:28-63) as tensor expressions with the analytic gradient ->
+    (translation [3], rotation [3,3], residual).  From t = 0, r6 = I[:, :2]: `iters` plain gradient steps of size lr on the mean over all
+    16 entries of (M^n - T)^2; the loop leaves AFTER the step at which isclose(M^n, T, rtol=1e-7, atol=1e-9) held on every entry of the
+    product computed before that step.  The result is the END POINT (t, R(r6)) -- for a short gap and a small motion the descent has
+    not converged, and the end point is what the later stages consume; residual = max |M^n - T| of it.  T: a 4x4 transform (or a 3x4
+    [R | t] block), any device; n outside [2, 32]: ValueError."""
+    n = _gap_length(n)
+    T = torch.as_tensor(T).detach().to(dtype)
+    if tuple(T.shape) == (3, 4) or T.numel() == 12:
+        T = torch.cat([T.reshape(3, 4), torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=dtype, device=T.device)])
+    T = T.reshape(4, 4)
+    t = torch.zeros(3, dtype=dtype, device=T.device)
+    r6 = torch.eye(3, dtype=dtype, device=T.device)[:, :2].reshape(6).clone()
+    for _ in range(int(iters)):
+        P, gt, g6 = descent_gradient(t, r6, T, n)
+        done = bool(torch.isclose(P, T, rtol=1e-7, atol=1e-9).all())
+        t, r6 = t - lr * gt, r6 - lr * g6
+        if done:
+            break
+    R = rot6d_to_matrix(r6)
+    return t, R, (_chain(_homogeneous(R, t), n)[-1] - T).abs().max()
+
+
+def interpolation_plan(keys, valid, frame_names, dynamic_phases):
+    """The reference's two passes over the sequence (interpolate_pose.py:83-109) on ints -> (new_keys, carried, gaps).
+    keys, valid: the old table's keys and one truth value per key; frame_names: every training frame; dynamic_phases: (first, last)
+    frame names, both ends inclusive.  new_keys: the new table's keys, sorted (the entries of frame_names as given); carried: {new row:
+    old row} of the rows that keep the old table's entry, valid or not; gaps: [(first_row, n, old_row)] -- n consecutive new rows ending
+    at the key old_row of the old table, all n of which receive the same pose, the key included.
+    Pass 1 walks the frames in order: an old key is taken over whatever the phases say; any other frame inside the CURRENT phase becomes
+    an empty entry; the phase index advances by one after a frame past the current phase's end (after that frame's own test, one phase
+    per frame), and the walk ends with the frame that moved it past the last phase -- old keys after it are dropped.  Pass 2 collects
+    runs of empty entries (an old key without a pose is one) up to the next key that has a pose; a run with no such key after it stays
+    empty."""
+    old = {int(k): i for i, k in enumerate(keys)}
+    phases = [(int(a), int(b)) for a, b in dynamic_phases]
+    if not phases:
+        raise ValueError("interpolation_plan: no dynamic phase")
+    frames = sorted(frame_names, key=int)
+    new_keys, source = [], []                        # source: the old row, or -1 for an empty entry
+    phase = 0
+    for name in frames:
+        f = int(name)
+        if f in old:
+            new_keys.append(name); source.append(old[f])
+        elif phases[phase][0] <= f <= phases[phase][1]:
+            new_keys.append(name); source.append(-1)
+        if f > phases[phase][1]:
+            phase += 1
+        if phase > len(phases) - 1:
+            break
+    carried = {row: src for row, src in enumerate(source) if src >= 0}
+    gaps, run = [], []
+    for row, src in enumerate(source):
+        has_pose = src >= 0 and bool(valid[src])
+        if not has_pose:
+            run.append(row)
+        elif run:
+            run.append(row)
+            gaps.append((run[0], len(run), src))
+            for r in run:
+                carried.pop(r, None)
+            run = []
+    return new_keys, carried, gaps
 
 
 # ---- the device-resident table --------------------------------------------------------------------------------------------------------
@@ -246,6 +365,51 @@ class PoseSequence:
         """get_accum_R_seq of export(): {key: 3x3 CPU tensor, None for an invalid key} -- the rotation blocks of accum."""
         acc, valid = self.accum.cpu().reshape(self.K, 3, 4), self.valid.cpu().tolist()
         return {k: (acc[i, :, :3].clone() if valid[i] else None) for i, k in enumerate(self.keys)}
+
+    def interpolated(self, frame_names, dynamic_phases, check=True):
+        """Stage 4 (interpolate_pose_seq): a NEW table on the same device whose keys are interpolation_plan's -- the old keys up to the
+        end of the last phase plus every other frame of frame_names inside a phase -- with the carried rows copied bit for bit and the
+        rows of every gap filled with the end point of the reference's descent: ONE launch of egs_pose_interpolate over all gaps on a
+        HIP device, decompose_transform per gap on the CPU.  accumulate() has been run; the pose and its Adam state are fresh (the
+        learning rates 0).  .gaps is the plan's list, .gap_residual float32[G] max |M^n - T| per gap.
+        check (HIP only; the CPU rows ARE the mirror's): one host read of the residuals; a gap whose residual is not within
+        max(RESIDUAL_FACTOR x the residual of its own float32 mirror, RESIDUAL_FLOOR) (decompose_transform on the CPU: about half a second per gap -- pass
+        check=False where that matters) is named in a warning.  A gap longer than 32 frames: ValueError, nothing is built."""
+        new_keys, carried, gaps = interpolation_plan(self._ints, self.valid.cpu().tolist(), frame_names, dynamic_phases)
+        for _, n, _ in gaps:
+            _gap_length(n)
+        new = PoseSequence(new_keys, self.device, self.betas, self.eps)
+        if carried:
+            rows = torch.tensor(sorted(carried), device=self.device)
+            src = torch.tensor([carried[r] for r in sorted(carried)], device=self.device)
+            new.rel[rows], new.valid[rows] = self.rel[src], self.valid[src]
+        new.gaps, G = gaps, len(gaps)
+        new.gap_residual = torch.zeros(G, device=self.device)
+        if G and self.device.type != "cuda":
+            for g, (first, n, old_row) in enumerate(gaps):
+                t, R, res = decompose_transform(self.rel[old_row], n)
+                new.rel[first:first + n] = torch.cat([R, t[:, None]], dim=1).reshape(12)
+                new.valid[first:first + n] = 1
+                new.gap_residual[g] = res
+        elif G:
+            words = torch.tensor(gaps, dtype=torch.int32).to(self.device)
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            with _hip.device_ctx(self.device):
+                _lib.check(_lib.load().egs_pose_interpolate(self.struct(), new.struct(), words.data_ptr(), G, DESCENT_ITERS, DESCENT_LR,
+                                                            new.gap_residual.data_ptr(), status.data_ptr(), _hip.stream_of(self.device)))
+            if check:
+                got, rel = new.gap_residual.cpu().tolist(), self.rel.cpu()
+                off = []
+                for (first, n, old_row), r in zip(gaps, got):
+                    bar = max(RESIDUAL_FACTOR * float(decompose_transform(rel[old_row], n)[2]), RESIDUAL_FLOOR)
+                    if not r <= bar:
+                        off.append(f"frames {new_keys[first]} .. {new_keys[first + n - 1]} (n = {n}): residual {r:.3e} > {bar:.3e}")
+                if off:
+                    import warnings
+                    warnings.warn("PoseSequence.interpolated: the descent of these gaps ended further from its key's pose than "
+                                  f"{RESIDUAL_FACTOR:g} x its float32 mirror does: " + "; ".join(off))
+        new.accumulate()
+        return new
 
     # ---- the kernels ------------------------------------------------------------------------------------------------------------------
     def struct(self):

@@ -668,6 +668,23 @@ int egs_pose_head(const egs_pose_sequence* seq, const int32_t* frame_word /*devi
 int egs_pose_tail(const egs_pose_sequence* seq, const int32_t* frame_word /*device [4]*/, const float* grad21 /*device [21]*/,
                   float* dpose /*device [9] out or NULL*/, const uint32_t* skip_flag /*device [1] or NULL*/, void* stream);
 int egs_pose_accumulate(const egs_pose_sequence* seq, void* stream);
+/* Stage 4, the poses of the held-out frames inside the dynamic phases (added within ABI 6: a new entry only;
+ * /root/reference/trainers/interpolate_pose.py:28-114).  A gap is n consecutive rows of the table `to` that end at a key whose pose T is
+ * row old_row of the table `from`; all n rows receive [R(r6) | t] of the END POINT of the reference's descent: from t = 0, r6 = the
+ * first two columns of I, `iters` plain gradient steps of size lr on mean over the 16 entries of (M^n - T)^2, M = [R(r6) | t; 0 0 0 1],
+ * leaving after the step at which every entry of the float32-rounded M^n is within 1e-9 + 1e-7 |T| of T.
+ *   gaps      device int32[n_gaps][3] = (first_row, n, old_row)
+ *   residual  device float[n_gaps] out: max |M^n - T| over the twelve entries, of the float64 end point
+ *   status    device int32[1] out: 1 when the launch refused the words, else 0
+ * One launch, one wave per gap, the iterations inside the kernel with the parameters in float64 registers; the n rows are the
+ * float32 rounding of the end point, their valid bytes are set, nothing else of `to` is written and `accum` is NOT rebuilt
+ * (egs_pose_accumulate afterwards).  A gap's rows depend on its own word and T only: same bits alone or among other gaps, run to run.
+ * n outside [2, 32], first_row < 0, first_row + n > to->K, old_row outside [0, from->K) in ANY gap: no wave writes a row or a residual
+ * and the call returns EGS_ERR_RANGE -- the words are read on the device by every wave, so the call copies `status` back and
+ * SYNCHRONISES the stream (it cannot be captured; it runs once per stage).  n_gaps > 65535: EGS_ERR_RANGE before any device work.
+ * EGS_ERR_ARG before any device work: a table egs_pose_head would refuse, a NULL argument, n_gaps < 1, iters < 0. */
+int egs_pose_interpolate(const egs_pose_sequence* from, const egs_pose_sequence* to, const int32_t* gaps /*device [n_gaps][3]*/, int n_gaps,
+                         int iters, float lr, float* residual /*device [n_gaps] out*/, int32_t* status /*device [1] out*/, void* stream);
 
 /* The same launch carrying, in extra workgroups, what a rasterizer backward of the same frame needs done before its blend
  * kernel: ordering the tiles by the cost the forward recorded, clearing the gradient accumulator (`scratch`) and, with a sink, the

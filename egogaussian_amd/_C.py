@@ -94,6 +94,8 @@ def binning_passes(P, W, H):
 # set_* helpers the tests use as context managers (tests/common.py) -- Python state of this module, not of the library.
 CALL_SYNC, CALL_KEEP_ALL_INSTANCES, CALL_SEPARATE_COUNT, CALL_SEPARATE_SORT, CALL_BALLOT_RANK = (
     _lib.CALL_SYNC, _lib.CALL_KEEP_ALL_INSTANCES, _lib.CALL_SEPARATE_COUNT, _lib.CALL_SEPARATE_SORT, _lib.CALL_BALLOT_RANK)
+CALL_DETERMINISTIC = _lib.CALL_DETERMINISTIC
+_BACKWARD_FLAGS = CALL_SYNC | CALL_DETERMINISTIC      # the bits of the word a backward acts on
 _env_on = lambda name: os.environ.get(name, "") not in ("", "0")
 default_call_flags = (CALL_SEPARATE_COUNT if _env_on("EGS_NO_FUSED_COUNT") else 0) | (CALL_SEPARATE_SORT if _env_on("EGS_NO_SORT_IN_BLEND") else 0)
 
@@ -131,6 +133,23 @@ def set_fused_count(on):
 def force_ballot_rank(on):
     """Default of calls that do not say: the per-tile sort's ballot-based ranking fallback (test hook).  -> the previous setting."""
     return _set_default(CALL_BALLOT_RANK, bool(on))
+
+
+def deterministic_backward(on):
+    """Default of calls that do not say: the backward blend's order-independent sums (CALL_DETERMINISTIC: gradients are the same bits on
+    every run, for two more launches and a second pass of the blend per backward) on, or the float atomics (the library's default).
+    -> the previous setting."""
+    return _set_default(CALL_DETERMINISTIC, bool(on))
+
+
+def backward_flags(debug=0):
+    """The flags word of a backward: the bits of call_flags(debug) a backward acts on."""
+    return call_flags(debug) & _BACKWARD_FLAGS
+
+
+def backward_scratch_bytes(P, debug=0):
+    """Bytes of scratch a backward of P Gaussians called with this `debug` word works in (egs_backward_scratch_bytes_ex)."""
+    return int(_lib.load().egs_backward_scratch_bytes_ex(int(P), backward_flags(debug)))
 
 
 def forward_fuses_count(P, W, H, debug=0):
@@ -476,7 +495,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     opacity_entropy (extension): an EntropyTerm -- weight * (mean entropy of the visible opacities) is part of the loss: its share joins dL_dopacity
     (and the Adam step of a fused opacity leaf) inside the preprocess backward, and the term's n_vis / value words are written
     (include/egs_raster.h egs_backward_entropy_lossgrad).  Not with object_motion, object_loss or the colours-only mask.
-    scratch (extension): a caller-owned uint8 tensor of egs_backward_scratch_bytes(P) for the call to work in instead of a temporary: it is left
+    debug: the call's EGS_CALL_* word; a backward acts on CALL_SYNC and CALL_DETERMINISTIC (order-independent gradient sums: every result
+    is the same bits on every run; include/egs_raster.h).
+    scratch (extension): a caller-owned uint8 tensor of backward_scratch_bytes(P, debug) for the call to work in instead of a temporary: it is left
     holding the blend's accumulator (inspection, tests: a later call given it as prologue_scratch with R = 0 runs the per-Gaussian launches
     alone, on those very sums)."""
     L = _lib.load()
@@ -557,10 +578,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             else:
                 entry, middle, sink_tail = L.egs_backward, upstream, ()
             # 2. the scratch buffer: the one a loss backward prepared, else the caller's, else a temporary
+            flags = backward_flags(debug)
+            need = int(L.egs_backward_scratch_bytes_ex(P, flags))
             if prologue_scratch is not None:
                 scratch = prologue_scratch
             elif scratch is None:
-                scratch = torch.empty((L.egs_backward_scratch_bytes(P),), device=dev, dtype=torch.uint8)
+                scratch = torch.empty((need,), device=dev, dtype=torch.uint8)
+            if (flags & CALL_DETERMINISTIC) and scratch.numel() * scratch.element_size() < need:
+                raise RuntimeError(f"rasterize_gaussians_backward: scratch of {scratch.numel()} bytes, the call needs {need} "
+                                   "(backward_scratch_bytes(P, debug): CALL_DETERMINISTIC works in more than the default)")
             # 3. the call (lib.py: _BWD_SCENE, _STATE, middle, _GRADS, _STATS, _BWD_TAIL)
             _lib.check(entry(
                 P, int(degree), M, int(R), _ptr(background), _ptr(means3D), _ptr(sh), _ptr(sh_rest), _ptr(colors), _ptr(scales),
@@ -568,7 +594,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(campos), W, H, float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
                 *middle, _ptr(dmeans2D), _ptr(dcolors), _ptr(dopacity), _ptr(dmeans3D_arg), _ptr(dcov3D), _ptr(dsh), _ptr(dsh_rest),
                 _ptr(dscales), _ptr(drots), *_stat_ptrs(densify_stats, P, dev), None if colors_only else _ptr(None if guard is None else guard.overflow),
-                *sink_tail, GRAD_COLORS if colors_only else 0, _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+                *sink_tail, GRAD_COLORS if colors_only else 0, _ptr(scratch), _stream(dev), flags))
             if owned:
                 sink.mark_stepped()
     if colors_only:
@@ -693,14 +719,18 @@ def backward_label(radii, geomBuffer, R, binningBuffer, imageBuffer, H, W, dL_do
     with _hip.device_ctx(dev):
         if want_grad and dlabel is None:
             dlabel = torch.empty((P,), device=dev, dtype=torch.float32)
+        flags = backward_flags(debug)
+        need = int(L.egs_backward_scratch_bytes_ex(P, flags))
         if scratch is None:
-            scratch = torch.empty((max(int(L.egs_backward_scratch_bytes(P)), 16),), device=dev, dtype=torch.uint8)
+            scratch = torch.empty((max(need, 16),), device=dev, dtype=torch.uint8)
+        elif (flags & CALL_DETERMINISTIC) and scratch.numel() * scratch.element_size() < need:
+            raise RuntimeError(f"backward_label: scratch of {scratch.numel()} bytes, the call needs {need} (backward_scratch_bytes(P, debug))")
         g_color = None if dL_dout_color is None else _f32c(dL_dout_color, "dL_dout_color")
         leaf, b1, b2, eps, coef = adam if adam is not None else (None, 0.0, 0.0, 0.0, None)
         _lib.check(L.egs_backward_label(P, int(R), int(W), int(H), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g_color),
                                         None if label_loss is None else C.byref(label_loss), _ptr(dlabel) if want_grad else None,
                                         None if leaf is None else C.byref(leaf), float(b1), float(b2), float(eps), _ptr(coef), _ptr(active_rows),
-                                        _ptr(None if guard is None else guard.overflow), _ptr(scratch), _stream(dev), (call_flags(debug) & CALL_SYNC)))
+                                        _ptr(None if guard is None else guard.overflow), _ptr(scratch), _stream(dev), flags))
     return dlabel if want_grad else None
 
 

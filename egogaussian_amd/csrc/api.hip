@@ -224,6 +224,18 @@ size_t egs_geom_bytes(int P) { return geom_layout(P).bytes; }
 size_t egs_binning_bytes(int P, int64_t R, int width, int height) { return bin_layout(P, R, width, height).bytes; }
 size_t egs_image_bytes(int width, int height) { return img_layout(width, height).bytes; }
 size_t egs_backward_scratch_bytes(int P) { return egs_align(egs_acc_floats((size_t)(P > 0 ? P : 0)) * sizeof(float)); }
+size_t egs_backward_scratch_bytes_ex(int P, int flags) {
+    return egs_backward_scratch_bytes(P) + ((flags & EGS_CALL_DETERMINISTIC) ? egs_det_bytes((size_t)(P > 0 ? P : 0)) : 0);
+}
+// EGS_CALL_DETERMINISTIC: the mode's lines behind the float accumulator, cleared here (the prologue, which the loss launch may have carried, clears
+// the float lines only) -> where they are; NULL without the bit
+static int det_lines_clear(void* scratch, int P, int flags, hipStream_t s, void** lines) {
+    *lines = nullptr;
+    if (!(flags & EGS_CALL_DETERMINISTIC)) return 0;
+    *lines = (char*)scratch + egs_backward_scratch_bytes(P);
+    EGS_TRY(egs_launch_zero_f4((float4*)*lines, egs_det_bytes((size_t)P) / 16, s));
+    return 0;
+}
 
 int egs_get_geom_layout(int P, egs_geom_layout* out) { if (!out || P < 0) return EGS_ERR_ARG; *out = geom_layout(P).o; return 0; }
 int egs_get_binning_layout(int P, int64_t R, int width, int height, egs_binning_layout* out) {
@@ -593,8 +605,9 @@ static int backward_impl(const BackwardCall& c) {
         EgsBinPtrs b = bin_ptrs(const_cast<void*>(c.binning_buffer), P, R, width, height);
         EgsImgPtrs im = img_ptrs(const_cast<void*>(c.image_buffer), width, height);
         if (!c.prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, nullptr, s));
+        void* det = nullptr; rc = det_lines_clear(c.scratch, P, debug, s, &det); if (rc) return rc;
         egs_prof_start(EGS_K_RENDER_BWD, s);
-        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 1, nullptr, s));
+        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 1, nullptr, s, det));
         egs_prof_stop(EGS_K_RENDER_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
         egs_prof_start(EGS_K_PREPROCESS_BWD, s);
@@ -657,8 +670,9 @@ static int backward_impl(const BackwardCall& c) {
     if (R == 0 && lgp) EGS_TRY(egs_launch_loss_finish(lgh, width, height, s));
     if (R > 0) {
         if (!c.prologue_done) EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, sink ? &tick : nullptr, s));
-        egs_prof_start(EGS_K_RENDER_BWD, s);                         // (the stage is the blend kernel alone)
-        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, c.dL_dout_depth, c.dL_dout_alpha, grad_acc, 0, lgp, s));
+        void* det = nullptr; rc = det_lines_clear(c.scratch, P, debug, s, &det); if (rc) return rc;
+        egs_prof_start(EGS_K_RENDER_BWD, s);                         // (the stage is the blend kernel alone; deterministic: its two passes and the decode)
+        EGS_TRY(egs_launch_render_backward(P, width, height, c.background, g, b.point_list, im, dL_dout_color, c.dL_dout_depth, c.dL_dout_alpha, grad_acc, 0, lgp, s, det));
         egs_prof_stop(EGS_K_RENDER_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
     }
@@ -889,10 +903,11 @@ int egs_backward_label(int P, int64_t R, int width, int height, const int32_t* r
     } else {
         EgsBinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), P, R, width, height);
         EGS_TRY(egs_launch_backward_prologue(P, width, height, im, grad_acc, g.block_hot, adam ? &tick : nullptr, s));
+        void* det = nullptr; rc = det_lines_clear(scratch, P, debug, s, &det); if (rc) return rc;
         EgsLabelLossK lk = {}; EgsLossGradHost lgh = {};
         if (loss) { lk = EgsLabelLossK{ loss->img, loss->mask, loss->gate, loss->upstream, loss->partial, inv_hw }; lgh.lab = &lk; }
         egs_prof_start(EGS_K_RENDER_BWD, s);
-        EGS_TRY(egs_launch_render_backward(P, width, height, nullptr, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 2, loss ? &lgh : nullptr, s));
+        EGS_TRY(egs_launch_render_backward(P, width, height, nullptr, g, b.point_list, im, dL_dout_color, nullptr, nullptr, grad_acc, 2, loss ? &lgh : nullptr, s, det));
         egs_prof_stop(EGS_K_RENDER_BWD, s);
         EGS_SYNC_IF_DEBUG(s);
     }

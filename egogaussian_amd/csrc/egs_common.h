@@ -243,7 +243,10 @@ hipError_t egs_launch_loss_finish(const EgsLossGradHost& lg, int W, int H, hipSt
 // lg (may be NULL): the blend computes dL/dcolour itself (k_render_backward<1, true>); dL_dcolor, dL_ddepth, dL_dalpha are then not read
 hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsGeomPtrs g, const uint32_t* point_list,
                                       EgsImgPtrs im, const float* dL_dcolor, const float* dL_ddepth,
-                                      const float* dL_dalpha, float* grad_acc, int colors_only /*2: one scalar colour (k_render_backward<3>)*/, const EgsLossGradHost* lg, hipStream_t s);
+                                      const float* dL_dalpha, float* grad_acc, int colors_only /*2: one scalar colour (k_render_backward<3>)*/, const EgsLossGradHost* lg, hipStream_t s,
+                                      void* det_lines = nullptr /*EGS_CALL_DETERMINISTIC: egs_det_bytes(P) of ZEROS (det_accum.h); the blend runs as two integer passes and a decode*/);
+// The deterministic mode's lines behind the float accumulator in the backward's scratch: uint32[P][12] maxima, then int64[P][12] sums
+static inline size_t egs_det_bytes(size_t P) { return egs_align(P * EGS_GRAD_STRIDE * (sizeof(uint32_t) + sizeof(int64_t))); }
 // colors_only: the blend left only the colour sums (k_render_backward<0>); this turns them into dL/dcolors_precomp [P,3]
 hipError_t egs_launch_colors_from_acc(int P, const float* grad_acc, const uint8_t* clamped, const int32_t* radii, float* dcolors, hipStream_t s);
 // The label step's last launch (label_loss.hip k_label_finish): dL/dlabel[i] = slot 6 of Gaussian i's line (+ its replica lines), 0 when radii[i] <= 0;

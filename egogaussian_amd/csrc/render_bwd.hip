@@ -25,6 +25,7 @@
 #include "blend_instrument.h"      // measurement / ablation hooks: all empty in the product build
 #include "loss_window.h"
 #include "label_bce.h"
+#include "det_accum.h"
 #include <algorithm>
 
 namespace {
@@ -97,7 +98,13 @@ struct EgsLossGrad { const float* img; const float* gt; const float* m0; const f
                      const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
                      EgsObjLossK obj; EgsLabelLossK lab; };      // obj (read by <2, true> only); lab (read by <3, true> only, label_bce.h); obj: the object stages' loss: the alpha plane the forward wrote, the mask, the alpha weights
 #define LG_COLS 27
-template <int MODE, bool LG>
+// DET (EGS_CALL_DETERMINISTIC; det_accum.h): 0 = the float atomics above.  Otherwise the blend runs twice over the same lists, `grad_acc`
+// then points to the mode's lines -- uint32[P][12] maxima, and hot_base words behind them int64[P][12] sums; no replica lines -- and a wave publishes
+//   1: float_bits(|out|) with an integer atomic max (the maximum of non-negative floats' bit patterns does not depend on the order),
+//   2: out / quantum(that maximum) as an integer with a 64-bit atomic add (integer sums associate).
+// The partial `out` of a (quadrant, splat) is the same bits in both passes and in every run: one wave, fixed lanes, a fixed fold order.
+// What a loss-gradient prologue leaves behind besides its gradient (the deferred loss value, added to a running sum) is left once, by pass 1.
+template <int MODE, bool LG, int DET>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_render_backward(
     int W, int H, int gx, int n_tiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float4* __restrict__ rec, const float* __restrict__ bg, const float* __restrict__ final_T,
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     float lg_r = 0.f, lg_g = 0.f, lg_b = 0.f;
     if (LG && MODE != 3) {
         // the loss value the forward deferred: one wave of the launch adds up the per-strip partial sums (loss_window.h), as k_l1_ssim_backward did
-        if (lg.fin_partial && blockIdx.x == 0 && wv == 0) {
+        if (DET != 2 && lg.fin_partial && blockIdx.x == 0 && wv == 0) {
             if (HAS_DA) wave_finish_obj_loss(lg.fin_n, lg.fin_partial, lg.fin_lambda, lg.obj, lg.fin_loss, lg.fin_running, lane);
             else wave_finish_loss(lg.fin_n, lg.fin_partial, lg.w_l1, lg.w_ssim, lg.fin_lambda, lg.fin_loss, lg.fin_running, lane);
         }
@@ -374,6 +381,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             out = dpp_add<0x4E>(out);       // quad_perm [2,3,0,1]
             }
             const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)my_id, j);
+            if (DET != 0) {                                             // (compile-time; the Gaussian's own line whether it is hot or not)
+                (void)hot_mask; (void)hot_slots;
+                if (slot >= 0) {
+                    uint32_t* det_max = reinterpret_cast<uint32_t*>(grad_acc);
+                    const uint32_t word = gid * (uint32_t)EGS_GRAD_STRIDE + (uint32_t)slot;
+                    if (DET == 1) atomicMax(det_max + word, egs_det_abs_bits(out));
+                    else atomicAdd(reinterpret_cast<unsigned long long*>(det_max + hot_base) + word, (unsigned long long)egs_det_encode(out, det_max[word]));
+                }
+                continue;
+            }
             EGS_BWD_ABL7(my[j * 3 + 2])
             uint32_t line = gid * (uint32_t)EGS_GRAD_STRIDE;            // first float of the accumulator line (48 P < 2^32 bytes: P < 89 M)
             if ((hot_mask >> j) & 1ull) {                               // (wave-uniform, rare)
@@ -429,9 +446,18 @@ hipError_t egs_launch_backward_prologue(int P, int W, int H, EgsImgPtrs im, floa
     return hipGetLastError();
 }
 
+// The deterministic mode's third step: the int64 sums of every (Gaussian, slot) as float32 in the accumulator's regular lines -- all twelve slots of
+// all P lines, visited or not (an untouched pair decodes to 0), so the per-Gaussian kernels behind the blend read what they always read.  The float
+// replica lines keep the zeros the prologue gave them.
+namespace {
+__global__ __launch_bounds__(256) void k_det_decode(size_t n, const uint32_t* __restrict__ det_max, const int64_t* __restrict__ det_sum, float* __restrict__ grad_acc) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) grad_acc[i] = egs_det_decode(det_sum[i], det_max[i]);
+}
+}  // namespace
 hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsGeomPtrs g, const uint32_t* point_list,
                                       EgsImgPtrs im, const float* dL_dcolor, const float* dL_ddepth,
-                                      const float* dL_dalpha, float* grad_acc, int colors_only, const EgsLossGradHost* lg, hipStream_t s) {
+                                      const float* dL_dalpha, float* grad_acc, int colors_only, const EgsLossGradHost* lg, hipStream_t s, void* det_lines) {
 #ifdef EGS_LG_CHECK
     if (!lg && egs_debug_lossgrad.img) lg = &egs_debug_lossgrad;      // (experiment hook: egs_debug_set_lossgrad)
 #endif
@@ -444,9 +470,12 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
               lgk.fin_partial = lg->fin_partial; lgk.fin_n = lg->fin_n; lgk.fin_lambda = lg->fin_lambda; lgk.fin_loss = lg->fin_loss; lgk.fin_running = lg->fin_running;
               if (lg->obj) lgk.obj = *lg->obj;
               if (lg->lab) lgk.lab = *lg->lab; }
-#define EGS_BWD_LAUNCH(MODE, LGF) hipLaunchKernelGGL((k_render_backward<MODE, LGF>), dim3(egs_blocks_for_tiles(n_tiles)), dim3(256), 0, s, W, H, gx, n_tiles, \
+#define EGS_BWD_LAUNCH_DET(MODE, LGF, DET, ACC) hipLaunchKernelGGL((k_render_backward<MODE, LGF, DET>), dim3(egs_blocks_for_tiles(n_tiles)), dim3(256), 0, s, W, H, gx, n_tiles, \
                            im.ranges, point_list, g.rec, bg, im.final_T, im.n_contrib, dL_dcolor, dL_ddepth, dL_dalpha, \
-                           im.tile_order, grad_acc, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * EGS_GRAD_STRIDE), (uint32_t)egs_hot_slots((size_t)P), lgk)
+                           im.tile_order, ACC, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * EGS_GRAD_STRIDE), (uint32_t)egs_hot_slots((size_t)P), lgk)
+    // det_lines (EGS_CALL_DETERMINISTIC): the maxima pass, the integer-sum pass, then the lines decoded into the float accumulator
+#define EGS_BWD_LAUNCH(MODE, LGF) do { if (!det_lines) EGS_BWD_LAUNCH_DET(MODE, LGF, 0, grad_acc); else { \
+                           EGS_BWD_LAUNCH_DET(MODE, LGF, 1, (float*)det_lines); EGS_BWD_LAUNCH_DET(MODE, LGF, 2, (float*)det_lines); } } while (0)
     if (colors_only == 2 && lg && lg->lab) EGS_BWD_LAUNCH(3, true);  // scalar colour, the label loss formed by the blend (dL_dcolor is not read)
     else if (colors_only == 2) EGS_BWD_LAUNCH(3, false);             // scalar colour, any loss: the three upstream planes added up
     else if (colors_only) EGS_BWD_LAUNCH(0, false);
@@ -454,6 +483,12 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
     else if (dL_ddepth || dL_dalpha) EGS_BWD_LAUNCH(2, false);
     else if (lg) EGS_BWD_LAUNCH(1, true);
     else EGS_BWD_LAUNCH(1, false);
+    if (det_lines) {
+        const size_t n = (size_t)P * EGS_GRAD_STRIDE;
+        hipLaunchKernelGGL(k_det_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const uint32_t*)det_lines,
+                           (const int64_t*)((const uint32_t*)det_lines + n), grad_acc);
+    }
+#undef EGS_BWD_LAUNCH_DET
 #undef EGS_BWD_LAUNCH
     return hipGetLastError();
 }

@@ -242,8 +242,12 @@ class GraphedTrainStep:
     def __init__(self, pc, optimizer, bg, lambda_dssim=0.2, pipe=Pipe, render_kwargs=None, densify_stats=False, dynamic=False,
                  which_object=1, gated=False, check_every=0, steps_per_replay=1, fuse_optimizer=True, double_buffer=False, loss_grad_in_blend=True,
                  motion=False, object_loss=None, pose=None, label_phase=False, entropy_reg=False, frame_store=None, ring_capacity=4096,
-                 pose_sequence=None):
-        """pose_sequence: (with dynamic=True, motion=True; not with pose=: ValueError) a poses.PoseSequence -- the object stages' pose table on
+                 pose_sequence=None, deterministic=False):
+        """deterministic: every backward of the step -- warm-up and captured -- runs with CALL_DETERMINISTIC (include/egs_raster.h: the backward
+                       blend's sums as integer atomics in two passes): parameters, moments and statistics after N replays from one seeded
+                       start are the same bits in every run.  Goes with every other option; costs a second pass of the backward blend
+                       and two small launches per iteration (profiles/deterministic_backward.md).
+        pose_sequence: (with dynamic=True, motion=True; not with pose=: ValueError) a poses.PoseSequence -- the object stages' pose table on
                        the device.  Every frame carries the word `pose_rows` = (fixed_row, train_row, reload) (pack_frame(pose_rows=),
                        PoseSequence.rows); per iteration the capture holds, in order, egs_pose_head (reads the slot's word, WRITES the
                        slot's accum_T / accum_R -- the buffers the rasterizer reads), the step, whose backward leaves dL/dA12, dL/dM9 in
@@ -320,6 +324,7 @@ class GraphedTrainStep:
                        depend on the model through that one render only -- which is the step this class captures.  Results are
                        bit-identical either way."""
         self.frame_store, self._ring = frame_store, None
+        self.deterministic = bool(deterministic)
         if frame_store is not None:
             if double_buffer:
                 raise ValueError("GraphedTrainStep(frame_store=) does not go with double_buffer: the decode is part of the graph, no copy is left to hide")
@@ -411,6 +416,22 @@ class GraphedTrainStep:
             self._entropy_weight_pushed = self._entropy_weight_host
 
     def _label_body(self, k=0):
+        old = _C.deterministic_backward(True) if self.deterministic else None      # (the bit travels in the calls the body makes; captured, it stays in the graph)
+        try:
+            return self._label_body_(k)
+        finally:
+            if old is not None:
+                _C.deterministic_backward(old)
+
+    def _body(self, k=0):
+        old = _C.deterministic_backward(True) if self.deterministic else None
+        try:
+            return self._body_(k)
+        finally:
+            if old is not None:
+                _C.deterministic_backward(old)
+
+    def _label_body_(self, k=0):
         """One iteration of the label phase on static frame k: no autograd, the library's calls in order."""
         from . import lib as _lib
         from .optim import _touched
@@ -441,7 +462,7 @@ class GraphedTrainStep:
         self._label_keep = (keep, m, v, step, lr_t, coef, geom, binning, img)
         return loss, {"render": color, "radii": radii, "label_grad": dl}
 
-    def _body(self, k=0):
+    def _body_(self, k=0):
         """One training iteration on static frame k."""
         f = self._slots[k]
         kw = dict(self.render_kwargs)

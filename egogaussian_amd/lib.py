@@ -12,6 +12,7 @@ ABI_VERSION = 6
 RETRY_LARGER = -100
 # per-call flags (include/egs_raster.h EGS_CALL_*, ABI 6): bits of the `debug` / `flags` word of the forwards
 CALL_SYNC, CALL_KEEP_ALL_INSTANCES, CALL_SEPARATE_COUNT, CALL_SEPARATE_SORT, CALL_BALLOT_RANK = 1, 2, 4, 8, 16
+CALL_DETERMINISTIC = 0x20      # backwards only: order-independent gradient sums (scratch of egs_backward_scratch_bytes_ex)
 # egs_forward_sort_plan's answer (EGS_SORT_*)
 SORT_IN_BLEND, SORT_SECOND_INSTANTIATION, SORT_BALLOT_RANK = 1, 2, 4
 
@@ -143,6 +144,7 @@ SIGNATURES = {
     "egs_binning_bytes": (C.c_size_t, [i32, i64, i32, i32]),
     "egs_image_bytes": (C.c_size_t, [i32, i32]),
     "egs_backward_scratch_bytes": (C.c_size_t, [i32]),
+    "egs_backward_scratch_bytes_ex": (C.c_size_t, [i32, i32]),
     "egs_order_words": (C.c_int, [i32, i32]),
     "egs_get_geom_layout": (C.c_int, [i32, C.POINTER(GeomLayout)]),
     "egs_get_binning_layout": (C.c_int, [i32, i64, i32, i32, C.POINTER(BinningLayout)]),

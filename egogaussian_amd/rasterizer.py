@@ -242,7 +242,7 @@ def backward_prologue_of(node):
     if P == 0 or node.prologue_scratch is not None:
         return None
     rs = node.raster_settings
-    scratch = torch.empty((_lib.load().egs_backward_scratch_bytes(P),), device=means3D.device, dtype=torch.uint8)
+    scratch = torch.empty((_C.backward_scratch_bytes(P, rs.debug),), device=means3D.device, dtype=torch.uint8)      # (what the node's backward, called with rs.debug, works in)
     side = _lib.BackwardPrologue()
     side.P, side.width, side.height = P, int(rs.image_width), int(rs.image_height)
     side.image_buffer, side.scratch, side.geom_buffer = img.data_ptr(), scratch.data_ptr(), geom.data_ptr()

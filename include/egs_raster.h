@@ -61,7 +61,7 @@ extern "C" {
                                          forward (colour only) */
 #define EGS_TILE 16                 /* tile edge in pixels; part of the parity contract */
 
-/* Per-call flags (ABI 6).  None of them changes an output value: colour, depth, alpha, radii, final transmittance and every gradient are
+/* Per-call flags (ABI 6).  None of them but EGS_CALL_DETERMINISTIC (see there) changes an output value: colour, depth, alpha, radii, final transmittance and every gradient are
  * bit-identical whatever the bits; they select which launches produce them (and, for KEEP_ALL_INSTANCES, what the internal lists hold). */
 #define EGS_CALL_SYNC               0x01   /* synchronise the stream and check for errors after every kernel (debugging) */
 #define EGS_CALL_KEEP_ALL_INSTANCES 0x02   /* no tile culling.  By default an instance (splat, tile) of the reference's 3-sigma rectangle is dropped
@@ -75,6 +75,20 @@ extern "C" {
 #define EGS_CALL_SEPARATE_SORT      0x08   /* the per-tile sort as launch(es) of its own instead of inside the forward blend's launch */
 #define EGS_CALL_BALLOT_RANK        0x10   /* the per-tile sort ranks keys with the ballot-based fallback instead of the LDS atomic whose lane-order
                                               behaviour is verified on the device once per process (test hook: covers the fallback) */
+#define EGS_CALL_DETERMINISTIC      0x20   /* backwards only (added within ABI 6; forwards ignore it): order-independent gradient sums.  By default the
+                                              quadrant-waves of the backward blend add their per-splat partial sums into the Gaussian's accumulator
+                                              line with float atomics, in an order that differs from run to run, so gradients differ in their last
+                                              bits.  With this bit -- honoured by egs_backward, egs_backward_adam, egs_backward_lossgrad,
+                                              egs_backward_object_lossgrad, egs_backward_entropy_lossgrad and egs_backward_label, in every blend mode --
+                                              the blend runs twice: the first pass gathers the largest |partial| of every (Gaussian, value) pair with an
+                                              integer atomic max, the second adds the partials as int64 multiples of a quantum <= 2^-38 of that
+                                              maximum, and the sum becomes a float32 once (csrc/det_accum.h).  Every output of the call -- dL_d*, the
+                                              densification statistics, what a sink steps, dL/dA12, dL/dM9, dL/dlabel -- is then a pure function of
+                                              the call's inputs: the same bits run to run, eager or replayed from a hipGraph.  The ONE flag that
+                                              changes output values: by at most the rounding of the float chain it replaces (N q / 2 + half an ulp
+                                              per pair; the default path's bars hold).  A pair that received an Inf or NaN partial comes back NaN.
+                                              PRECONDITION: `scratch` holds egs_backward_scratch_bytes_ex(P, flags) bytes -- more than
+                                              egs_backward_scratch_bytes(P); also when a loss launch prepared it (egs_backward_prologue.scratch). */
 #define EGS_MAX_SH_DEGREE 3
 
 #define EGS_ERR_ARG        (-1)     /* NULL / inconsistent arguments */
@@ -94,6 +108,9 @@ size_t egs_geom_bytes(int P);
 size_t egs_binning_bytes(int P, int64_t R, int width, int height);
 size_t egs_image_bytes(int width, int height);
 size_t egs_backward_scratch_bytes(int P);
+/* the same for a backward called with `flags` (EGS_CALL_* bits): == egs_backward_scratch_bytes(P) unless EGS_CALL_DETERMINISTIC is among them,
+ * which adds the mode's lines (12 P uint32 maxima + 12 P int64 sums, rounded up to 256 bytes) behind the float accumulator */
+size_t egs_backward_scratch_bytes_ex(int P, int flags);
 /* words of a tile-order array (image layout `tile_order`; second part of the placement buffer, behind 4 words per tile): one per
  * workgroup of a blend launch -- 8 XCD bands of equal slot counts, 0xffffffff = padding workgroup */
 int    egs_order_words(int width, int height);

@@ -184,19 +184,14 @@ class FrameStore:
                              "pass quantize=True to round them to the nearest code")
         return q
 
-    def put(self, i, cam, gt=None, accum_R=None, accum_T=None, gate=None, obj_mask=None, quantize=False, _premasked=False, pose_rows=None):
-        """Stores frame i -- the arguments of graph.pack_frame / pack_label_frame, and frame(i) then equals what those return for them, bit
-        for bit.  cam: a camera, or its packed float32[35] block.  gt: uint8 [3,H,W], or float32 with every value exactly k / 255 in float32
-        (x == round(x * 255) / 255 bit for bit), else ValueError unless quantize=True (then round(clamp(x, 0, 1) * 255), ties to even, is
-        stored).  gate, obj_mask: [H,W] or [1,H,W], exactly 0 or 1, else ValueError.  The layout decides what must be given: everything it
-        has, nothing it lacks.  With object_loss the image is stored pre-multiplied by obj_mask, as pack_frame(obj_mask=) stores gt * obj_mask."""
-        i = _check_indices([i], self.n_frames, "FrameStore.put")[0]
-        lay = self.layout
-        has_mask = lay["object_loss"] or lay["label_phase"]
-        for name, given, wanted in (("gt", gt, not lay["label_phase"]), ("accum_R", accum_R, lay["dynamic"]), ("accum_T", accum_T, lay["motion"]),
-                                    ("gate", gate, lay["gated"]), ("obj_mask", obj_mask, has_mask), ("pose_rows", pose_rows, lay.get("pose_rows", False))):
+    def _check_given(self, who, items):
+        """The layout decides what must be given: everything it has, nothing it lacks.  items: (name, value, wanted) triples."""
+        for name, given, wanted in items:
             if (given is not None) != wanted:
-                raise ValueError(f"FrameStore.put: this store's layout {'needs' if wanted else 'has no'} {name} ({lay})")
+                raise ValueError(f"{who}: this store's layout {'needs' if wanted else 'has no'} {name} ({self.layout})")
+
+    def _small_block(self, cam, accum_R=None, accum_T=None, pose_rows=None):
+        """One frame's row of `small` on the store's device (put() and ingest.FrameIngest.put() write it the same way)."""
         dev = self.device
         block = torch.zeros(self.small_floats, dtype=torch.float32, device=dev)
         rel = lambda n: slice(self.off[n][0] - self.small_begin, self.off[n][1] - self.small_begin)
@@ -211,6 +206,21 @@ class FrameStore:
         if pose_rows is not None:                                       # (fixed_row, train_row[, reload]), or the int32[4] word itself
             word = pose_rows.detach().reshape(-1).to(torch.int32) if torch.is_tensor(pose_rows) else pose_word(pose_rows)
             block[rel("pose_rows")].view(torch.int32).copy_(word)
+        return block
+
+    def put(self, i, cam, gt=None, accum_R=None, accum_T=None, gate=None, obj_mask=None, quantize=False, _premasked=False, pose_rows=None):
+        """Stores frame i -- the arguments of graph.pack_frame / pack_label_frame, and frame(i) then equals what those return for them, bit
+        for bit.  cam: a camera, or its packed float32[35] block.  gt: uint8 [3,H,W], or float32 with every value exactly k / 255 in float32
+        (x == round(x * 255) / 255 bit for bit), else ValueError unless quantize=True (then round(clamp(x, 0, 1) * 255), ties to even, is
+        stored).  gate, obj_mask: [H,W] or [1,H,W], exactly 0 or 1, else ValueError.  The layout decides what must be given: everything it
+        has, nothing it lacks.  With object_loss the image is stored pre-multiplied by obj_mask, as pack_frame(obj_mask=) stores gt * obj_mask."""
+        i = _check_indices([i], self.n_frames, "FrameStore.put")[0]
+        lay = self.layout
+        has_mask = lay["object_loss"] or lay["label_phase"]
+        self._check_given("FrameStore.put", (("gt", gt, not lay["label_phase"]), ("accum_R", accum_R, lay["dynamic"]), ("accum_T", accum_T, lay["motion"]),
+                                             ("gate", gate, lay["gated"]), ("obj_mask", obj_mask, has_mask), ("pose_rows", pose_rows, lay.get("pose_rows", False))))
+        dev = self.device
+        block = self._small_block(cam, accum_R, accum_T, pose_rows)
         planes = {}
         if gate is not None:
             planes["gate"] = _plane(gate, "gate", self.H, self.W, dev)

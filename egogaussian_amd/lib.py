@@ -108,6 +108,7 @@ class LpipsWeights(C.Structure):               # egs_lpips_weights
 
 FRAME_DYNAMIC, FRAME_MOTION, FRAME_GATED, FRAME_OBJECT_LOSS, FRAME_LABEL_PHASE = 1, 2, 4, 8, 16      # EGS_FRAME_*
 FRAME_POSE_ROWS = 32                             # EGS_FRAME_POSE_ROWS
+INGEST_IMAGE, INGEST_HAND_MASK, INGEST_OBJ_MASK = 0, 1, 2      # EGS_INGEST_*
 SINK_MEANS3D, SINK_OPACITY, SINK_SCALES, SINK_ROTATIONS, SINK_SH, SINK_SH_REST = range(6)      # EGS_SINK_*
 
 # ---- the long rasterizer entry points: their parameter lists are runs of the same few segments (include/egs_raster.h) ----------------
@@ -180,6 +181,9 @@ SIGNATURES = {
     "egs_interaction_gate": (C.c_int, [i32, i32, vp, vp, i32, vp, vp]),
     "egs_frame_store_layout": (C.c_int, [i32, i32, i32, C.POINTER(FrameLayout)]),
     "egs_frame_decode": (C.c_int, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "egs_resample_ksize": (C.c_int, [i32, i32]),
+    "egs_resample_tables": (C.c_int, [i32, i32, vp, vp]),
+    "egs_frame_ingest": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "egs_pose_head": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp]),
     "egs_pose_tail": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp, vp]),
     "egs_pose_accumulate": (C.c_int, [C.POINTER(PoseSequence), vp]),

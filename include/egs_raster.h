@@ -647,6 +647,54 @@ int egs_frame_decode(int height, int width, int flags, int n_frames, int n_rows,
  * small_floats is then 64. */
 #define EGS_FRAME_POSE_ROWS   32
 
+/* ---- frame ingest: the producer of the 8-bit frame store (added within ABI 6: new entries only).
+ *      The reference resizes every image, hand mask and object mask with PIL.Image.resize (default filter: bicubic, antialiased, on 8-bit
+ *      data), divides by 255 and collapses the masks to {0, 1} (utils/camera_utils.py:21-94, utils/general_utils.py:22-60).  These entries
+ *      take the source-resolution 8-bit arrays and leave in a store's rows the bits that path followed by a put() would leave there.
+ *
+ *      The resize of modes L and RGB (Pillow, Resample.c): a horizontal pass when the width changes, then a vertical pass when the height
+ *      changes; the intermediate is 8-bit, rounded and clamped like the output; a pass whose size does not change is skipped.  One axis,
+ *      in -> out, in C double, in this order of evaluation:
+ *          scale = in / out;  filterscale = max(scale, 1.0);  support = 2.0 * filterscale;  ksize = (int)ceil(support) * 2 + 1
+ *          per output xx:  center = (xx + 0.5) * scale;  ss = 1.0 / filterscale
+ *                          xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), in) - xmin
+ *                          w[x] = bicubic((x + xmin - center + 0.5) * ss), x < xmax;  ww = their sum in index order;  w[x] /= ww when ww != 0
+ *                          kk[x] = (int)(w < 0 ? -0.5 + w * 2^22 : 0.5 + w * 2^22), 0 for xmax <= x < ksize
+ *          bicubic(x), a = -0.5, x = |x|:  x < 1: ((a + 2) x - (a + 3)) x x + 1;  x < 2: (((x - 5) x + 8) x - 4) a;  else 0
+ *      A pixel of a pass: clamp((2^21 + sum in[xmin + x] * kk[x]) >> 22, 0, 255), int32, arithmetic shift.
+ *      A mask is "any channel > 0" of the resized bytes; the hand mask enters the store as the gate 1 - hand_mask; with OBJECT_LOSS the
+ *      image bytes are stored multiplied by the object plane.
+ *
+ *      egs_resample_ksize   ksize of in -> out; 0 when in or out < 1.
+ *      egs_resample_tables  HOST arithmetic, no device: kk[out][ksize] and bounds[out] = {xmin, xmax} as above.  in or out < 1 or a NULL
+ *                           pointer: EGS_ERR_ARG.
+ *      egs_frame_ingest     resizes ONE source array, src = device uint8 [src_h][src_w][src_c] (interleaved), to width x height and writes
+ *                           frame `frame` of a store of the layout `flags` (img, bits: the store's arrays, egs_frame_store_layout):
+ *                             EGS_INGEST_IMAGE     src_c = 3: img[frame] as CHW bytes (the padding up to image_stride is not written);
+ *                                                  with OBJECT_LOSS each byte times the bit of the frame's obj_mask plane, which the
+ *                                                  launch READS: ingest the object mask of a frame before its image
+ *                             EGS_INGEST_HAND_MASK src_c = 1 or 3: the gate plane, bit = no channel > 0
+ *                             EGS_INGEST_OBJ_MASK  src_c = 1 or 3: the obj_mask plane, bit = any channel > 0
+ *                           Both passes run in one launch: the horizontal result of an output tile lies in LDS as bytes (at most 41 KB per
+ *                           workgroup), nothing intermediate in device memory.  A plane's words of the frame are cleared by a memset node
+ *                           on `stream` and the tiles OR their bits in: any width, the same words whatever the order.  kk_h, bounds_h: the
+ *                           device copies of egs_resample_tables(src_w, width), kk_v, bounds_v: of (src_h, height); those of an axis that
+ *                           does not change are not read and may be NULL.  The kernel clamps what it reads from them into the source.
+ *                           No allocation, no global state, no synchronisation; can be captured.
+ *                           EGS_ERR_ARG before any device work: height, width, n_frames, src_h or src_w < 1, frame outside [0, n_frames),
+ *                           unknown flag bits or plane, src_c not 3 (image) / 1 or 3 (masks), a NULL src, a NULL img / bits where the
+ *                           plane needs it, a NULL table of an axis that changes.  EGS_ERR_MODE: a layout that has no such plane (or is
+ *                           refused by egs_frame_store_layout).  EGS_ERR_RANGE: a side of the source or the target > 32767, or
+ *                           src_w > 8 width or src_h > 8 height (ksize <= 33 bounds the tile in LDS). */
+#define EGS_INGEST_IMAGE      0
+#define EGS_INGEST_HAND_MASK  1
+#define EGS_INGEST_OBJ_MASK   2
+int egs_resample_ksize(int in, int out);
+int egs_resample_tables(int in, int out, int32_t* kk /*HOST out [out][ksize]*/, int32_t* bounds /*HOST out [out][2]*/);
+int egs_frame_ingest(int height, int width, int flags, int n_frames, int frame, int plane, uint8_t* img, uint32_t* bits,
+                     const uint8_t* src, int src_h, int src_w, int src_c, const int32_t* kk_h, const int32_t* bounds_h,
+                     const int32_t* kk_v, const int32_t* bounds_v, void* stream);
+
 /* ---- the object pose sequence on the device (added within ABI 6: new entries only).
  *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the
  *      frame's key and rebuild the accumulated sequence (/root/reference/trainers/fine_obj.py:97-126,216-224,

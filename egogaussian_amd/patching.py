@@ -59,14 +59,16 @@ def make_loss_functions(orig_l1=None, orig_ssim=None):
     they do not cover goes to `orig_*` (default: this package's PyTorch mirrors, losses.py)."""
     from . import fused, losses
     orig_l1 = orig_l1 or losses.l1_loss
-    orig_ssim = orig_ssim or (lambda a, b, window_size=11, size_average=True: losses.ssim(a, b))
+    orig_ssim = orig_ssim or losses.ssim
 
     # The trainers call l1_loss(x, gt) and ssim(x, gt) on the SAME pair one after the other (train_static.py:92-95): the first call runs
     # the fused kernel once for both values, the second takes its half -- and one backward launch serves both (fused.l1_and_ssim).
     pending = {}
 
     def _pair(a, b, want):
-        key = (id(a), a._version, b.data_ptr(), b._version)
+        # (the grad mode is part of the key: a half computed under torch.no_grad() has no grad_fn, and handed to a call that records it would
+        # drop that term from loss.backward() without a word)
+        key = (id(a), a._version, b.data_ptr(), b._version, torch.is_grad_enabled())
         hit = pending.pop("pair", None)
         if hit is not None and hit[0] == key and hit[1] is a and hit[2] != want:
             return hit[3]

@@ -1,5 +1,5 @@
 """Float64 anchors for the three streaming kernels most of the suite compares with bit for bit: the Adam step (adam.hip), the covariance
-producer (cov3d.hip) and the image loss (loss.hip).  Input builders, float64 references, float32 CPU yardsticks and the checks themselves;
+producer (cov3d.hip) and the image loss (loss.hip; its two-value form, fused.l1_and_ssim, in the last section).  Input builders, float64 references, float32 CPU yardsticks and the checks themselves;
 the GPU tests (tests/test_gpu_anchor_*.py) hand the kernels' outputs to these checks, tests/test_anchors_cpu.py hands them the yardsticks
 and deliberately wrong variants.  No bar in here comes from a kernel's own output: each is derived where it is defined, taken from
 tests/common.py, or a multiple of what the float32 CPU formulation of the same operation is away from float64 on the same inputs."""
@@ -407,23 +407,18 @@ def loss_zones(H, W):
     return seam | np.zeros((H, W), bool), border | np.zeros((H, W), bool)
 
 
-def check_loss(value, grad, ref64, ref32, gate=None, what="", factors=None):
-    """value: |l - l64| <= 2e-6 max(1, |l64|).  Gradient per pixel e = |g - g64| / max|g64|: max e <= 1e-4; max e and q99 e <= 3 x the float32
-    yardstick's; gated pixels exactly zero.  factors: {'max' | 'q99': factor} replaces the 3 of one statistic (a recorded finding only).
-    -> figures, the maxima on the strip seams and on the border among them."""
-    l64, g64 = ref64
-    l32, g32 = ref32
+def _loss_grad_rule(grad, g64, g32, gate=None, factors=None):
+    """The gradient rule of check_loss (and of check_pair): per pixel e = |g - g64| / max|g64|; max e <= 1e-4; max e and q99 e <= 3 x the float32
+    yardstick's; gated pixels exactly zero.  -> (figures, what failed, e)."""
     g = np.asarray(grad, np.float64)
     scale = float(np.abs(g64).max())
     e, e_y = np.abs(g - g64) / scale, np.abs(g32 - g64) / scale
     seam, border = loss_zones(*g.shape[1:])
     zone = lambda a, m: float(a[:, m].max()) if m.any() else 0.0
-    fig = dict(value=abs(value - l64), value_yard=abs(l32 - l64), max=(float(e.max()), float(e_y.max())),
+    fig = dict(max=(float(e.max()), float(e_y.max())),
                q99=(float(np.quantile(e, 0.99)), float(np.quantile(e_y, 0.99))), seam=(zone(e, seam), zone(e_y, seam)), border=(zone(e, border), zone(e_y, border)),
                interior=(zone(e, ~(seam | border)), zone(e_y, ~(seam | border))))
     fails = []
-    if not abs(value - l64) <= LOSS_VALUE_BAR * max(1.0, abs(l64)):
-        fails.append(f"value {value!r} vs float64 {l64!r}")
     if gate is not None and np.any(g[:, np.asarray(gate) == 0] != 0):
         fails.append("a gated pixel has a non-zero gradient")
     if not e.max() <= LOSS_GRAD_BAR:
@@ -433,6 +428,19 @@ def check_loss(value, grad, ref64, ref32, gate=None, what="", factors=None):
         f = (factors or {}).get(stat, LOSS_FACTOR)
         if not fig[stat][0] <= f * fig[stat][1]:
             fails.append(f"{stat} e {fig[stat][0]:.3e} > {f:g} x the float32 form's {fig[stat][1]:.3e}; seams {fig['seam']}, border {fig['border']}, interior {fig['interior']}")
+    return fig, fails, e
+
+
+def check_loss(value, grad, ref64, ref32, gate=None, what="", factors=None):
+    """value: |l - l64| <= 2e-6 max(1, |l64|).  Gradient per pixel e = |g - g64| / max|g64|: max e <= 1e-4; max e and q99 e <= 3 x the float32
+    yardstick's; gated pixels exactly zero.  factors: {'max' | 'q99': factor} replaces the 3 of one statistic (a recorded finding only).
+    -> figures, the maxima on the strip seams and on the border among them."""
+    l64, g64 = ref64
+    l32, g32 = ref32
+    fig, fails, _ = _loss_grad_rule(grad, g64, g32, gate, factors)
+    fig = dict(value=abs(value - l64), value_yard=abs(l32 - l64), **fig)
+    if not abs(value - l64) <= LOSS_VALUE_BAR * max(1.0, abs(l64)):
+        fails.insert(0, f"value {value!r} vs float64 {l64!r}")
     assert not fails, f"{what}: " + "; ".join(fails)
     return fig
 
@@ -476,3 +484,92 @@ def loss_numpy64(img, gt, lam, gate=None, drop=None):
     if gate is not None:
         grad = grad * np.asarray(gate, np.float64)[None]
     return float(value), grad
+
+
+# ============================================================ two-value loss ============================================================
+# (mean|x - y|, mean SSIM) as a pair with an upstream scalar each: fused.l1_and_ssim, what the trainers' l1_loss() and ssim() become
+PAIR_UPSTREAMS = ((0.8, -0.2), (-0.37, 2.5), (0.0, 1.0), (1.0, 0.0), (2.5, 0.0))      # the first: what (1 - l) l1 + l (1 - ssim) sends down
+PAIR_TIE_ROWS, PAIR_TIE_COLS = slice(6, 10), slice(7, 13)
+PAIR_L1_ONLY_BAR = 2.0 ** -22      # SSIM switched off: u0 sign(x - y) / n by two float32 roundings (1 / n, the product), see check_pair
+
+
+def pair_tie_mask(C, H, W):
+    """bool[C,H,W]: the block where pair_inputs makes the image EQUAL to the ground truth (none below the 11-tap window: at (1, 1, 1) a tie
+    leaves a float64 gradient of ~1e-15 or exactly 0, and an error relative to it means nothing)."""
+    m = np.zeros((C, H, W), bool)
+    if H >= 11 and W >= 11:
+        m[:, PAIR_TIE_ROWS, PAIR_TIE_COLS] = True
+    return m
+
+
+def pair_inputs(C, H, W, seed=0):
+    """loss_inputs with a block of exact ties (background pixels the render reproduces): there sign(x - y) = 0 and only SSIM has a gradient."""
+    img, gt, gate = loss_inputs(C, H, W, seed)
+    tie = torch.from_numpy(pair_tie_mask(C, H, W))
+    return torch.where(tie, gt, img), gt, gate
+
+
+PAIR_FAULTS = ("upstreams_swapped", "ssim_sign_flipped", "ssim_upstream_one", "tie_sign_plus_one")
+
+
+def pair_reference(img, gt, u, dtype, gate=None, fault=None):
+    """losses.l1_loss and losses.ssim on the CPU in `dtype` and the gradient of u[0] l1 + u[1] ssim through autograd -> (l1, ssim, gradient
+    [C,H,W] float64 numpy, gated when a gate is given).  The upstream scalars are taken as float32 carries them (f32w): they reach the kernel
+    as float32 device scalars, so that is the operation it is asked for.  fault: one of PAIR_FAULTS -- deliberately wrong gradients."""
+    from egogaussian_amd.losses import l1_loss, ssim
+    u0, u1 = f32w(u[0]), f32w(u[1])
+    if fault == "upstreams_swapped":
+        u0, u1 = u1, u0
+    elif fault == "ssim_sign_flipped":
+        u1 = -u1
+    elif fault == "ssim_upstream_one":
+        u1 = 1.0
+    x, y = img.detach().clone().to(dtype).requires_grad_(True), gt.to(dtype)
+    l1v, ssv = l1_loss(x, y), ssim(x, y)
+    (u0 * l1v + u1 * ssv).backward()
+    g = x.grad
+    if fault == "tie_sign_plus_one":
+        g = g + (u0 / x.numel()) * (x.detach() == y).to(dtype)
+    if gate is not None:
+        g = g * gate.to(dtype)[None]
+    g = g.double().numpy()
+    assert np.abs(g).max() > 0
+    return float(l1v.detach()), float(ssv.detach()), g
+
+
+def check_pair(values, grad, ref64, ref32, u, gate=None, what=""):
+    """values = (l1, ssim), each |v - v64| <= 2e-6 max(1, |v64|); gated pixels exactly zero; every element finite.  The gradient,
+    u[1] != 0: check_loss's rule (_loss_grad_rule), and the tie block (pair_tie_mask: no L1 term there) once more on its own, max e <= 1e-4.
+    u[1] == 0 (SSIM switched off): the float32 yardstick is 2e-9 .. 5e-8 there and a multiple of it would be a bar on luck; the definition
+    gives one instead.  The float64 gradient is u0 sign(x - y) / n, zero exactly on ties (and under the gate): there the subject must be
+    zero (either sign); elsewhere |g - g64| <= 2^-22 |g64| -- float32 reaches it by two roundings, of 1 / n and of the product with u0
+    (2^-23 together; the sign and the switched-off SSIM term add none).  -> figures as check_loss's, 'tie' and 'l1_only' among them."""
+    l1_64, ss_64, g64 = ref64
+    l1_32, ss_32, g32 = ref32
+    g = np.asarray(grad, np.float64)
+    fig = dict(values=(abs(values[0] - l1_64), abs(values[1] - ss_64)), values_yard=(abs(l1_32 - l1_64), abs(ss_32 - ss_64)))
+    fails = [f"{name} {v!r} vs float64 {v64!r}" for name, v, v64 in (("l1", values[0], l1_64), ("ssim", values[1], ss_64))
+             if not abs(v - v64) <= LOSS_VALUE_BAR * max(1.0, abs(v64))]
+    if not np.isfinite(g).all():
+        fails.append(f"{int((~np.isfinite(g)).sum())} elements are not finite")
+    tie = pair_tie_mask(*g.shape)
+    if u[1] != 0:
+        gfig, gfails, e = _loss_grad_rule(g, g64, g32, gate)
+        scale = float(np.abs(g64).max())
+        fig.update(gfig, tie=((float(e[tie].max()), float((np.abs(g32 - g64) / scale)[tie].max())) if tie.any() else (0.0, 0.0)))
+        fails += gfails
+        if not fig["tie"][0] <= LOSS_GRAD_BAR:
+            fails.append(f"tie block (no L1 term): max e {fig['tie'][0]:.3e} > {LOSS_GRAD_BAR:g}")
+    else:
+        if gate is not None and np.any(g[:, np.asarray(gate) == 0] != 0):
+            fails.append("a gated pixel has a non-zero gradient")
+        zero = g64 == 0
+        assert zero[tie].all(), "the float64 gradient of the L1 term alone is not zero on a tie"
+        if np.any(g[zero] != 0):
+            fails.append(f"{int((g[zero] != 0).sum())} elements are not zero where x == y (or under the gate)")
+        rel = np.abs(g - g64)[~zero] / np.abs(g64)[~zero]
+        fig["l1_only"] = (float(rel.max()), float((np.abs(g32 - g64)[~zero] / np.abs(g64)[~zero]).max()))
+        if not rel.max() <= PAIR_L1_ONLY_BAR:
+            fails.append(f"u0 sign(x - y) / n: {int((rel > PAIR_L1_ONLY_BAR).sum())} elements over 2^-22 of their float64 value (worst {rel.max() / U:.2f} u)")
+    assert not fails, f"{what}: " + "; ".join(fails)
+    return fig

@@ -134,6 +134,25 @@ def test_argument_errors_precede_device_work():
     assert L.egs_mark_visible(5, none, none, none, none, none) == -1
 
 
+def test_pair_loss_argument_errors_precede_device_work():
+    """egs_l1_ssim_pair_forward / _backward: every case returns from an argument check (api.hip, loss.hip: read there) before any launch; the
+    fake non-null pointers are never dereferenced."""
+    from egogaussian_amd import lib
+    L = lib.load()
+    p, none = C.c_void_p(4096), None
+    fwd = lambda c=3, h=16, w=55, img=p, gt=p, partial=p, m0=p, m1=p, m2=p, l1=p, ss=p: L.egs_l1_ssim_pair_forward(c, h, w, img, gt, partial, m0, m1, m2, l1, ss, none)
+    assert fwd(l1=none) == -1 and fwd(ss=none) == -1
+    assert fwd(c=0) == -1 and fwd(h=0) == -1 and fwd(w=0) == -1 and fwd(c=-3) == -1 and fwd(h=-16) == -1 and fwd(w=-55) == -1
+    assert fwd(m0=none) == -1 and fwd(m1=none) == -1 and fwd(m2=none) == -1
+    assert fwd(img=none) == -1 and fwd(gt=none) == -1 and fwd(partial=none) == -1
+    bwd = lambda c=3, h=16, w=55, img=p, gt=p, u1=p, u2=p, gate=none, m0=p, m1=p, m2=p, dimg=p: L.egs_l1_ssim_pair_backward(c, h, w, img, gt, u1, u2, gate, m0, m1, m2,
+                                                                                                                       dimg, none, none)
+    assert bwd(u1=none) == -1 and bwd(u2=none) == -1
+    assert bwd(c=0) == -1 and bwd(h=0) == -1 and bwd(w=0) == -1 and bwd(c=-3) == -1 and bwd(h=-16) == -1 and bwd(w=-55) == -1
+    assert bwd(m0=none) == -1 and bwd(m1=none) == -1 and bwd(m2=none) == -1 and bwd(dimg=none) == -1 and bwd(img=none) == -1 and bwd(gt=none) == -1
+    assert bwd(gate=p, u2=none) == -1                                   # (the gate is optional: it changes no check)
+
+
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "size_t": C.c_size_t}
 # pointers the binding types exactly: strings, and the HOST words a call writes (non-const: the caller passes byref); a pointer to a struct
 # lib.py mirrors (egs_foo_bar -> lib.FooBar) is POINTER(that); every other pointer, the const HOST arrays included, is c_void_p

@@ -147,3 +147,62 @@ def test_loss_zones():
     assert border[:5].all() and border[:, :5].all() and border[-5:].all() and border[:, -5:].all() and not border[5:-5, 5:-5].any()
     seam, border = A.loss_zones(1, 1)
     assert not seam.any() and border.all()
+
+
+# ---- two-value loss ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _pair(shape, u, dtype, gated=False, fault=None):
+    img, gt, gate = A.pair_inputs(*shape)
+    return A.pair_reference(img, gt, u, dtype, gate if gated else None, fault)
+
+
+@pytest.mark.parametrize("C,H,W", A.LOSS_SHAPES)
+def test_pair_float32_form_passes_the_pair_check(C, H, W):
+    """The float32 CPU form is its own yardstick in the mixed rule (factor 1 <= 3); what this shows is that it meets the fixed bars -- 1e-4, and
+    with SSIM switched off 2^-22 of each element and exact zeros on the ties -- with and without the gate."""
+    gate = A.pair_inputs(C, H, W)[2].numpy()
+    for u in A.PAIR_UPSTREAMS:
+        for gated in (False, True):
+            ref64, ref32 = _pair((C, H, W), u, torch.float64, gated), _pair((C, H, W), u, torch.float32, gated)
+            fig = A.check_pair(ref32[:2], ref32[2], ref64, ref32, u, gate if gated else None, what=f"{(C, H, W)} u {u} gate {gated}")
+            if u[1] != 0:
+                print(f"{(C, H, W)} u {u} gate {gated}: float32 torch form values {fig['values_yard'][0]:.1e} {fig['values_yard'][1]:.1e}, gradient max {fig['max'][1]:.2e}, "
+                      f"q99 {fig['q99'][1]:.2e}, seams {fig['seam'][1]:.2e}, border {fig['border'][1]:.2e}, ties {fig['tie'][1]:.2e}")
+            else:
+                print(f"{(C, H, W)} u {u} gate {gated}: float32 torch form, L1 term alone: {fig['l1_only'][1] / A.U:.2f} u of each element")
+
+
+def test_pair_inputs_hold_the_tie_block():
+    for C, H, W in A.LOSS_SHAPES:
+        img, gt, _ = A.pair_inputs(C, H, W)
+        tie = (img == gt).numpy()
+        assert np.array_equal(tie, A.pair_tie_mask(C, H, W)) and bool(tie.any()) == (H >= 11 and W >= 11)      # (11 x 11 clips the block to 4 x 4)
+
+
+def _fault_applies(fault, shape, u):
+    """Whether the wrong form changes the float64 gradient at all -- found by evaluating it in float64."""
+    return not np.array_equal(_pair(shape, u, torch.float64, False, fault)[2], _pair(shape, u, torch.float64)[2])
+
+
+@pytest.mark.parametrize("fault", A.PAIR_FAULTS)
+def test_pair_check_rejects_a_wrong_pair_gradient(fault):
+    """Each wrong float32 form is refused at every shape and upstream pair at which the same wrong form, in float64, differs from the right
+    float64 gradient.  That set is DERIVED (_fault_applies); what it has to come out as is stated here and compared: swapped upstreams change
+    every pair of PAIR_UPSTREAMS (none has u0 == u1); a flipped SSIM sign those with u1 != 0; an SSIM upstream taken as 1 those with
+    u1 != 1; sign(0) = +1 those with u0 != 0, at the shapes that have ties."""
+    expected = {"upstreams_swapped": lambda s, u: u[0] != u[1], "ssim_sign_flipped": lambda s, u: u[1] != 0, "ssim_upstream_one": lambda s, u: u[1] != 1,
+                "tie_sign_plus_one": lambda s, u: u[0] != 0 and s[1] >= 11 and s[2] >= 11}[fault]
+    rejected = 0
+    for shape in A.LOSS_SHAPES:
+        for u in A.PAIR_UPSTREAMS:
+            applies = _fault_applies(fault, shape, u)
+            assert applies == expected(shape, u), (fault, shape, u)
+            if not applies:
+                continue
+            ref64, ref32, wrong = _pair(shape, u, torch.float64), _pair(shape, u, torch.float32), _pair(shape, u, torch.float32, False, fault)
+            with pytest.raises(AssertionError):
+                A.check_pair(wrong[:2], wrong[2], ref64, ref32, u, what=f"{fault} {shape} {u}")
+            d = np.abs(wrong[2] - ref64[2]).max() / np.abs(ref64[2]).max()
+            print(f"{fault} {shape} u {u}: {d:.2e} of max|g64| away")
+            rejected += 1
+    assert rejected > 0

@@ -14,6 +14,13 @@
 
 namespace {
 
+// The mean of the sorted triple.  A point with fewer than three neighbours (fewer than four finite points in the cloud) still has
+// an empty slot: its answer is +inf.  With two or three empty slots the sum overflows to that by itself; with one it would not
+// ((d0 + d1) + FLT_MAX = FLT_MAX, a finite FLT_MAX / 3 that reads like a distance), so the empty slot is tested.
+__device__ __forceinline__ float knn_mean3(float b0, float b1, float b2) {
+    return b2 < FLT_MAX ? (b0 + b1 + b2) / 3.0f : INFINITY;
+}
+
 __global__ __launch_bounds__(256) void k_knn3_mean_dist2(int N, const float* __restrict__ pts, float* __restrict__ out) {
     __shared__ float4 tile[KNN_TILE];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -41,7 +48,7 @@ __global__ __launch_bounds__(256) void k_knn3_mean_dist2(int N, const float* __r
             b0 = fminf(b0, d); b1 = n1; b2 = n2;
         }
     }
-    if (have) out[i] = (b0 + b1 + b2) / 3.0f;
+    if (have) out[i] = knn_mean3(b0, b1, b2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(256) void k_knn_query(int N, const float* __restric
         const float reach = ((float)r - 1e-3f) * g.cell;
         if ((r >= 1 && b2 <= reach * reach) || r >= rmax) break;
     }
-    out[self] = (b0 + b1 + b2) / 3.0f;
+    out[self] = knn_mean3(b0, b1, b2);
 }
 
 __global__ __launch_bounds__(256) void k_knn_nonfinite(int N, const uint32_t* __restrict__ cell_of_point, float* __restrict__ out) {

@@ -1014,7 +1014,8 @@ int egs_split_children(int64_t rows, const int32_t* src_index, const uint8_t* ki
 
 /* ---- f-2: mean squared distance of every point to its 3 nearest neighbours (self excluded by index).
  *      Replaces simple_knn._C.distCUDA2 (un-vendored submodule, /root/reference/.gitmodules:4-6), imported at
- *      /root/reference/scene/gaussian_model.py:21 and called at :301.  Exact (all pairs). */
+ *      /root/reference/scene/gaussian_model.py:21 and called at :301.  Exact (all pairs).  A point with fewer than three
+ *      neighbours (a cloud of fewer than four finite points) gets +inf, in this call and in the grid search. */
 int egs_knn3_mean_dist2(int N, const float* points /*[N,3]*/, float* mean_dist2 /*[N] out*/, void* stream);
 /* The same statistic, bit for bit, through a uniform-grid search (counting sort of the points by cell, then rings of cells around
  * every query until the third neighbour is provably inside): O(N) for clouds of roughly even density instead of O(N^2) -- the

@@ -127,6 +127,7 @@ CASES = [
     (2000, 50, 37, 4, 2, "sh_sr", 3.0),
     (2000, 64, 80, 5, 0, "col_cov", 3.0),
     (20000, 270, 480, 6, 0, "sh_cov", 2.0),
+    (2000, 50, 37, 7, 1, "sh_sr", 3.0),        # SH degree 1: M = 4 under the per-row check
 ]
 
 

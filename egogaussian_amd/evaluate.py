@@ -121,7 +121,7 @@ class EvalPass(CapturedSweep):
     def _bytes(self, res):
         return res["q_image"]
 
-    def run(self, frames, cam, capacity=None, capacity_margin=1.25):
+    def run(self, frames, cam, capacity=None, capacity_margin=1.25, save_renders=None):
         """frames: packed frames of graph.pack_frame(cam, gt, accum_R=, gate=keep, accum_T=) -- a list or an [F, frame] tensor; `gate` is
         keep = 1 - hand mask (frames packed without it keep every pixel) --, or a frames.FrameStore of that layout: every frame of it, each
         brought into the static buffers by one decode launch (from a ring set to 0 .. F - 1 before the sweep) instead of a copy.  cam: any camera of the sweep: the image size and field of view
@@ -129,7 +129,11 @@ class EvalPass(CapturedSweep):
         capacity_margin x the first frame's count; frames that outgrow it are rendered again eagerly).
         -> dict(psnr, ssim: float64[F]; sse: int64[F]; mean_psnr, mean_ssim: the plain means; rerendered: indices of the frames rendered
         again; instances: int64[F], the captured forwards' instance counts (0 for eager frames)[; images: uint8[F,3,H,W] on the device]
-        [; lpips: float64[F], lpips_taps: float64[F,5], mean_lpips -- with lpips=])."""
+        [; lpips: float64[F], lpips_taps: float64[F,5], mean_lpips -- with lpips=]).
+        save_renders: F file names -- after the sweep the quantised renders are encoded on the device and written as 8-bit PNG files
+        (png.PngWriter; needs keep_images=True; the result then also carries png_bytes, the file sizes).  The captured body is the same."""
+        if save_renders is not None and not self.keep_images:
+            raise ValueError("EvalPass.run(save_renders=) writes the quantised renders: construct the pass with keep_images=True")
         if self.lpips is not None and self.graph is not None:
             for t in self._partner(self._rows):                                # the captured rows' partner starts again at row 0, as they do
                 t.zero_()
@@ -138,6 +142,10 @@ class EvalPass(CapturedSweep):
                    rerendered=again, instances=fig["instances"])
         if images is not None:
             out["images"] = images
+        if save_renders is not None:
+            from .png import PngWriter
+            F, C, H, W = images.shape
+            out["png_bytes"] = PngWriter(H, W, C, images.device, batch=min(F, 32)).save(images, save_renders)
         if self.lpips is not None:
             out.update(lpips=fig["lpips"], lpips_taps=fig["lpips_taps"], mean_lpips=float(np.mean(fig["lpips"])))
         return out

@@ -321,6 +321,34 @@ class FrameStore:
                                           p(ring.ring), ring.capacity, p(ring.ctl), p(self.status), p(out), _hip.stream_of(dev)))
         return out
 
+    def png(self, indices, what="gt"):
+        """The stored image bytes of frames `indices` as PNG files, encoded where they lie (png.encode / include/egs_raster.h egs_png_encode):
+        the bytes are planar uint8 already, the strides are the store's.  -> (buf uint8 [K, bound], sizes int32 [K]) on the store's device;
+        buf[k, :sizes[k]] is the file of frame indices[k] (for an object_loss store: of the image times its object mask, what is stored).
+        A run of consecutive indices is one call.  HIP stores only; nothing is read back."""
+        from . import png as _png
+        if what != "gt":
+            raise ValueError(f"FrameStore.png: what = 'gt' (the image bytes); masks are bit planes here, got {what!r}")
+        if self.img is None:
+            raise ValueError(f"FrameStore.png: this store's layout has no image ({self.layout})")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"FrameStore.png: the store is on {self.device}: the PNG encoder has no CPU path (png.encode_statement is the host statement)")
+        idx = _check_indices([indices] if isinstance(indices, int) else indices, self.n_frames, "FrameStore.png")
+        if not idx:
+            raise ValueError("FrameStore.png: no frames")
+        K, run = len(idx), 1
+        buf = torch.empty((K, _png.bound(self.W, self.H, 3)), dtype=torch.uint8, device=self.device)
+        sizes = torch.empty(K, dtype=torch.int32, device=self.device)
+        scratch = torch.empty(_png.scratch_bytes(K, self.W, self.H, 3), dtype=torch.uint8, device=self.device)
+        for k in range(0, K, 1):
+            if k + 1 < K and idx[k + 1] == idx[k] + 1:
+                run += 1
+                continue
+            k0 = k + 1 - run
+            _png._launch(run, self.W, self.H, 3, self.img[idx[k0]].data_ptr(), self.image_stride, self.n_pix, buf[k0:], sizes[k0:], scratch, self.device)
+            run = 1
+        return buf, sizes
+
     def ok(self):
         """True while the kernel never had to clamp a frame index (reads the status word: synchronises)."""
         return int(self.status.item()) == 0

@@ -184,6 +184,9 @@ SIGNATURES = {
     "egs_resample_ksize": (C.c_int, [i32, i32]),
     "egs_resample_tables": (C.c_int, [i32, i32, vp, vp]),
     "egs_frame_ingest": (C.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "egs_png_bound": (C.c_size_t, [i32, i32, i32]),
+    "egs_png_scratch_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+    "egs_png_encode": (C.c_int, [i32, i32, i32, i32, vp, i64, i64, vp, i64, vp, vp, vp]),
     "egs_pose_head": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp]),
     "egs_pose_tail": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp, vp]),
     "egs_pose_accumulate": (C.c_int, [C.POINTER(PoseSequence), vp]),

@@ -13,7 +13,8 @@ uint8[F,H,W] device tensor; the host reads the rows once, after the last frame. 
 clipped it is rendered again eagerly.  The gate itself is fused.interaction_gate, which can write straight into the `gate` segment of a
 graph.pack_frame frame.  losses.label_mask / losses.interaction_gate are the torch statements of both definitions.
 
-Writing the masks to image files and copying them into a dataset is the caller's: `masks` stays on the device (0 / 255, what the PNG holds).
+`masks` stays on the device (0 / 255, what the PNG holds); run(save_masks=paths) also writes them as 8-bit PNG files, encoded on the device
+(png.PngWriter).  Copying them into a dataset is the caller's.
 """
 import copy
 
@@ -81,7 +82,7 @@ class MaskPass(CapturedSweep):
     def _bytes(self, res):
         return self._mask8
 
-    def run(self, frames, cam, capacity=None, capacity_margin=1.25):
+    def run(self, frames, cam, capacity=None, capacity_margin=1.25, save_masks=None):
         """frames: packed frames of graph.pack_label_frame(cam, obj_mask[, gate=keep]) -- a list or an [F, frame] tensor; `gate` is
         keep = 1 - hand mask (frames packed without it count every pixel), the object mask is the target the prediction is counted against --,
         or a frames.FrameStore(label_phase=True): every frame of it, each brought into the static buffers by one decode launch (from a ring
@@ -91,10 +92,17 @@ class MaskPass(CapturedSweep):
         -> dict(masks: uint8[F,H,W] on the device, 255 where the label render's channel mean exceeds the threshold -- every pixel, gated or
         not; predicted, target, intersection, kept: int64[F], counted over the kept pixels; iou: float64[F] (1.0 where the union is empty);
         mean_iou; rerendered: indices of the frames rendered again; instances: int64[F], the captured forwards' instance counts (0 for eager
-        frames))."""
+        frames)).
+        save_masks: F file names -- after the sweep the masks are encoded on the device and written as 8-bit PNG files (png.PngWriter; the
+        result then also carries png_bytes, the file sizes).  The captured body is the same."""
         fig, again, masks = self._sweep(frames, cam, capacity, capacity_margin)
-        return dict(masks=masks, predicted=fig["predicted"], target=fig["target"], intersection=fig["intersection"], kept=fig["kept"],
-                    iou=fig["iou"], mean_iou=float(np.mean(fig["iou"])), rerendered=again, instances=fig["instances"])
+        out = dict(masks=masks, predicted=fig["predicted"], target=fig["target"], intersection=fig["intersection"], kept=fig["kept"],
+                   iou=fig["iou"], mean_iou=float(np.mean(fig["iou"])), rerendered=again, instances=fig["instances"])
+        if save_masks is not None:
+            from .png import PngWriter
+            F, H, W = masks.shape
+            out["png_bytes"] = PngWriter(H, W, 1, masks.device, batch=min(F, 32)).save(masks, save_masks)
+        return out
 
 
 def infer_is_object_from_label(g):

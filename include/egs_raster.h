@@ -695,6 +695,33 @@ int egs_frame_ingest(int height, int width, int flags, int n_frames, int frame, 
                      const uint8_t* src, int src_h, int src_w, int src_c, const int32_t* kk_h, const int32_t* bounds_h,
                      const int32_t* kk_v, const int32_t* bounds_v, void* stream);
 
+/* ---- PNG files written on the device (added within ABI 6: new entries only).
+ *      Every stage of the reference that produces images ends in 8-bit PNG files (trainers/eval_metric.py:95-126 render_results,
+ *      trainers/train_static.py:183-197 the predicted masks).  This entry turns planar uint8 images on the device -- [C][H][W] with
+ *      plane_stride bytes between channels, image_stride between images; the evaluation sweep's `images`, the mask pass's `masks`, a frame
+ *      store's `img` -- into complete files in the caller's buffer: out + i * out_stride holds sizes[i] bytes of
+ *          signature, IHDR (bit depth 8, colour type 0 for one channel and 2 for three, no interlace), IDAT ..., IEND; no other chunk.
+ *      The IDAT payloads together are ONE zlib stream (32 KB window) of the filtered data: H rows of 1 + W C bytes, the filter type then the
+ *      filtered interleaved bytes.  Filter type of a row: filters 0 .. 4 (None, Sub, Up, Average with floor((a + b) / 2), Paeth) on the raw
+ *      neighbours, the pixel to the left and the row above taken as 0 where they do not exist; score = sum of min(v, 256 - v) over the
+ *      W C filtered bytes; the lowest score wins, ties go to the lowest type -- a pure function of the image (egogaussian_amd/png.py
+ *      filter_rows is the torch statement).  The stream is compressed in independent segments, one per row (a row of more than 4096
+ *      stream bytes in pieces of 4096), each a stored block or a fixed / dynamic Huffman block followed by the empty stored block of a
+ *      zlib full flush, each an IDAT chunk of its own; the 2-byte zlib header and the final block with the Adler-32 are two more.
+ *      Three launches whatever the content, no allocation, no synchronisation, no global state: can be captured.  Same input, same bytes.
+ *        egs_png_bound          capacity of one image's slot: 77 + H (W C + 1) + 17 H ceil((W C + 1) / 4096) -- the fixed chunks, the
+ *                               filtered data, and per segment 12 bytes of chunk framing + 5 of a stored block's header.  0 for a size
+ *                               egs_png_encode refuses.  Host arithmetic.
+ *        egs_png_scratch_bytes  device bytes `scratch` must hold for n_images (16-byte aligned); 0 for a refused size or n_images < 1.
+ *        egs_png_encode         EGS_ERR_ARG before any device work: n_images < 1, a NULL pointer, a misaligned scratch (16) or sizes (4),
+ *                               plane_stride < W H with three channels, image_stride shorter than an image when n_images > 1,
+ *                               out_stride < egs_png_bound.  EGS_ERR_RANGE: a side outside 1 .. 32767, channels not 1 or 3,
+ *                               n_images > 65535, a bound of 4 GiB or more. */
+size_t egs_png_bound(int width, int height, int channels);
+size_t egs_png_scratch_bytes(int n_images, int width, int height, int channels);
+int egs_png_encode(int n_images, int width, int height, int channels, const uint8_t* src, int64_t image_stride, int64_t plane_stride,
+                   uint8_t* out, int64_t out_stride, uint32_t* sizes /*device [n_images] out*/, void* scratch, void* stream);
+
 /* ---- the object pose sequence on the device (added within ABI 6: new entries only).
  *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the
  *      frame's key and rebuild the accumulated sequence (/root/reference/trainers/fine_obj.py:97-126,216-224,

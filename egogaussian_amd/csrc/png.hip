@@ -28,6 +28,7 @@
 //   k_png_gather    grid (segments, images): the chunk goes to its offset in the file.
 // Every byte is a pure function of the image: integer LDS atomics (add, or, xor) and scans only, nothing depends on arrival order.
 #include "egs_common.h"
+#include "png_common.h"
 
 #define PNG_WG 256
 #define PNG_PER 16
@@ -42,7 +43,6 @@
 #define PNG_CHUNK_EXTRA 17               // per segment: chunk framing 12 + stored-block header 5
 #define PNG_MAX_SIDE 32767
 #define PNG_ADLER 65521u
-#define PNG_POLY 0xedb88320u
 
 namespace {
 
@@ -63,12 +63,6 @@ __host__ __device__ inline int png_seg_len(const PngArgs& a, int seg) {       //
     return rest < PNG_SEG ? rest : PNG_SEG;
 }
 
-__device__ __forceinline__ int png_paeth(int a, int b, int c) {
-    const int p = a + b - c;
-    const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
 __device__ __forceinline__ int png_filter(int f, int x, int a, int b, int c) {
     int v;
     switch (f) {
@@ -79,17 +73,6 @@ __device__ __forceinline__ int png_filter(int f, int x, int a, int b, int c) {
         default: v = x - png_paeth(a, b, c); break;
     }
     return v & 255;
-}
-
-// a * b mod P over GF(2), reflected (bit 31 is x^0), as zlib's multmodp; 32 steps whatever the operands
-__device__ __forceinline__ uint32_t png_mulmod(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-#pragma unroll 4
-    for (int i = 31; i >= 0; i--) {
-        if ((a >> i) & 1u) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ PNG_POLY : b >> 1;
-    }
-    return p;
 }
 
 __device__ __forceinline__ uint32_t png_crc_bitwise(uint32_t c, uint32_t byte) {

@@ -149,3 +149,62 @@ class EvalPass(CapturedSweep):
         if self.lpips is not None:
             out.update(lpips=fig["lpips"], lpips_taps=fig["lpips_taps"], mean_lpips=float(np.mean(fig["lpips"])))
         return out
+
+
+def metrics_from_files(renders, gts, hands, lpips=None, device="cuda", batch=32):
+    """The device route of the reference's calculate_metric (its trainers/eval_metric.py:129-175): the figures of a directory of 8-bit PNG
+    files -- renders[k], gts[k] (RGB) and hands[k] (1 or 3 channels, channel 0 is used; the file render_results wrote: 255 where the pixel
+    counts) -- paths or bytes.  The files go up as they are and are decoded on the device (png.PngReader); keep = (hand byte / 255) >= 0.5,
+    the images are byte / 255 as planar float tensors, and the same kernels as EvalPass measure them (fused.eval_metrics and, with
+    lpips=lpips.LPIPS(...), csrc/lpips.hip) -- an EvalPass sweep that saved these files reports the same sse, ssim_sum and LPIPS rows.
+    A hand file with a byte other than 0 / 255 raises ValueError: masks are binary by contract (include/egs_raster.h egs_eval_metrics).
+    One read of the decoder's status words per batch of files, one of the hand check, one of the rows.
+    -> dict(ssim, psnr[, lpips]: float64[F]; sse: int64[F]; ssim_sum: float64[F]; rows: [(ssim, psnr[, lpips])] per file; means: the same
+    tuple of plain means, in the reference's order SSIM, PSNR, LPIPS)."""
+    from . import png as _png
+    renders, gts, hands = list(renders), list(gts), list(hands)
+    F = len(renders)
+    if F < 1 or len(gts) != F or len(hands) != F:
+        raise ValueError(f"metrics_from_files: {F} renders, {len(gts)} ground truths and {len(hands)} hand masks; one of each per frame, at least one")
+    dev = torch.device(device)
+    reader = _png.PngReader(dev, batch=batch)
+    try:
+        arrays = reader.read(renders + gts + hands)
+    except ValueError as e:
+        raise ValueError(f"metrics_from_files: {e} (files 0 .. {F - 1}: renders, then the ground truths, then the hand masks)") from None
+    triples = []
+    for k in range(F):
+        r, g, h = arrays[k], arrays[F + k], arrays[2 * F + k]
+        if r.shape[2] != 3 or r.shape != g.shape or h.shape[:2] != r.shape[:2]:
+            raise ValueError(f"metrics_from_files: frame {k}: render {tuple(r.shape)}, ground truth {tuple(g.shape)}, hand mask {tuple(h.shape)}; "
+                             "the images are [h,w,3] of one size and the mask has their size")
+        triples.append((r, g, h[:, :, 0]))
+    grey = torch.stack([((h != 0) & (h != 255)).any() for _, _, h in triples]).cpu().tolist()
+    if any(grey):
+        raise ValueError(f"metrics_from_files: hand mask(s) {[k for k, b in enumerate(grey) if b]} hold bytes other than 0 and 255: masks are binary "
+                         "by contract")
+    rows, cursor = fused.eval_rows(F, dev)
+    lp_rows, lp_cursor = fused.lpips_rows(F, dev) if lpips is not None else (None, None)
+    sizes = []
+    with torch.no_grad():
+        for r, g, h in triples:
+            image, gt = r.permute(2, 0, 1).to(torch.float32) / 255, g.permute(2, 0, 1).to(torch.float32) / 255
+            keep = (h.to(torch.float32) / 255 >= 0.5).to(torch.float32)
+            res = fused.eval_metrics(image.contiguous(), gt.contiguous(), keep=keep, rows=rows, cursor=cursor, out8=lpips is not None)
+            if lpips is not None:
+                lpips(res["q_image"], res["q_gt"], keep=keep, rows=lp_rows, cursor=lp_cursor)
+            sizes.append(image.numel())
+    both = rows if lpips is None else torch.cat([rows, lp_rows.view(torch.int64)], 1)
+    both = both.cpu()
+    out = dict(sse=np.zeros(F, dtype=np.int64), ssim_sum=np.zeros(F), ssim=np.zeros(F), psnr=np.zeros(F))
+    for k in range(F):
+        fig = decode_rows(both[k:k + 1, :fused.EVAL_ROW_WORDS].contiguous(), sizes[k])
+        for name in out:
+            out[name][k] = fig[name][0]
+    names = ["ssim", "psnr"]
+    if lpips is not None:
+        out.update(decode_lpips_rows(both[:, fused.EVAL_ROW_WORDS:].contiguous().view(torch.float64)))
+        names.append("lpips")
+    out["rows"] = [tuple(float(out[n][k]) for n in names) for k in range(F)]
+    out["means"] = tuple(float(np.mean(out[n])) for n in names)
+    return out

@@ -14,7 +14,11 @@ masks collapse to {0, 1} (binarize_mask, :41-60).  This module states that path 
 
 The resize (Pillow Resample.c, modes L and RGB, no box, no reducing gap): a horizontal pass when the width changes, then a vertical pass
 when the height changes; the intermediate is 8-bit, rounded and clamped like the output; a pass whose size does not change is skipped.  A
-pixel of a pass is clamp((2^21 + sum in[xmin + x] * kk[x]) >> 22, 0, 255) in int32 with an arithmetic shift.  File decoding stays on the host.
+pixel of a pass is clamp((2^21 + sum in[xmin + x] * kk[x]) >> 22, 0, 255) in int32 with an arithmetic shift.
+
+Files: FrameIngest.put_files takes 8-bit grey or RGB PNG files (paths or bytes) in place of arrays and decodes them on the device
+(egogaussian_amd/png.py PngReader, csrc/png_decode.hip) in front of the same kernel; put() with host-decoded arrays is unchanged.  JPEG, and
+the PNG modes Pillow resizes differently (palette, alpha, 16-bit, interlaced ones too), are decoded on the host and go through put().
 """
 import math
 
@@ -175,6 +179,8 @@ class FrameIngest:
         self._pinned = torch.empty((3, h * w * 3), dtype=torch.uint8).pin_memory()
         self._device = torch.empty((3, h * w * 3), dtype=torch.uint8, device=dev)
         self._uploaded = [None, None, None]
+        from . import png as _png
+        self._reader = _png.PngReader(dev, batch=3)                    # put_files: its buffers are allocated by the first decode
 
     source = staticmethod(_source)      # (array, name, h, w, channels) -> uint8 [h,w,C] tensor, or the refusal
 
@@ -222,6 +228,31 @@ class FrameIngest:
         st.small[i] = block
         for plane, slot, t in groups:
             self._launch(i, plane, slot, t)
+
+    def put_files(self, i, cam, image=None, hand_mask=None, obj_mask=None, accum_R=None, accum_T=None, pose_rows=None):
+        """put() with 8-bit PNG files -- paths or bytes -- in place of the arrays.  The sizes and channel counts are checked from IHDR
+        against src_hw before any device work (png.parse; a mode this path does not take is refused there); the files are then uploaded as
+        they are and decoded on the device on the store's stream, in front of the ingest launches.  Nothing is read back but the decoder's
+        status words, once; a file the device refuses raises ValueError and the store is left as it was.  The store ends up bit-identical
+        to put() with the decoded arrays."""
+        given = [(name, f) for name, f in (("obj_mask", obj_mask), ("hand_mask", hand_mask), ("image", image)) if f is not None]
+        who = ", ".join(f"file {k} is {name}" for k, (name, _) in enumerate(given))
+        try:
+            loaded = self._reader.load([f for _, f in given])           # host only: the chunk walk and IHDR of every file
+        except ValueError as e:
+            raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
+        for (name, _), (W, H, C, _, _) in zip(given, loaded[2]):
+            if (H, W) != (self.h, self.w) or (name == "image" and C != 3):
+                raise ValueError(f"FrameIngest.put_files: {name} is {W}x{H} with {C} channel(s); the source resolution is {self.w}x{self.h}"
+                                 f"{' and an image has 3' if name == 'image' else ''}; {_ADVICE}")
+        with _hip.device_ctx(self.store.device):
+            try:
+                decoded = self._reader.decode(*loaded)
+            except ValueError as e:
+                raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
+        arrays = {name: t for (name, _), t in zip(given, decoded)}
+        self.put(i, cam, image=arrays.get("image"), hand_mask=arrays.get("hand_mask"), obj_mask=arrays.get("obj_mask"), accum_R=accum_R,
+                 accum_T=accum_T, pose_rows=pose_rows)
 
     def plane(self, i, which, array):
         """One plane group of frame i alone: which = "image", "hand_mask" or "obj_mask" (put() is the small block and up to three of these,

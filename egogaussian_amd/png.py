@@ -1,4 +1,4 @@
-"""8-bit PNG files from device tensors: the write side of the files frame ingest reads.
+"""8-bit PNG files from device tensors and back: the write side of the files frame ingest reads, and (at the end of the module) their read side.
 
 Every stage of the reference that produces images ends in 8-bit PNG files: render_results (its trainers/eval_metric.py:95-126) writes render,
 ground truth and 1 - hand mask for every frame, and the end of each static phase (trainers/train_static.py:183-197) one predicted mask per
@@ -13,6 +13,10 @@ file bytes there (csrc/png.hip, include/egs_raster.h egs_png_encode) so that the
     encode            device uint8 [F,C,H,W] or [F,H,W] -> (buf uint8 [F, bound], sizes int32 [F]) by the kernel
     PngWriter         owns buf, scratch and pinned staging; save(images, paths) encodes batch by batch, reads each batch's sizes once, copies
                       the used prefix of each slot and writes the files from a small thread pool
+
+    parse             the host's share of READING a file, O(chunks): signature, chunk walk, the small chunks' CRCs, IHDR -> (W, H, C, IDAT table)
+    PngReader         file bytes -> device uint8 [h,w,C] by the kernels (csrc/png_decode.hip, csrc/png_inflate.h: CRC, inflate, unfilter and
+                      every check of the stream on the device, one status word per file); decode_device for a single file
 
 The file: signature, IHDR (bit depth 8, colour type 0 or 2, no interlace), IDAT ..., IEND.  The IDAT payloads together are one zlib stream
 of the filtered data -- H rows of a filter-type byte and the W C filtered bytes of the interleaved row.  The filter type is libpng's
@@ -297,3 +301,264 @@ class PngWriter:
                 list(pool.map(_write, paths[lo:lo + n], [memoryview(host[i])[:sz[i]] for i in range(n)]))      # (done before staging is reused)
                 written += sz
         return written
+
+
+# ---- the read side: file bytes go up as they are, the device inflates, checks and unfilters them (csrc/png_decode.hip) ------------------------
+STATUS = {1: "wrong CRC-32 in an IDAT chunk", 2: "zlib header (CM, CINFO, FCHECK or FDICT)", 3: "block type 3", 4: "a stored block's LEN / NLEN",
+          5: "a code-length code or a set of code lengths over-subscribed or incomplete", 6: "a repeat code with no previous length or past HLIT + HDIST",
+          7: "no end-of-block code", 8: "literal/length symbol 286 / 287, distance symbol 30 / 31, or bits no code owns",
+          9: "a distance reaching before the start of the output", 10: "the stream ends inside a block", 11: "more inflated bytes than H (1 + W C)",
+          12: "fewer inflated bytes than H (1 + W C)", 13: "wrong Adler-32", 14: "bytes behind the zlib stream", 15: "a filter type above 4"}
+_FILE = np.dtype([("width", "<i4"), ("height", "<i4"), ("channels", "<i4"), ("n_idat", "<i4"), ("idat_begin", "<u4"), ("stream_bytes", "<u4"),
+                  ("file_offset", "<u8"), ("file_bytes", "<u8"), ("stream_offset", "<u8"), ("inflate_offset", "<u8"), ("out_offset", "<u8")])      # egs_png_file
+_IDAT = np.dtype([("file", "<u4"), ("src", "<u4"), ("length", "<u4"), ("dst", "<u4")])                                                             # egs_png_idat
+_CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
+
+
+def status_text(word):
+    """What a status word of egs_png_decode says."""
+    word = int(word)
+    if word == 0:
+        return "ok"
+    text = STATUS.get(word & 255, f"status {word}")
+    return f"{text} (IDAT chunk {word >> 8})" if (word & 255) == 1 else text
+
+
+def parse(file_bytes):
+    """The host's share of reading a PNG file, O(number of chunks): signature, the chunk walk (lengths inside the file, IHDR first and 13
+    bytes, IDAT chunks consecutive, IEND last and nothing behind it, no unknown critical chunk), the CRC-32 of IHDR, PLTE and IEND, the IHDR
+    fields.  No IDAT byte is touched: their CRCs, the zlib stream and the filter types are the device's (png.PngReader).
+    -> (W, H, C, [(offset, length)] of the IDAT payloads).  ValueError for every refusal; the modes frame ingest does not take (palette,
+    alpha, 1 / 2 / 4 / 16 bits, interlace) name the field and carry ingest's advice."""
+    from .ingest import _ADVICE
+    data = file_bytes if isinstance(file_bytes, (bytes, bytearray, memoryview)) else bytes(file_bytes)
+    n = len(data)
+    if bytes(data[:8]) != SIGNATURE:
+        raise ValueError("png.parse: no PNG signature")
+    pos, idat, ihdr, state, ended = 8, [], None, 0, False               # state 0: before the IDATs, 1: inside, 2: behind
+    while pos < n:
+        if pos + 12 > n:
+            raise ValueError(f"png.parse: a truncated chunk header at byte {pos}")
+        length, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        if pos + 12 + length > n:
+            raise ValueError(f"png.parse: chunk {kind!r} at byte {pos} runs past the end of the file")
+        if (ihdr is None) != (kind == b"IHDR"):
+            raise ValueError(f"png.parse: IHDR must be the first chunk and the only one of its kind; chunk {kind!r} at byte {pos}")
+        if kind in (b"IHDR", b"PLTE", b"IEND"):
+            if struct.unpack(">I", data[pos + 8 + length:pos + 12 + length])[0] != (zlib.crc32(data[pos + 4:pos + 8 + length]) & 0xFFFFFFFF):
+                raise ValueError(f"png.parse: wrong CRC-32 in chunk {kind!r} at byte {pos}")
+        if kind == b"IHDR":
+            if length != 13:
+                raise ValueError(f"png.parse: IHDR is 13 bytes, not {length}")
+            ihdr = struct.unpack(">IIBBBBB", data[pos + 8:pos + 21])
+        elif kind == b"IDAT":
+            if state == 2:
+                raise ValueError(f"png.parse: the IDAT chunks must be consecutive; another one at byte {pos}")
+            state = 1
+            idat.append((pos + 8, length))
+        else:
+            if kind not in _CRITICAL and not (kind[0] & 0x20):
+                raise ValueError(f"png.parse: unknown critical chunk {kind!r} at byte {pos}")
+            if state == 1:
+                state = 2
+        pos += 12 + length
+        if kind == b"IEND":
+            if length:
+                raise ValueError("png.parse: IEND carries data")
+            ended = True
+            break
+    if not ended:
+        raise ValueError("png.parse: the file ends without an IEND chunk")
+    if pos != n:
+        raise ValueError("png.parse: bytes behind IEND")
+    if not idat:
+        raise ValueError("png.parse: no IDAT chunk")
+    W, H, depth, colour, comp, filt, lace = ihdr
+    if not 1 <= W <= MAX_SIDE:
+        raise ValueError(f"png.parse: IHDR width {W} is outside 1 .. {MAX_SIDE}")
+    if not 1 <= H <= MAX_SIDE:
+        raise ValueError(f"png.parse: IHDR height {H} is outside 1 .. {MAX_SIDE}")
+    if depth != 8:
+        raise ValueError(f"png.parse: IHDR bit depth {depth}: this path reads 8-bit samples, Pillow resizes the other depths differently; {_ADVICE}")
+    if colour not in (0, 2):
+        raise ValueError(f"png.parse: IHDR colour type {colour} (palette or alpha): this path reads grey and RGB; {_ADVICE}")
+    if comp:
+        raise ValueError(f"png.parse: IHDR compression method {comp}")
+    if filt:
+        raise ValueError(f"png.parse: IHDR filter method {filt}")
+    if lace:
+        raise ValueError(f"png.parse: IHDR interlace method {lace}: interlaced files are not read here; {_ADVICE}")
+    return W, H, 3 if colour == 2 else 1, idat
+
+
+def _up(v, a):
+    return (v + a - 1) // a * a
+
+
+def plan(parsed, out_gap=0):
+    """parsed: [(W, H, C, idat, file length)] -> dict(desc, idat: the two tables of egs_png_decode with files, streams, inflated data and outputs
+    packed in order -- files at multiples of 16, outputs at multiples of 256 with `out_gap` bytes between them --, files_bytes, stream_bytes,
+    inflate_bytes, out_bytes: the totals)."""
+    desc = np.zeros(len(parsed), dtype=_FILE)
+    idat = np.zeros(sum(len(p[3]) for p in parsed), dtype=_IDAT)
+    fo = so = io = oo = k = 0
+    for i, (W, H, C, chunks, nbytes) in enumerate(parsed):
+        stream = sum(n for _, n in chunks)
+        if nbytes >= 1 << 32 or stream >= 1 << 31:
+            raise ValueError(f"png: file {i} has {nbytes} bytes, {stream} of them in IDAT chunks; the limit is 2 GiB")
+        desc[i] = (W, H, C, len(chunks), k, stream, fo, nbytes, so, io, oo)
+        at = 0
+        for off, n in chunks:
+            idat[k] = (i, off, n, at)
+            at += n
+            k += 1
+        fo += _up(nbytes, 16)
+        so += _up(stream, 16)
+        io += _up(H * (1 + W * C), 16)
+        oo += _up(H * W * C + out_gap, 256)
+    return dict(desc=desc, idat=idat, files_bytes=fo, stream_bytes=so, inflate_bytes=io, out_bytes=oo)
+
+
+class PngReader:
+    """8-bit PNG files -> device uint8 [h, w, C] tensors: the mirror of PngWriter.  Owns the pinned staging, the device buffer the files and
+    their tables are uploaded to, the scratch, the outputs and the status words; each grows to what the largest batch so far needed
+    (max_file_bytes / max_pixels reserve it up front).  Per batch of at most `batch` files: the host walks the chunks (parse), ONE upload,
+    three launches, ONE read of the status words.  guard > 0 (a multiple of 256) is for tests: every byte of the device buffers that a
+    call is not entitled to -- `guard` bytes before and behind each buffer, the gaps between the output slots, and everything behind the
+    status words, the scratch bytes and the outputs IN USE up to the end of their allocations -- holds 0xA5 before the launches, and
+    check_guards() says whether all of it still does."""
+    GUARD_BYTE = 0xA5
+
+    def __init__(self, device, batch=32, max_file_bytes=0, max_pixels=0, guard=0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"PngReader: the PNG decoder has no CPU path (device {self.device}); png.decode is the host reader")
+        self.batch, self.guard = int(batch), int(guard)
+        if self.batch < 1 or self.batch > 65535 or self.guard < 0 or self.guard % 256:
+            raise ValueError("PngReader: batch of 1 .. 65535, guard a multiple of 256")
+        self._dev, self._pin = {}, None
+        self.host_reads = 0                                             # reads of the status words (one per batch)
+        self.last_status, self.last_results = [], []                    # of the last read(): a refused batch leaves them to look at
+        self._slack_ok, self._gaps = True, []
+        if max_file_bytes or max_pixels:
+            self._pinned(self.batch * (_up(int(max_file_bytes), 16) + 4096))
+            self._buffer("blob", self.batch * (_up(int(max_file_bytes), 16) + 4096))
+            self._buffer("out", self.batch * _up(3 * int(max_pixels) + self.guard, 256))
+            self._buffer("scratch", self.batch * (_up(int(max_file_bytes), 16) + _up(3 * int(max_pixels) + MAX_SIDE, 16)) + 4096)
+
+    def _pinned(self, nbytes):
+        if self._pin is None or self._pin.numel() < nbytes:
+            self._pin = torch.empty(_up(nbytes, 4096), dtype=torch.uint8).pin_memory()
+        return self._pin
+
+    def _buffer(self, name, nbytes):
+        """The inner `nbytes` (at least) of a device buffer with `guard` bytes on either side."""
+        g, t = self.guard, self._dev.get(name)
+        if t is None or t.numel() < nbytes + 2 * g:
+            t = torch.full((_up(nbytes, 4096) + 2 * g,), self.GUARD_BYTE, dtype=torch.uint8, device=self.device)
+            self._dev[name] = t
+        return t[g:t.numel() - g]
+
+    def _intact(self, t):
+        return bool((t == self.GUARD_BYTE).all())
+
+    def check_guards(self):
+        """True when every guard byte still holds GUARD_BYTE: around the buffers, between and behind the output slots of the last read(),
+        and -- looked at after every batch of that read() -- behind the status words and the scratch bytes the batch used."""
+        g = self.guard
+        ok = self._slack_ok
+        for name, t in self._dev.items():
+            if g:
+                ok = ok and bool((t[:g] == self.GUARD_BYTE).all()) and bool((t[t.numel() - g:] == self.GUARD_BYTE).all())
+        for lo, hi in self._gaps:
+            ok = ok and bool((self._dev["out"][lo:hi] == self.GUARD_BYTE).all())
+        return ok
+
+    def read(self, files):
+        """files: a list of bytes or paths -> a list of device uint8 [h, w, C] tensors, views into the reader's output buffer, valid until the
+        next call.  ValueError for a file parse() refuses, and for a file the device refuses: it names the file's index (and path) and says
+        what the status word says."""
+        return self.decode(*self.load(files))
+
+    @staticmethod
+    def load(files):
+        """The host's share of read(): files (bytes or paths) -> (blobs, names, parsed), parsed[i] = parse(blob) + (len(blob),).  No device
+        work; ValueError for a file parse() refuses."""
+        blobs, names = [], []
+        for i, f in enumerate(files):
+            if isinstance(f, (bytes, bytearray, memoryview)):
+                blobs.append(f)
+                names.append(f"file {i}")
+            else:
+                with open(f, "rb") as fh:
+                    blobs.append(fh.read())
+                names.append(f"file {i} ({f})")
+        parsed = []
+        for name, b in zip(names, blobs):
+            try:
+                parsed.append(parse(b) + (len(b),))
+            except ValueError as e:
+                raise ValueError(f"{name}: {e}") from None
+        return blobs, names, parsed
+
+    def decode(self, blobs, names, parsed):
+        """The device's share of read(), from what load() returned."""
+        self._slack_ok, self._gaps = True, []
+        if not parsed:
+            return []
+        whole = plan(parsed, self.guard)
+        out = self._buffer("out", whole["out_bytes"])
+        g0 = self.guard
+        if g0:
+            out.fill_(self.GUARD_BYTE)
+            self._gaps.append((g0 + whole["out_bytes"], g0 + out.numel()))      # behind the last slot, up to the end of the allocation
+        results, failures = [], []
+        lib = _lib.load()
+        for lo in range(0, len(parsed), self.batch):
+            part = parsed[lo:lo + self.batch]
+            p = plan(part, self.guard)
+            n, n_idat = len(part), len(p["idat"])
+            t_desc, t_idat = _up(n * _FILE.itemsize, 256), _up(n_idat * _IDAT.itemsize, 256)
+            up_bytes = t_desc + t_idat + p["files_bytes"]
+            pin = self._pinned(up_bytes)
+            host = pin.numpy()
+            host[:n * _FILE.itemsize] = p["desc"].view(np.uint8).reshape(-1)
+            host[t_desc:t_desc + n_idat * _IDAT.itemsize] = p["idat"].view(np.uint8).reshape(-1)
+            for d, b in zip(p["desc"], blobs[lo:lo + n]):
+                at = t_desc + t_idat + int(d["file_offset"])
+                host[at:at + len(b)] = np.frombuffer(b, dtype=np.uint8)
+            blob = self._buffer("blob", up_bytes)
+            blob[:up_bytes].copy_(pin[:up_bytes], non_blocking=True)
+            need = int(lib.egs_png_decode_scratch_bytes(n_idat, p["stream_bytes"], p["inflate_bytes"]))
+            scratch = self._buffer("scratch", need)
+            status = self._buffer("status", 4 * self.batch)
+            base = int(whole["desc"]["out_offset"][lo])                  # this batch's slots inside the call's output buffer
+            self.last_call = (n, blob.data_ptr() + t_desc + t_idat, p["files_bytes"], pin.data_ptr(), blob.data_ptr(), pin.data_ptr() + t_desc,
+                              blob.data_ptr() + t_desc, n_idat, out.data_ptr() + base, p["out_bytes"], status.data_ptr(), scratch.data_ptr(), need)
+            if g0:                                                      # everything behind the bytes in use holds the guard byte
+                status[4 * n:].fill_(self.GUARD_BYTE)
+                scratch[need:].fill_(self.GUARD_BYTE)
+            with _hip.device_ctx(self.device):
+                _lib.check(lib.egs_png_decode(*self.last_call, _hip.stream_of(self.device)))
+            words = status[:4 * n].view(torch.int32).cpu().tolist()     # (synchronises: the staging may be refilled)
+            self.host_reads += 1
+            if g0:
+                self._slack_ok = self._slack_ok and self._intact(status[4 * n:]) and self._intact(scratch[need:])
+            for k, (d, w) in enumerate(zip(p["desc"], words)):
+                W, H, C = int(d["width"]), int(d["height"]), int(d["channels"])
+                o = base + int(d["out_offset"])
+                results.append(out[o:o + H * W * C].view(H, W, C))
+                if self.guard:
+                    self._gaps.append((g0 + o + H * W * C, g0 + o + _up(H * W * C + self.guard, 256)))
+                if w:
+                    failures.append(f"{names[lo + k]}: {status_text(w & 0xFFFFFFFF)} (status {w & 0xFFFFFFFF})")
+            self.last_status = (self.last_status if lo else []) + [w & 0xFFFFFFFF for w in words]
+        self.last_results = results
+        if failures:
+            raise ValueError("PngReader.read: " + "; ".join(failures))
+        return results
+
+
+def decode_device(file_bytes, device="cuda"):
+    """One file (bytes or a path) -> device uint8 [h, w, C], by the kernels.  (A reader of many files keeps a PngReader.)"""
+    return PngReader(device, batch=1).read([file_bytes])[0].clone()

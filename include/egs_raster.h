@@ -722,6 +722,55 @@ size_t egs_png_scratch_bytes(int n_images, int width, int height, int channels);
 int egs_png_encode(int n_images, int width, int height, int channels, const uint8_t* src, int64_t image_stride, int64_t plane_stride,
                    uint8_t* out, int64_t out_stride, uint32_t* sizes /*device [n_images] out*/, void* scratch, void* stream);
 
+/* ---- PNG files read on the device (added within ABI 6: new entries only): the read side of the entry above.
+ *      The reference opens 8-bit PNG files at dataset load (scene/dataset_readers.py:137-160: image, hand mask, object mask), at the stage
+ *      hand-off (the masks the static stage wrote) and in calculate_metric (trainers/eval_metric.py:129-175).  This entry takes the bytes
+ *      of a batch of files as they are on disk and leaves interleaved uint8 [height][width][channels] arrays in `out`, which is what frame
+ *      ingest (egs_ingest_*) starts from.  Accepted: bit depth 8, colour type 0 or 2, no interlace; ancillary chunks anywhere; the zlib
+ *      stream cut into IDAT chunks anywhere (empty ones too); any CINFO <= 7; stored, fixed and dynamic blocks in any mix.  Everything else
+ *      is the caller's to refuse from IHDR (egogaussian_amd/png.py parse does).
+ *      Host work is the chunk walk -- O(chunks), no IDAT byte touched -- which fills two tables:
+ *        egs_png_file   per file: width, height, channels (1 or 3); its IDAT chunks idat[idat_begin .. idat_begin + n_idat), n_idat >= 1;
+ *                       stream_bytes, the sum of their lengths; file_offset / file_bytes, the file inside `files`; stream_offset and
+ *                       inflate_offset (multiples of 16), its places in the scratch areas of 16-byte-rounded streams and of the inflated data
+ *                       (height (1 + width channels) bytes, rounded to 16); out_offset, where its pixels go in `out`.
+ *        egs_png_idat   per chunk: file, src (offset of the payload inside the file; "IDAT" precedes it, the CRC follows), length, dst
+ *                       (offset inside the file's stream: the chunks of a file tile its stream in order).
+ *      Both tables are passed twice: a host copy, which the entry checks, and a device copy with the same content, which the kernels
+ *      read (the caller uploads it with the files; the entry copies nothing, so the call can be captured).
+ *      Three launches (gather + CRC per chunk; inflate, one wave per file; unfilter), no allocation, no synchronisation, no global state.
+ *      status[i] (device): 0, or the first failure of file i --
+ *          1 | chunk << 8  CRC-32 of that IDAT chunk          6  repeat without a previous length / past HLIT + HDIST    11  more inflated bytes than H (1 + W C)
+ *          2  zlib header (CM, CINFO, FCHECK, FDICT)        7  no end-of-block code                                    12  fewer
+ *          3  block type 3                                   8  symbol 286 / 287, distance symbol 30 / 31, or bits      13  Adler-32
+ *          4  stored LEN / NLEN                                 no code of an incomplete set owns                       14  bytes behind the stream
+ *          5  a code set over-subscribed or incomplete       9  a distance before the start of the output               15  filter type above 4
+ *             (zlib's exception: one code of 1 bit;         10  the stream ends inside a block
+ *             for distances also none)
+ *      A failed file leaves its pixels unspecified inside its own slot; nothing else is touched and the other files are unaffected.
+ *      Verdicts equal zlib's inflate().  EGS_ERR_ARG before any device work: n_files or n_idat < 1, a NULL pointer, a misaligned scratch
+ *      (16), status (4) or device table, files / streams / inflated data / outputs that are not ascending, overlap or leave their buffers
+ *      (files_bytes, out_bytes, scratch_bytes), chunks that leave their file or do not tile the stream.  EGS_ERR_RANGE: a side outside
+ *      1 .. 32767, channels not 1 or 3, n_files > 65535, a per-file output or stream of 2 GiB or more.
+ *        egs_png_decode_scratch_bytes   256-aligned areas: 4 n_idat flag bytes, the streams, the inflated data (totals as the offsets above
+ *                                       imply: the sums of the 16-byte-rounded sizes); 0 for n_idat < 1. */
+typedef struct egs_png_file {
+    int32_t width, height, channels, n_idat;
+    uint32_t idat_begin, stream_bytes;
+    uint64_t file_offset, file_bytes, stream_offset, inflate_offset, out_offset;
+} egs_png_file;
+typedef struct egs_png_idat { uint32_t file, src, length, dst; } egs_png_idat;
+size_t egs_png_decode_scratch_bytes(int n_idat, size_t total_stream_bytes, size_t total_inflate_bytes);
+int egs_png_decode(int n_files, const uint8_t* files /*device*/, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
+                   const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out /*device*/, size_t out_bytes,
+                   uint32_t* status /*device [n_files] out*/, void* scratch, size_t scratch_bytes, void* stream);
+/*      The same call restricted to some of its launches, for measurements (tools/time_png_decode.py): phases is a mask of 1 (gather + CRC),
+ *      2 (inflate) and 4 (unfilter), 1 .. 7 (else EGS_ERR_ARG).  A later launch alone reads what an earlier call with the same arguments
+ *      left in `scratch` and `status`.  egs_png_decode is phases = 7. */
+int egs_png_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
+                          const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
+                          uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases);
+
 /* ---- the object pose sequence on the device (added within ABI 6: new entries only).
  *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the
  *      frame's key and rebuild the accumulated sequence (/root/reference/trainers/fine_obj.py:97-126,216-224,

@@ -15,10 +15,13 @@
 //                    y0 + l one pixel behind lane l - 1, takes b and c (the pixels above and above-left) from that lane by a shift of the
 //                    wave and keeps a (the pixel to the left) itself; a block takes W + 63 steps.  The predictor is selected per lane
 //                    without a branch.  Lane 0 reads the row above the block from the output, which the block before it wrote.
+// egs_png_decode_ex adds, behind flags (include/egs_raster.h), the segmented route -- k_pngd_measure, k_pngd_scan, k_pngd_place in front of
+// k_pngd_inflate, which then skips the files they decoded (png_segments.h).
 // A file whose status is not 0 leaves its output unspecified inside its own slot; nothing outside a file's slots is written (the bounds
 // argument is in png_inflate.h for the inflater, and at each index below for the rest).
 #include "egs_common.h"
 #include "png_inflate.h"
+#include "png_segments.h"
 #include "png_common.h"
 
 #define PNGD_WG 256
@@ -35,7 +38,13 @@ struct PngdArgs {
     uint32_t* status;
     uint8_t* scratch;                        // flag words [n_idat], then the streams, then the inflated data
     unsigned long long stream_base, inflate_base;
+    // egs_png_decode_ex with EGS_PNG_SEGMENTS (else NULL: the launches below that do not name them run as they always did)
+    PngsRecord* records;                     // scratch: a record per IDAT chunk
+    uint32_t* routes;                        // scratch: the route word per file, which k_pngd_inflate reads as its skip array
+    uint32_t* route_out;                     // the caller's copy, or NULL
 };
+
+static_assert(PNGS_MAX == EGS_PNG_SEGMENT_MAX && sizeof(PngsRecord) == 16, "png_segments.h and egs_raster.h disagree");
 
 __device__ __forceinline__ uint32_t pngd_x8n(uint32_t k) {       // x^(8 k) mod P: at most 32 squarings
     uint32_t p = 0x80000000u, sq = 0x00800000u;
@@ -84,9 +93,64 @@ __global__ __launch_bounds__(PNGD_WG) void k_pngd_gather(PngdArgs a) {
     }
 }
 
+// ---- the segmented route (png_segments.h): measure per chunk, scan per file, place per chunk -------------------------------------------------
+// 15 KiB of LDS (the 8 KiB segment buffer, the code tables, the buffer of the stream): ten workgroups per CU.
+__device__ __forceinline__ void pngd_chunk(const PngdArgs& a, uint32_t k, PngsState& s, uint32_t& start, bool& first, egs_png_file& f, egs_png_idat& e) {
+    e = a.idat[k];
+    f = a.desc[e.file];
+    s.in = a.scratch + a.stream_base + f.stream_offset;               // the file's stream; the wave reads below n = this chunk's end
+    s.n = e.dst + e.length;                                           // <= stream_bytes (host-checked: the chunks tile the stream)
+    s.out = nullptr;
+    start = e.dst;
+    first = k == f.idat_begin;
+}
+
+__global__ __launch_bounds__(64) void k_pngd_measure(PngdArgs a) {
+    __shared__ PngsMem mem;
+    PngsState s;
+    s.m = &mem;
+    uint32_t start;
+    bool first;
+    egs_png_file f;
+    egs_png_idat e;
+    pngd_chunk(a, blockIdx.x, s, start, first, f, e);
+    const bool flag = reinterpret_cast<const uint32_t*>(a.scratch)[blockIdx.x] != 0u;
+    const PngsRecord r = pngs_measure(s, start, first, e.length == 0u, flag);
+    if (threadIdx.x == 0) a.records[blockIdx.x] = r;
+}
+
+__global__ __launch_bounds__(64) void k_pngd_scan(PngdArgs a) {
+    const uint32_t file = blockIdx.x;
+    const egs_png_file f = a.desc[file];
+    const uint32_t expect = (uint32_t)f.height * (1u + (uint32_t)f.width * (uint32_t)f.channels);
+    const uint32_t route = pngs_scan(a.records + f.idat_begin, (uint32_t)f.n_idat, expect);      // idat_begin + n_idat <= the table's length
+    if (threadIdx.x == 0) {
+        a.routes[file] = route;
+        if (a.route_out) a.route_out[file] = route;
+        if (route == PNGS_ROUTE_SEGMENTS) a.status[file] = PNGD_OK;  // (the serial wave, which writes every other status, skips this file)
+    }
+}
+
+__global__ __launch_bounds__(64) void k_pngd_place(PngdArgs a) {
+    __shared__ PngsMem mem;
+    if (a.routes[a.idat[blockIdx.x].file] != PNGS_ROUTE_SEGMENTS) return;      // (uniform)
+    const PngsRecord r = a.records[blockIdx.x];
+    if (r.length == 0u) return;
+    PngsState s;
+    s.m = &mem;
+    uint32_t start;
+    bool first;
+    egs_png_file f;
+    egs_png_idat e;
+    pngd_chunk(a, blockIdx.x, s, start, first, f, e);
+    // aux + length <= the sum of the file's lengths = H (1 + W C): inside the file's inflated data
+    pngs_place(s, start, first, r.length, a.scratch + a.inflate_base + f.inflate_offset + r.aux);
+}
+
 __global__ __launch_bounds__(64) void k_pngd_inflate(PngdArgs a) {
     __shared__ PngiMem mem;
     const uint32_t lane = threadIdx.x, file = blockIdx.x;
+    if (a.routes && a.routes[file] == PNGS_ROUTE_SEGMENTS) return;    // (uniform) the segments of this file are in place
     const egs_png_file f = a.desc[file];
     const uint32_t* flags = reinterpret_cast<const uint32_t*>(a.scratch) + f.idat_begin;
     uint32_t bad = 0xffffffffu;
@@ -185,10 +249,17 @@ size_t egs_png_decode_scratch_bytes(int n_idat, size_t total_stream_bytes, size_
     return egs_align((size_t)n_idat * 4) + egs_align(total_stream_bytes) + egs_align(total_inflate_bytes);
 }
 
-int egs_png_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
-                          const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
-                          uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases) {
-    if (n_files < 1 || n_idat < 1 || phases < 1 || phases > 7) return EGS_ERR_ARG;
+size_t egs_png_decode_scratch_bytes_ex(int n_idat, size_t total_stream_bytes, size_t total_inflate_bytes, int flags) {
+    if (n_idat < 1 || (flags & ~EGS_PNG_SEGMENTS)) return 0;
+    size_t need = egs_png_decode_scratch_bytes(n_idat, total_stream_bytes, total_inflate_bytes);
+    if (flags & EGS_PNG_SEGMENTS) need += egs_align((size_t)n_idat * sizeof(PngsRecord)) + egs_align((size_t)n_idat * 4);
+    return need;
+}
+
+int egs_png_decode_ex(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
+                      const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
+                      uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases, int flags, uint32_t* route) {
+    if (n_files < 1 || n_idat < 1 || phases < 1 || phases > 7 || (flags & ~EGS_PNG_SEGMENTS) || ((uintptr_t)route & 3)) return EGS_ERR_ARG;
     if (n_files > 65535) return EGS_ERR_RANGE;
     if (!files || !desc_host || !desc_device || !idat_host || !idat_device || !out || !status || !scratch) return EGS_ERR_ARG;
     if (((uintptr_t)scratch & 15) || ((uintptr_t)status & 3) || ((uintptr_t)desc_device & 7) || ((uintptr_t)idat_device & 3)) return EGS_ERR_ARG;
@@ -224,22 +295,43 @@ int egs_png_decode_phases(int n_files, const uint8_t* files, size_t files_bytes,
         idat_next = f.idat_begin + (uint32_t)f.n_idat;
     }
     if (idat_next != (uint32_t)n_idat) return EGS_ERR_ARG;
-    const size_t need = egs_png_decode_scratch_bytes(n_idat, stream_total, inflate_total);
+    const size_t need = egs_png_decode_scratch_bytes_ex(n_idat, stream_total, inflate_total, flags);
     if (need > scratch_bytes) return EGS_ERR_ARG;
     PngdArgs a;
     a.files = files; a.desc = desc_device; a.idat = idat_device; a.out = out; a.status = status; a.scratch = (uint8_t*)scratch;
     a.stream_base = (unsigned long long)egs_align((size_t)n_idat * 4);
     a.inflate_base = a.stream_base + (unsigned long long)egs_align(stream_total);
+    a.records = nullptr; a.routes = nullptr; a.route_out = nullptr;
+    if (flags & EGS_PNG_SEGMENTS) {
+        const unsigned long long records_base = a.inflate_base + (unsigned long long)egs_align(inflate_total);
+        a.records = reinterpret_cast<PngsRecord*>((uint8_t*)scratch + records_base);
+        a.routes = reinterpret_cast<uint32_t*>((uint8_t*)scratch + records_base + egs_align((size_t)n_idat * sizeof(PngsRecord)));
+        a.route_out = route;
+    }
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     if (phases & 1) hipLaunchKernelGGL(k_pngd_gather, dim3((unsigned)n_idat), dim3(PNGD_WG), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
+    if ((phases & 2) && (flags & EGS_PNG_SEGMENTS)) {
+        hipLaunchKernelGGL(k_pngd_measure, dim3((unsigned)n_idat), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_pngd_scan, dim3((unsigned)n_files), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_pngd_place, dim3((unsigned)n_idat), dim3(64), 0, st, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
     if (phases & 2) hipLaunchKernelGGL(k_pngd_inflate, dim3((unsigned)n_files), dim3(64), 0, st, a);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (phases & 4) hipLaunchKernelGGL(k_pngd_unfilter, dim3((unsigned)n_files), dim3(64), 0, st, a);
     return (int)hipGetLastError();
+}
+
+int egs_png_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
+                          const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
+                          uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases) {
+    return egs_png_decode_ex(n_files, files, files_bytes, desc_host, desc_device, idat_host, idat_device, n_idat, out, out_bytes, status, scratch,
+                             scratch_bytes, stream, phases, 0, nullptr);
 }
 
 int egs_png_decode(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,

@@ -6,7 +6,7 @@
 //
 // Memory.  PngiMem is the working set (LDS on the device, 39 KiB): the 32 KiB window as a ring, a 1 KiB buffer of the stream, the two
 // code tables (a 10-bit direct table + count per length + the symbols in canonical order: every length up to 15 is reachable), the code
-// lengths.  A match reads the ring, never global memory.  Output leaves through pngi_flush: whole 32-bit words, lane after lane.
+// lengths (PngiMemT<WIN>: png_segments.h decodes one segment with an 8 KiB buffer, 15 KiB in all).  A match reads the ring, never global memory.  Output leaves through pngi_flush: whole 32-bit words, lane after lane.
 //
 // Bounds and termination (the contract, not an afterthought):
 //   * the stream is read at two places.  Every BIT comes through pngi_word: bytes at or past `n` read as zero; pngi_drop counts the bits
@@ -29,6 +29,10 @@
 #else
 #define PNGI_FN static inline
 #endif
+// Every function that takes the state is a template over WIN, the bytes of output the working set keeps (a power of two).  The file
+// inflater is WIN = PNGI_WINDOW, the deflate window as a ring; png_segments.h decodes one independent segment with a smaller WIN that holds
+// the segment whole.
+#define PNGI_T template <uint32_t WIN> PNGI_FN
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PNGI_LANE ((uint32_t)threadIdx.x)
@@ -65,7 +69,6 @@ enum {
 };
 
 #define PNGI_WINDOW 32768u
-#define PNGI_WMASK (PNGI_WINDOW - 1u)
 #define PNGI_FAST_BITS 10
 #define PNGI_FAST (1u << PNGI_FAST_BITS)
 #define PNGI_INBUF 1024u              // bytes of the stream kept in PngiMem
@@ -82,20 +85,21 @@ struct PngiCode {
     uint16_t offs[16];                // (the fill positions while sym[] is built)
 };
 
-struct PngiMem {
-    uint32_t win32[PNGI_WINDOW / 4];  // the window, a ring: byte j of the output lives at j & PNGI_WMASK
+template <uint32_t WIN> struct PngiMemT {
+    uint32_t win32[WIN / 4];          // the window, a ring: byte j of the output lives at j & (WIN - 1)
     uint32_t inbuf[PNGI_INBUF / 4];
     PngiCode lit, dist;               // (dist holds the code-length code while a dynamic block's header is read)
     uint8_t lens[320];
     uint8_t cl[20];
 };
+typedef PngiMemT<PNGI_WINDOW> PngiMem;
 
-struct PngiState {
+template <uint32_t WIN> struct PngiStateT {
     const uint8_t* in;                // the zlib stream, 4-byte aligned; readable up to n rounded up to 4
     uint32_t n;
     uint8_t* out;                     // 4-byte aligned, `expect` bytes
     uint32_t expect;
-    PngiMem* m;
+    PngiMemT<WIN>* m;
     uint64_t bitbuf;
     uint32_t bitcnt, pos;             // bits in bitbuf; the stream byte the next word comes from (consumed bits: 8 pos - bitcnt)
     uint32_t in_base;                 // first stream byte inbuf holds (device)
@@ -104,15 +108,16 @@ struct PngiState {
     uint32_t status;
     uint64_t iters;
 };
+typedef PngiStateT<PNGI_WINDOW> PngiState;
 
-PNGI_FN void pngi_fail(PngiState& s, uint32_t code) {
+PNGI_T void pngi_fail(PngiStateT<WIN>& s, uint32_t code) {
     if (!s.status) s.status = code;
 }
 
-PNGI_FN uint8_t* pngi_win(PngiState& s) { return reinterpret_cast<uint8_t*>(s.m->win32); }
+PNGI_T uint8_t* pngi_win(PngiStateT<WIN>& s) { return reinterpret_cast<uint8_t*>(s.m->win32); }
 
 // ---- the one fetch: four stream bytes at `pos`, little-endian, zero at and past n ---------------------------------------------------------
-PNGI_FN uint32_t pngi_word(PngiState& s, uint32_t pos) {
+PNGI_T uint32_t pngi_word(PngiStateT<WIN>& s, uint32_t pos) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t a = pos & ~3u;
     if (a < s.in_base || a + 8u > s.in_base + PNGI_INBUF) {           // (uniform: every lane holds the same pos)
@@ -141,7 +146,7 @@ PNGI_FN uint32_t pngi_word(PngiState& s, uint32_t pos) {
 #endif
 }
 
-PNGI_FN void pngi_need(PngiState& s, uint32_t k) {                    // k <= 32
+PNGI_T void pngi_need(PngiStateT<WIN>& s, uint32_t k) {                    // k <= 32
     if (s.bitcnt < k) {
         s.bitbuf |= (uint64_t)pngi_word(s, s.pos) << s.bitcnt;        // bitcnt < 32: the word fits
         s.pos += 4u;
@@ -149,13 +154,13 @@ PNGI_FN void pngi_need(PngiState& s, uint32_t k) {                    // k <= 32
     }
 }
 
-PNGI_FN void pngi_drop(PngiState& s, uint32_t k) {                    // k <= bitcnt
+PNGI_T void pngi_drop(PngiStateT<WIN>& s, uint32_t k) {                    // k <= bitcnt
     s.bitbuf >>= k;
     s.bitcnt -= k;
     if (8ull * s.pos - s.bitcnt > 8ull * s.n) pngi_fail(s, PNGD_TRUNCATED);
 }
 
-PNGI_FN uint32_t pngi_bits(PngiState& s, uint32_t k) {                // k <= 16
+PNGI_T uint32_t pngi_bits(PngiStateT<WIN>& s, uint32_t k) {                // k <= 16
     if (!k) return 0;
     pngi_need(s, k);
     const uint32_t v = (uint32_t)s.bitbuf & ((1u << k) - 1u);
@@ -173,7 +178,7 @@ PNGI_FN uint32_t pngi_sum(uint32_t v) {
 
 // [flushed, outpos) leaves the ring for `out` in pieces of at most PNGI_FLUSH bytes, whole words unless `all`; the Adler pair follows.
 // A piece of m <= 4096 bytes: A = sum b_j, B = sum (m - j) b_j <= 255 * 4096 * 4097 / 2 < 2^32 -- 32-bit sums hold.
-PNGI_FN void pngi_flush(PngiState& s, bool all) {
+PNGI_T void pngi_flush(PngiStateT<WIN>& s, bool all) {
     PNGI_SYNC();
     const uint32_t upto = all ? s.outpos : s.outpos & ~3u;
     const uint8_t* win = pngi_win(s);
@@ -182,7 +187,7 @@ PNGI_FN void pngi_flush(PngiState& s, bool all) {
         const uint32_t f1 = upto - f0 > PNGI_FLUSH ? f0 + PNGI_FLUSH : upto;
         uint32_t A = 0, B = 0;
         for (uint32_t j = f0 + PNGI_LANE; j < f1; j += PNGI_LANES) {
-            const uint32_t b = win[j & PNGI_WMASK];
+            const uint32_t b = win[j & (WIN - 1u)];
             A += b;
             B += (f1 - j) * b;
         }
@@ -193,40 +198,45 @@ PNGI_FN void pngi_flush(PngiState& s, bool all) {
         const uint32_t nw = (f1 - f0) >> 2;                           // f0 is a multiple of 4: flushed only ends elsewhere after `all`
         uint32_t* out32 = reinterpret_cast<uint32_t*>(s.out);
         for (uint32_t w = PNGI_LANE; w < nw; w += PNGI_LANES)
-            out32[(f0 >> 2) + w] = s.m->win32[((f0 >> 2) + w) & (PNGI_WINDOW / 4u - 1u)];   // f0 + 4 w + 3 < f1 <= outpos <= expect
-        for (uint32_t j = f0 + 4u * nw + PNGI_LANE; j < f1; j += PNGI_LANES) s.out[j] = win[j & PNGI_WMASK];
+            out32[(f0 >> 2) + w] = s.m->win32[((f0 >> 2) + w) & (WIN / 4u - 1u)];   // f0 + 4 w + 3 < f1 <= outpos <= expect
+        for (uint32_t j = f0 + 4u * nw + PNGI_LANE; j < f1; j += PNGI_LANES) s.out[j] = win[j & (WIN - 1u)];
         s.flushed = f1;
     }
     PNGI_SYNC();
 }
 
-PNGI_FN void pngi_emit_literal(PngiState& s, uint32_t b) {
+// pending output leaves at PNGI_FLUSH bytes -- of the ring.  A smaller WIN holds its whole output (expect <= WIN) until its caller takes it.
+PNGI_T void pngi_pending(PngiStateT<WIN>& s) {
+    if (WIN >= PNGI_WINDOW && s.outpos - s.flushed >= PNGI_FLUSH) pngi_flush(s, false);
+}
+
+PNGI_T void pngi_emit_literal(PngiStateT<WIN>& s, uint32_t b) {
     if (s.outpos >= s.expect) { pngi_fail(s, PNGD_TOO_MANY); return; }
-    pngi_win(s)[s.outpos & PNGI_WMASK] = (uint8_t)b;                  // (every lane the same byte)
+    pngi_win(s)[s.outpos & (WIN - 1u)] = (uint8_t)b;                  // (every lane the same byte)
     s.outpos++;
-    if (s.outpos - s.flushed >= PNGI_FLUSH) pngi_flush(s, false);
+    pngi_pending(s);
 }
 
 // len 3 .. 258, dist 1 .. 32768.  Byte k of the match is byte k % dist of the dist bytes before it: sources lie before outpos, targets at
 // or behind it (at dist = 32768 a lane's source and target share a ring slot: it reads, then writes).
-PNGI_FN void pngi_emit_match(PngiState& s, uint32_t len, uint32_t dist) {
+PNGI_T void pngi_emit_match(PngiStateT<WIN>& s, uint32_t len, uint32_t dist) {
     if (dist > s.outpos) { pngi_fail(s, PNGD_DISTANCE); return; }
     if (len > s.expect - s.outpos) { pngi_fail(s, PNGD_TOO_MANY); return; }
     PNGI_SYNC();                                                      // the bytes other lanes copied are in the ring
     uint8_t* win = pngi_win(s);
     const uint32_t from = s.outpos - dist;
     for (uint32_t k = PNGI_LANE; k < len; k += PNGI_LANES) {
-        const uint32_t v = win[(from + k % dist) & PNGI_WMASK];
-        win[(s.outpos + k) & PNGI_WMASK] = (uint8_t)v;
+        const uint32_t v = win[(from + k % dist) & (WIN - 1u)];
+        win[(s.outpos + k) & (WIN - 1u)] = (uint8_t)v;
     }
     s.outpos += len;
-    if (s.outpos - s.flushed >= PNGI_FLUSH) pngi_flush(s, false);
+    pngi_pending(s);
 }
 
 // ---- code tables ----------------------------------------------------------------------------------------------------------------------------
 // lens[0 .. n) -> code.  false (and the status) for an over-subscribed set, and for an incomplete one unless `lone` allows what zlib
 // allows: a single code of length 1, or (lone == 2, the distance set) no code at all.
-PNGI_FN bool pngi_build(PngiState& s, PngiCode& c, const uint8_t* lens, uint32_t n, int lone) {
+PNGI_T bool pngi_build(PngiStateT<WIN>& s, PngiCode& c, const uint8_t* lens, uint32_t n, int lone) {
     PNGI_SYNC();
     if (PNGI_LANE == 0) {
         for (int l = 0; l < 16; l++) c.count[l] = 0;
@@ -267,7 +277,7 @@ PNGI_FN bool pngi_build(PngiState& s, PngiCode& c, const uint8_t* lens, uint32_t
 }
 
 // the next symbol of `c`, or -1 (PNGD_SYMBOL) when no code owns the bits
-PNGI_FN int pngi_decode(PngiState& s, const PngiCode& c) {
+PNGI_T int pngi_decode(PngiStateT<WIN>& s, const PngiCode& c) {
     pngi_need(s, 15);
     const uint32_t v = (uint32_t)s.bitbuf;
     const uint32_t e = PNGI_UNI(c.fast[v & (PNGI_FAST - 1u)]);
@@ -289,7 +299,7 @@ PNGI_FN int pngi_decode(PngiState& s, const PngiCode& c) {
 }
 
 // ---- blocks -------------------------------------------------------------------------------------------------------------------------------
-PNGI_FN void pngi_stored(PngiState& s) {
+PNGI_T void pngi_stored(PngiStateT<WIN>& s) {
     pngi_drop(s, s.bitcnt & 7u);
     const uint32_t len = pngi_bits(s, 16), nlen = pngi_bits(s, 16);
     if (s.status) return;
@@ -302,14 +312,14 @@ PNGI_FN void pngi_stored(PngiState& s) {
     while (rest) {                                                    // each turn consumes >= 1 stream byte
         s.iters++;
         const uint32_t m = rest < 2048u ? rest : 2048u;
-        for (uint32_t k = PNGI_LANE; k < m; k += PNGI_LANES) win[(s.outpos + k) & PNGI_WMASK] = s.in[bp + k];      // bp + k < bp + rest <= n
+        for (uint32_t k = PNGI_LANE; k < m; k += PNGI_LANES) win[(s.outpos + k) & (WIN - 1u)] = s.in[bp + k];      // bp + k < bp + rest <= n
         s.outpos += m; bp += m; rest -= m;
-        if (s.outpos - s.flushed >= PNGI_FLUSH) pngi_flush(s, false);
+        pngi_pending(s);
     }
     s.pos = bp; s.bitbuf = 0; s.bitcnt = 0;
 }
 
-PNGI_FN void pngi_codes(PngiState& s) {
+PNGI_T void pngi_codes(PngiStateT<WIN>& s) {
     // every turn consumes at least one bit (every code has a length >= 1) or sets the status, and the status ends the loop
     while (!s.status) {
         s.iters++;
@@ -334,7 +344,7 @@ PNGI_FN void pngi_codes(PngiState& s) {
     }
 }
 
-PNGI_FN bool pngi_fixed_tables(PngiState& s) {
+PNGI_T bool pngi_fixed_tables(PngiStateT<WIN>& s) {
     PNGI_SYNC();
     for (uint32_t i = PNGI_LANE; i < 320u; i += PNGI_LANES)
         s.m->lens[i] = (uint8_t)(i < 144u ? 8 : i < 256u ? 9 : i < 280u ? 7 : i < 288u ? 8 : 5);      // 288 literal/length, 32 distance codes of 5 bits
@@ -342,7 +352,7 @@ PNGI_FN bool pngi_fixed_tables(PngiState& s) {
     return pngi_build(s, s.m->lit, s.m->lens, 288, 0) && pngi_build(s, s.m->dist, s.m->lens + 288, 32, 0);
 }
 
-PNGI_FN bool pngi_dynamic_tables(PngiState& s) {
+PNGI_T bool pngi_dynamic_tables(PngiStateT<WIN>& s) {
     const uint32_t nlen = pngi_bits(s, 5) + 257u, ndist = pngi_bits(s, 5) + 1u, ncode = pngi_bits(s, 4) + 4u;
     if (s.status) return false;
     if (nlen > 286u || ndist > 30u) { pngi_fail(s, PNGD_SYMBOL); return false; }
@@ -378,23 +388,26 @@ PNGI_FN bool pngi_dynamic_tables(PngiState& s) {
     return pngi_build(s, s.m->lit, s.m->lens, nlen, 1) && pngi_build(s, s.m->dist, s.m->lens + nlen, ndist, 2);
 }
 
+// One block, from its header bits -> BFINAL.  It consumes its 3 header bits or sets the status; see the loops inside for theirs.
+PNGI_T bool pngi_block(PngiStateT<WIN>& s) {
+    s.iters++;
+    const bool last = pngi_bits(s, 1) != 0;
+    const uint32_t type = pngi_bits(s, 2);
+    if (s.status) return last;
+    if (type == 0) pngi_stored(s);
+    else if (type == 3) pngi_fail(s, PNGD_BLOCK_TYPE);
+    else if (type == 1 ? pngi_fixed_tables(s) : pngi_dynamic_tables(s)) pngi_codes(s);
+    return last;
+}
+
 // The whole stream.  s.in / n / out / expect / m are set by the caller; -> s.status (0: `expect` bytes are in `out`).
-PNGI_FN void pngi_inflate(PngiState& s) {
+PNGI_T void pngi_inflate(PngiStateT<WIN>& s) {
     s.bitbuf = 0; s.bitcnt = 0; s.pos = 0; s.in_base = 0x80000000u;
     s.outpos = 0; s.flushed = 0; s.adler_a = 1; s.adler_b = 0; s.status = 0; s.iters = 0;
     const uint32_t cmf = pngi_bits(s, 8), flg = pngi_bits(s, 8);
     if (!s.status && ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 32u))) pngi_fail(s, PNGD_ZLIB_HEADER);
     bool last = false;
-    // every block consumes its 3 header bits or sets the status; see the loops inside for theirs
-    while (!last && !s.status) {
-        s.iters++;
-        last = pngi_bits(s, 1) != 0;
-        const uint32_t type = pngi_bits(s, 2);
-        if (s.status) break;
-        if (type == 0) pngi_stored(s);
-        else if (type == 3) pngi_fail(s, PNGD_BLOCK_TYPE);
-        else if (type == 1 ? pngi_fixed_tables(s) : pngi_dynamic_tables(s)) pngi_codes(s);
-    }
+    while (!last && !s.status) last = pngi_block(s);
     if (s.status) return;
     pngi_flush(s, true);
     pngi_drop(s, s.bitcnt & 7u);

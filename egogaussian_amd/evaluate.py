@@ -151,14 +151,15 @@ class EvalPass(CapturedSweep):
         return out
 
 
-def metrics_from_files(renders, gts, hands, lpips=None, device="cuda", batch=32):
+def metrics_from_files(renders, gts, hands, lpips=None, device="cuda", batch=32, segments=False):
     """The device route of the reference's calculate_metric (its trainers/eval_metric.py:129-175): the figures of a directory of 8-bit PNG
     files -- renders[k], gts[k] (RGB) and hands[k] (1 or 3 channels, channel 0 is used; the file render_results wrote: 255 where the pixel
     counts) -- paths or bytes.  The files go up as they are and are decoded on the device (png.PngReader); keep = (hand byte / 255) >= 0.5,
     the images are byte / 255 as planar float tensors, and the same kernels as EvalPass measure them (fused.eval_metrics and, with
     lpips=lpips.LPIPS(...), csrc/lpips.hip) -- an EvalPass sweep that saved these files reports the same sse, ssim_sum and LPIPS rows.
     A hand file with a byte other than 0 / 255 raises ValueError: masks are binary by contract (include/egs_raster.h egs_eval_metrics).
-    One read of the decoder's status words per batch of files, one of the hand check, one of the rows.
+    One read of the decoder's status words per batch of files, one of the hand check, one of the rows.  segments=True decodes with the
+    segmented route (png.PngReader): the files EvalPass.run(save_renders=) wrote take it; the rows are the same either way.
     -> dict(ssim, psnr[, lpips]: float64[F]; sse: int64[F]; ssim_sum: float64[F]; rows: [(ssim, psnr[, lpips])] per file; means: the same
     tuple of plain means, in the reference's order SSIM, PSNR, LPIPS)."""
     from . import png as _png
@@ -167,7 +168,7 @@ def metrics_from_files(renders, gts, hands, lpips=None, device="cuda", batch=32)
     if F < 1 or len(gts) != F or len(hands) != F:
         raise ValueError(f"metrics_from_files: {F} renders, {len(gts)} ground truths and {len(hands)} hand masks; one of each per frame, at least one")
     dev = torch.device(device)
-    reader = _png.PngReader(dev, batch=batch)
+    reader = _png.PngReader(dev, batch=batch, segments=segments)
     try:
         arrays = reader.read(renders + gts + hands)
     except ValueError as e:

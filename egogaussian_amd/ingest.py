@@ -229,12 +229,15 @@ class FrameIngest:
         for plane, slot, t in groups:
             self._launch(i, plane, slot, t)
 
-    def put_files(self, i, cam, image=None, hand_mask=None, obj_mask=None, accum_R=None, accum_T=None, pose_rows=None):
+    def put_files(self, i, cam, image=None, hand_mask=None, obj_mask=None, accum_R=None, accum_T=None, pose_rows=None, segments=False):
         """put() with 8-bit PNG files -- paths or bytes -- in place of the arrays.  The sizes and channel counts are checked from IHDR
         against src_hw before any device work (png.parse; a mode this path does not take is refused there); the files are then uploaded as
         they are and decoded on the device on the store's stream, in front of the ingest launches.  Nothing is read back but the decoder's
         status words, once; a file the device refuses raises ValueError and the store is left as it was.  The store ends up bit-identical
-        to put() with the decoded arrays."""
+        to put() with the decoded arrays.  segments=True decodes with the segmented route (png.PngReader: a wave per IDAT chunk for the files
+        that allow it, e.g. this project's own; the same store either way)."""
+        from . import png as _png
+        self._reader.flags = (self._reader.flags & ~_png.SEGMENTS) | (_png.SEGMENTS if segments else 0)
         given = [(name, f) for name, f in (("obj_mask", obj_mask), ("hand_mask", hand_mask), ("image", image)) if f is not None]
         who = ", ".join(f"file {k} is {name}" for k, (name, _) in enumerate(given))
         try:

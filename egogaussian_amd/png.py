@@ -313,6 +313,21 @@ _FILE = np.dtype([("width", "<i4"), ("height", "<i4"), ("channels", "<i4"), ("n_
                   ("file_offset", "<u8"), ("file_bytes", "<u8"), ("stream_offset", "<u8"), ("inflate_offset", "<u8"), ("out_offset", "<u8")])      # egs_png_file
 _IDAT = np.dtype([("file", "<u4"), ("src", "<u4"), ("length", "<u4"), ("dst", "<u4")])                                                             # egs_png_idat
 _CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
+# egs_png_decode_ex: the flags, and the route words with EGS_PNG_SEGMENTS (1: the file's IDAT chunks were inflated as independent segments, a
+# wave each; else 0 | reason << 8: why the serial wave inflated it)
+SEGMENTS = 1
+SEGMENT_MAX = 8192
+ROUTE_SEGMENTS = 1
+ROUTE_REASON = {0: "the segmented route was not asked for", 1: "chunk 0 is shorter than the zlib header", 2: "a chunk does not end on a block end",
+                3: "a distance before the start of its segment", 4: f"a segment of more than {SEGMENT_MAX} bytes",
+                5: "the final block or the Adler-32 is not at the end of the last non-empty chunk", 6: "the segments' lengths do not sum to H (1 + W C)",
+                7: "the combined Adler-32", 8: "an inflate error inside a segment", 9: "an IDAT chunk's CRC-32"}
+
+
+def route_text(word):
+    """What a route word of egs_png_decode_ex says."""
+    word = int(word)
+    return "segments" if word == ROUTE_SEGMENTS else "serial: " + ROUTE_REASON.get(word >> 8, f"route {word}")
 
 
 def status_text(word):
@@ -423,22 +438,27 @@ class PngReader:
     """8-bit PNG files -> device uint8 [h, w, C] tensors: the mirror of PngWriter.  Owns the pinned staging, the device buffer the files and
     their tables are uploaded to, the scratch, the outputs and the status words; each grows to what the largest batch so far needed
     (max_file_bytes / max_pixels reserve it up front).  Per batch of at most `batch` files: the host walks the chunks (parse), ONE upload,
-    three launches, ONE read of the status words.  guard > 0 (a multiple of 256) is for tests: every byte of the device buffers that a
+    three launches, ONE read of the status words.  segments=True asks for the segmented route (egs_png_decode_ex with EGS_PNG_SEGMENTS: a file
+    whose IDAT chunks are independent deflate segments -- the device encoder's files, zlib with a full flush per chunk -- is inflated by one
+    wave per chunk, every other file by the serial wave as before; statuses and pixels are the same either way); last_route then holds the
+    route word per file of the last read() (route_text), read with the status words in the same one read.  guard > 0 (a multiple of 256) is for tests: every byte of the device buffers that a
     call is not entitled to -- `guard` bytes before and behind each buffer, the gaps between the output slots, and everything behind the
     status words, the scratch bytes and the outputs IN USE up to the end of their allocations -- holds 0xA5 before the launches, and
     check_guards() says whether all of it still does."""
     GUARD_BYTE = 0xA5
 
-    def __init__(self, device, batch=32, max_file_bytes=0, max_pixels=0, guard=0):
+    def __init__(self, device, batch=32, max_file_bytes=0, max_pixels=0, guard=0, segments=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError(f"PngReader: the PNG decoder has no CPU path (device {self.device}); png.decode is the host reader")
         self.batch, self.guard = int(batch), int(guard)
+        self.flags = SEGMENTS if segments else 0
         if self.batch < 1 or self.batch > 65535 or self.guard < 0 or self.guard % 256:
             raise ValueError("PngReader: batch of 1 .. 65535, guard a multiple of 256")
         self._dev, self._pin = {}, None
         self.host_reads = 0                                             # reads of the status words (one per batch)
         self.last_status, self.last_results = [], []                    # of the last read(): a refused batch leaves them to look at
+        self.last_route = []                                            # with segments=True: the route word per file (else zeros)
         self._slack_ok, self._gaps = True, []
         if max_file_bytes or max_pixels:
             self._pinned(self.batch * (_up(int(max_file_bytes), 16) + 4096))
@@ -529,21 +549,30 @@ class PngReader:
                 host[at:at + len(b)] = np.frombuffer(b, dtype=np.uint8)
             blob = self._buffer("blob", up_bytes)
             blob[:up_bytes].copy_(pin[:up_bytes], non_blocking=True)
-            need = int(lib.egs_png_decode_scratch_bytes(n_idat, p["stream_bytes"], p["inflate_bytes"]))
+            routed = bool(self.flags & SEGMENTS)
+            need = int(lib.egs_png_decode_scratch_bytes_ex(n_idat, p["stream_bytes"], p["inflate_bytes"], self.flags) if self.flags else
+                       lib.egs_png_decode_scratch_bytes(n_idat, p["stream_bytes"], p["inflate_bytes"]))
             scratch = self._buffer("scratch", need)
-            status = self._buffer("status", 4 * self.batch)
+            status = self._buffer("status", 8 * self.batch)             # the status words, then (segments) the route words: one read
+            words_bytes = 8 * n if routed else 4 * n
             base = int(whole["desc"]["out_offset"][lo])                  # this batch's slots inside the call's output buffer
             self.last_call = (n, blob.data_ptr() + t_desc + t_idat, p["files_bytes"], pin.data_ptr(), blob.data_ptr(), pin.data_ptr() + t_desc,
                               blob.data_ptr() + t_desc, n_idat, out.data_ptr() + base, p["out_bytes"], status.data_ptr(), scratch.data_ptr(), need)
+            self.last_route_ptr = status.data_ptr() + 4 * n if routed else None
             if g0:                                                      # everything behind the bytes in use holds the guard byte
-                status[4 * n:].fill_(self.GUARD_BYTE)
+                status[words_bytes:].fill_(self.GUARD_BYTE)
                 scratch[need:].fill_(self.GUARD_BYTE)
             with _hip.device_ctx(self.device):
-                _lib.check(lib.egs_png_decode(*self.last_call, _hip.stream_of(self.device)))
-            words = status[:4 * n].view(torch.int32).cpu().tolist()     # (synchronises: the staging may be refilled)
+                if self.flags:
+                    _lib.check(lib.egs_png_decode_ex(*self.last_call, _hip.stream_of(self.device), 7, self.flags,
+                                                     status.data_ptr() + 4 * n if routed else None))
+                else:
+                    _lib.check(lib.egs_png_decode(*self.last_call, _hip.stream_of(self.device)))
+            words = status[:words_bytes].view(torch.int32).cpu().tolist()      # (synchronises: the staging may be refilled)
+            words, routes = words[:n], [r & 0xFFFFFFFF for r in words[n:]] if routed else [0] * n
             self.host_reads += 1
             if g0:
-                self._slack_ok = self._slack_ok and self._intact(status[4 * n:]) and self._intact(scratch[need:])
+                self._slack_ok = self._slack_ok and self._intact(status[words_bytes:]) and self._intact(scratch[need:])
             for k, (d, w) in enumerate(zip(p["desc"], words)):
                 W, H, C = int(d["width"]), int(d["height"]), int(d["channels"])
                 o = base + int(d["out_offset"])
@@ -553,12 +582,14 @@ class PngReader:
                 if w:
                     failures.append(f"{names[lo + k]}: {status_text(w & 0xFFFFFFFF)} (status {w & 0xFFFFFFFF})")
             self.last_status = (self.last_status if lo else []) + [w & 0xFFFFFFFF for w in words]
+            self.last_route = (self.last_route if lo else []) + routes
         self.last_results = results
         if failures:
             raise ValueError("PngReader.read: " + "; ".join(failures))
         return results
 
 
-def decode_device(file_bytes, device="cuda"):
-    """One file (bytes or a path) -> device uint8 [h, w, C], by the kernels.  (A reader of many files keeps a PngReader.)"""
-    return PngReader(device, batch=1).read([file_bytes])[0].clone()
+def decode_device(file_bytes, device="cuda", segments=False):
+    """One file (bytes or a path) -> device uint8 [h, w, C], by the kernels; segments as PngReader takes it.  (A reader of many files
+    keeps a PngReader.)"""
+    return PngReader(device, batch=1, segments=segments).read([file_bytes])[0].clone()

@@ -770,6 +770,39 @@ int egs_png_decode(int n_files, const uint8_t* files /*device*/, size_t files_by
 int egs_png_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
                           const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
                           uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases);
+/*      The segmented route (added within ABI 6: new entries only; egs_png_decode and egs_png_decode_phases are unchanged).
+ *      The files egs_png_encode writes keep every row segment in an IDAT chunk of its own, ending on a byte boundary with the empty stored
+ *      block of a full flush: such chunks inflate independently.  With EGS_PNG_SEGMENTS in `flags` the entry decides PER FILE, on the device,
+ *      from the stream itself, whether the file's IDAT chunks are such segments, and inflates an accepted file with one wave per chunk.  The
+ *      route only ever accepts: a file it does not accept is inflated by the serial wave of egs_png_decode in the same call and that wave's
+ *      status word stands, so statuses, the CRC word and "verdicts equal zlib's" are what they are without the flag.  Accepted when ALL hold
+ *      (the argument that such a file is one the serial inflater accepts with the same bytes is in csrc/png_segments.h):
+ *        no IDAT CRC fails; chunk 0 holds at least the 2-byte zlib header (a valid one); every chunk, read from its first bit, is a sequence
+ *        of whole deflate blocks ending exactly at its last bit (an empty chunk is a segment without blocks); every block is non-final but
+ *        the last block of the last non-empty chunk, which is final and is followed, after byte alignment, by exactly the four Adler-32
+ *        bytes and the chunk's end; no match reaches before the first byte its own segment produced; no segment produces more than
+ *        EGS_PNG_SEGMENT_MAX bytes; the segments' lengths sum to H (1 + W C); their Adler-32 values combined in order equal the trailer.
+ *      Launches with the flag, whatever the files hold (no allocation, no synchronisation, ordered by launch boundaries only; can be
+ *      captured): gather + CRC; measure, one wave per chunk (a speculative decode -> a 16-byte record: length, Adler-32, reason);
+ *      scan, one wave per file (the rules above, the offsets, the route word); place, one wave per chunk (exits at once for files not
+ *      accepted, else decodes again straight into the inflated data: bytes at a segment's unaligned head and tail, words in between);
+ *      the serial inflate, skipping accepted files; unfilter.  phases bit 2 covers the four inflate launches.
+ *      route[i] (device, written only with EGS_PNG_SEGMENTS; may be NULL): 1 when the segmented route decoded file i, else 0 | reason << 8 --
+ *          1  chunk 0 shorter than the zlib header             4  a segment of more than EGS_PNG_SEGMENT_MAX bytes     7  the combined Adler-32
+ *          2  a chunk does not end on a block end              5  the final block or the trailer is not where the       8  any other inflate error inside a segment
+ *          3  a distance before the start of its segment          rule above puts them                                  9  an IDAT CRC (status says which)
+ *                                                              6  the lengths do not sum to H (1 + W C)
+ *      flags = 0: exactly the launches and bytes of egs_png_decode_phases (route is not touched).  EGS_ERR_ARG before any device work:
+ *      everything egs_png_decode_phases refuses, a bit of `flags` that is not defined, a route that is not 4-byte aligned, a scratch
+ *      smaller than egs_png_decode_scratch_bytes_ex(..., flags): with EGS_PNG_SEGMENTS the three areas of egs_png_decode_scratch_bytes at
+ *      the same offsets, then 16 n_idat record bytes and 4 n_idat route bytes, each 256-aligned.  0 for n_idat < 1 or an undefined flag. */
+#define EGS_PNG_SEGMENTS         1
+#define EGS_PNG_SEGMENT_MAX      8192      /* bytes one segment may produce: the segment buffer in LDS (ten workgroups per CU) */
+size_t egs_png_decode_scratch_bytes_ex(int n_idat, size_t total_stream_bytes, size_t total_inflate_bytes, int flags);
+int egs_png_decode_ex(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
+                      const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
+                      uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases, int flags,
+                      uint32_t* route /*device [n_files] out, or NULL*/);
 
 /* ---- the object pose sequence on the device (added within ABI 6: new entries only).
  *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the

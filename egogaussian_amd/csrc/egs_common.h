@@ -171,7 +171,7 @@ struct EgsScene {
     const float* scales; float mod; const float* rots; const float* cov3D; int act;
 };
 // Spherical harmonics as launches of their own (M > 1 coefficients, or DC / rest given as two arrays; rows of 12 M bytes: the wave-tiled
-// kernels of preprocess.hip).  The preprocess kernels are then given shs = NULL: the forward leaves the record's colour open, the backward
+// kernels of sh.hip).  The preprocess kernels are then given shs = NULL: the forward leaves the record's colour open, the backward
 // leaves dL/dSH and the view-direction part of dL/dmean3D to egs_launch_sh_backward (which must run after it).
 static inline bool egs_sh_apart(const EgsScene& sc) { return sc.shs && (sc.M > 1 || sc.shs_rest); }
 // Where a backward writes (HOST record; members may be NULL as include/egs_raster.h says), and the densification statistics it updates

@@ -1,4 +1,4 @@
-"""Float64 anchor of the spherical-harmonics kernels (csrc/preprocess.hip: k_sh_forward, k_sh_backward, k_sh16_forward<CAT|SPLIT>,
+"""Float64 anchor of the spherical-harmonics kernels (csrc/sh.hip: k_sh_forward, k_sh_backward, k_sh16_forward<CAT|SPLIT>,
 k_sh16_backward<CAT|SPLIT>): the case builder and the table of cases, the Python mirror of the dispatch rule, the float64 reference written
 from the definition (the real SH polynomials as monomial tables), the float32 CPU yardstick with its deliberately wrong variants, and the
 checks themselves.  tests/test_gpu_sh.py hands the kernels' outputs to these checks, tests/test_sh_anchor_cpu.py the yardstick and the
@@ -230,7 +230,7 @@ def get_case(key):
 
 # ------------------------------------------------------- the dispatch rule, mirrored ---------------------------------------------------
 def expected_path(case):
-    """-> (kernel family, {(direction, loader)}) the launches of this case take (csrc/preprocess.hip egs_launch_sh_forward / _backward).
+    """-> (kernel family, {(direction, loader)}) the launches of this case take (csrc/sh.hip egs_launch_sh_forward / _backward).
     family: 'inline' (M = 1: no launch of its own), 'sh16-cat' / 'sh16-split' (M = 16 and every base 16-byte aligned), else 'generic'.
     loader, per 64-row block and array: 'vector' iff the block's base is 16-byte aligned, (nvalid rw) % 4 == 0 and rw <= 48 (a store has no
     limit on rw); else 'tail' -- the generic kernels' scalar loop, the ragged tails of SPLIT (`lane < 3`), the `row < nvalid` guard of CAT

@@ -1,4 +1,4 @@
-"""GPU: the spherical-harmonics kernels (csrc/preprocess.hip k_sh_forward / k_sh_backward / k_sh16_forward / k_sh16_backward, CAT and SPLIT)
+"""GPU: the spherical-harmonics kernels (csrc/sh.hip k_sh_forward / k_sh_backward / k_sh16_forward / k_sh16_backward, CAT and SPLIT)
 against float64 over every layout, active degree and visibility pattern of tests/sh_anchor.py's table: one 32 x 32 forward and
 deterministic backward per case through _C.rasterize_gaussians(_backward), and the same geometry once more with the record's colours as
 colors_precomp (the twin), whose dL/dmeans3D is the projection term alone.  Every gradient array is carved from a NaN-filled buffer for

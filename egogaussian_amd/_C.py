@@ -174,6 +174,15 @@ def sort_plan(P, W, H, capacity=None, debug=0, retried=False):
     return int(_lib.load().egs_forward_sort_plan(int(P), int(capacity), int(W), int(H), flags))
 
 
+def bin_geometry(P, W, H, debug=0):
+    """The launch geometry of the tile bucketing of a forward of this size with these flags, as a dict (include/egs_raster.h
+    egs_forward_bin_geometry; host arithmetic, no device work): n_tiles, gx, nblocks, stride, n_chunks, gpr, cull, use_map, groups_per_block,
+    rounds, prefixed, can_fuse, lds."""
+    q = _lib.BinGeometry()
+    _lib.check(_lib.load().egs_forward_bin_geometry(int(P), int(W), int(H), call_flags(debug), C.byref(q)))
+    return {n: int(getattr(q, n)) for n, _ in _lib.BinGeometry._fields_}
+
+
 def last_instance_count(device=None, P=None):
     """R (rectangle instances) of the most recent EAGER forward on `device`, summed from the page-locked per-workgroup counts
     that call copied out.  Captured forwards skip the copy; they are checked through set_running_max / stats["total_view"]."""

@@ -196,6 +196,25 @@ int egs_forward_sort_plan(int P, int64_t capacity, int width, int height, int fl
     if (P <= 0 || capacity <= 0 || width <= 0 || height <= 0) return 0;
     return egs_sort_plan(P, capacity, (int)egs_tiles(width, height), flags);
 }
+// (the rules themselves: binning.hip egs_bin_geometry / egs_table_scan_prefixed, bin_walk.h bin_groups_per_block, preprocess.hip egs_can_fuse_count)
+int egs_forward_bin_geometry(int P, int width, int height, int flags, egs_bin_geometry_info* out) {
+    if (!out) return EGS_ERR_ARG;
+    if (int rc = check_dims(P, width, height)) return rc;
+    const int cull = cull_on(flags);
+    const EgsBinGeometry q = egs_bin_geometry(P, width, height, cull);
+    egs_bin_geometry_info o = {};
+    o.n_tiles = q.n_tiles; o.gx = q.gx;
+    if (P > 0) {
+        o.nblocks = (int32_t)q.nblocks; o.stride = (int32_t)q.stride; o.n_chunks = (int32_t)q.n_chunks;
+        o.gpr = q.gpr; o.cull = q.cull; o.use_map = q.use_map; o.lds = (int64_t)q.lds;
+        o.groups_per_block = (int32_t)egs_bin_groups_per_block(P);
+        o.rounds = (o.groups_per_block + q.gpr - 1) / q.gpr;
+        o.prefixed = egs_table_scan_prefixed(q.n_chunks);
+        o.can_fuse = egs_can_fuse_count(P, width, height, cull) ? 1 : 0;
+    }
+    *out = o;
+    return 0;
+}
 
 const char* egs_error_string(int code) {
     switch (code) {

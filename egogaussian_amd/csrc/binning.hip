@@ -319,6 +319,8 @@ hipError_t egs_launch_scan_u32(const uint32_t* in, uint32_t* out, size_t n, int 
 #endif
 int egs_bin_gpb(int P) { const int k = (P + 256 * EGS_BIN_TARGET_BLOCKS - 1) / (256 * EGS_BIN_TARGET_BLOCKS); return 256 * (k > 1 ? k : 1); }      // whole 256-Gaussian blocks (bin_walk.h)
 uint32_t egs_bin_blocks(int P) { const int g = egs_bin_gpb(P); return (uint32_t)((P + g - 1) / g); }
+uint32_t egs_bin_groups_per_block(int P) { return P > 0 ? bin_groups_per_block((unsigned)P, egs_bin_blocks(P)) : 0u; }
+int egs_table_scan_prefixed(uint32_t n_chunks) { return n_chunks >= EGS_CHUNK_PREFIX_MIN ? 1 : 0; }
 
 // Launch geometry of the bucketing kernels for a model of P Gaussians at W x H (also used by preprocess.hip's fused count pass).
 EgsBinGeometry egs_bin_geometry(int P, int W, int H, int cull) {
@@ -401,7 +403,7 @@ hipError_t egs_launch_binning(int P, int64_t R64, int W, int H, EgsGeomPtrs g, E
                            b.table, stride, b.chunk_sum);
         EGS_DBG(s);
     }
-    const int prefixed = n_chunks >= EGS_CHUNK_PREFIX_MIN;
+    const int prefixed = egs_table_scan_prefixed(n_chunks);
     if (prefixed) hipLaunchKernelGGL(k_chunk_prefix, dim3(1), dim3(1024), 0, s, b.chunk_sum, n_chunks);
     hipLaunchKernelGGL(k_table_scan, dim3(n_chunks), dim3(EGS_SCAN_THREADS), 0, s, b.table, (size_t)n_tiles * stride, stride, nblocks, b.chunk_sum, n_chunks, b.total, prefixed);
     hipLaunchKernelGGL(k_bin_scatter, dim3(((nblocks + 7) / 8) * 8), dim3(EGS_BIN_THREADS), lds, s, P, gpr, g.offsets, g.rect, g.rec, gx, n_tiles, nblocks,

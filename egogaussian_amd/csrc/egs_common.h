@@ -101,6 +101,8 @@ uint32_t egs_bin_blocks(int P);
 int egs_bin_gpb(int P);                                          // Gaussians per bucketing workgroup for a model of P Gaussians
 struct EgsBinGeometry { uint32_t nblocks, stride, n_chunks; int gpr, cull, use_map, n_tiles, gx; size_t lds; };
 EgsBinGeometry egs_bin_geometry(int P, int W, int H, int cull);  // launch geometry of the bucketing kernels (binning.hip); cull: tile culling wanted (EGS_CALL_KEEP_ALL_INSTANCES clear)
+uint32_t egs_bin_groups_per_block(int P);                        // 64-Gaussian groups of the busiest bucketing workgroup (bin_walk.h bin_groups_per_block)
+int egs_table_scan_prefixed(uint32_t n_chunks);                  // whether the count table's scan is preceded by the prefix pass over its chunk sums (binning.hip)
 #define EGS_SCAN_THREADS 256
 #define EGS_SCAN_ITEMS 8
 #define EGS_SCAN_EPB (EGS_SCAN_THREADS * EGS_SCAN_ITEMS)      // elements per block

@@ -28,6 +28,12 @@ class BinningLayout(C.Structure):
                [(n, C.c_int) for n in ("bin_blocks", "key_bits", "index_passes", "table_stride")]
 
 
+class BinGeometry(C.Structure):
+    """egs_bin_geometry_info: the launch geometry of a forward's tile bucketing (egs_forward_bin_geometry)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_tiles", "gx", "nblocks", "stride", "n_chunks", "gpr", "cull", "use_map", "groups_per_block", "rounds",
+                                         "prefixed", "can_fuse")] + [("lds", C.c_int64)]
+
+
 class ImageLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("ranges", "final_T", "n_contrib", "quad_work", "tile_order", "quad_pairs")]
 
@@ -231,6 +237,7 @@ SIGNATURES = {
     "egs_knn3_grid": (C.c_int, [i32, vp, vp, vp, vp]),
     "egs_forward_fuses_count": (C.c_int, [i32, i32, i32, i32]),
     "egs_forward_sort_plan": (C.c_int, [i32, i64, i32, i32, i32]),
+    "egs_forward_bin_geometry": (C.c_int, [i32, i32, i32, i32, vp]),
     "egs_profile_begin": (C.c_int, [i32]),
     "egs_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "egs_profile_stage_name": (C.c_char_p, [i32]),

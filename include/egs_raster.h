@@ -1157,6 +1157,31 @@ int egs_forward_fuses_count(int P, int width, int height, int flags);
 #define EGS_SORT_BALLOT_RANK           0x4
 int egs_forward_sort_plan(int P, int64_t capacity, int width, int height, int flags);
 
+/* ---- the launch geometry of the tile bucketing of a forward (added within ABI 6: new entries only).
+ * The bucketing (count pass, table scan, scatter pass) deals the model's 256-Gaussian blocks to `nblocks` workgroups, which take their
+ * 64-Gaussian groups `gpr` at a time.  All of it is host arithmetic on the model size, the image size and the call's EGS_CALL_* flags (of
+ * which only EGS_CALL_KEEP_ALL_INSTANCES is read); this entry returns what the launches of such a forward act on -- the same function
+ * decides inside the forward.  It launches no device work and needs no device.
+ *   n_tiles, gx        tiles of the image, tiles per row
+ *   nblocks            bucketing workgroups = columns of the [tile][workgroup] count table that are in use
+ *   stride             row pitch of that table in words (a power of two >= 4 and >= nblocks)
+ *   n_chunks           2048-entry scan chunks of the table = workgroups of its scan
+ *   gpr                groups a workgroup sets up per round
+ *   cull               1: the walk drops the instances whose tile the splat cannot reach (0 with EGS_CALL_KEEP_ALL_INSTANCES)
+ *   use_map            1: the walk finds a slot's Gaussian through the owner map in LDS, 0: by binary search only
+ *   lds                bytes of dynamic LDS of the bucketing workgroups
+ *   groups_per_block   groups of the busiest workgroup;  rounds = ceil(groups_per_block / gpr)
+ *   prefixed           1: the table is large enough for its scan to be preceded by a prefix pass over the chunk sums
+ *   can_fuse           1: the count pass of this geometry can run inside the preprocess launch (what egs_forward_fuses_count answers for a
+ *                      call without EGS_CALL_SEPARATE_COUNT)
+ * P == 0: nothing is bucketed, every field but n_tiles and gx is 0.
+ * -> 0, EGS_ERR_ARG (out == NULL, P < 0, an image side <= 0) or EGS_ERR_RANGE (an image the forwards refuse). */
+typedef struct egs_bin_geometry_info {
+    int32_t n_tiles, gx, nblocks, stride, n_chunks, gpr, cull, use_map, groups_per_block, rounds, prefixed, can_fuse;
+    int64_t lds;
+} egs_bin_geometry_info;
+int egs_forward_bin_geometry(int P, int width, int height, int flags, egs_bin_geometry_info* out);
+
 /* ---- optional per-stage timing with HIP events on the caller's stream (bench / profiling aid) ------
  * The only process-wide state in the library; off by default.  egs_profile_begin allocates an event pool and
  * turns recording on; every stage launched afterwards is bracketed by two events on its stream;

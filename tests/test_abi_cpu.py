@@ -83,6 +83,21 @@ def test_sizes_and_layouts():
     finally:
         _C.set_sort_in_blend(old)
     assert _C.sort_plan(3000, 64, 64, 32768) == IN_BLEND
+    # the launch geometry of the bucketing (added within ABI 6): host arithmetic on the model size, the image size and the culling flag
+    q = lib.BinGeometry()
+    geo = lambda P, W, H, flags=0: (L.egs_forward_bin_geometry(P, W, H, flags, C.byref(q)), {n: int(getattr(q, n)) for n, _ in lib.BinGeometry._fields_})[1]
+    assert re.search(r"int32_t n_tiles, gx, nblocks, stride, n_chunks, gpr, cull, use_map, groups_per_block, rounds, prefixed, can_fuse;\s*int64_t lds;", hdr)
+    assert C.sizeof(lib.BinGeometry) == 12 * 4 + 8
+    g = geo(500000, 960, 540)
+    assert (g["n_tiles"], g["gx"], g["nblocks"], g["stride"], g["n_chunks"]) == (2040, 60, 489, 512, 510)
+    assert L.egs_get_binning_layout(500000, 5000, 960, 540, C.byref(b)) == 0 and (g["nblocks"], g["stride"]) == (b.bin_blocks, b.table_stride)
+    assert (g["gpr"], g["groups_per_block"], g["rounds"], g["cull"], g["use_map"], g["prefixed"], g["can_fuse"]) == (16, 16, 1, 1, 1, 0, 1)
+    assert geo(500000, 960, 540, lib.CALL_KEEP_ALL_INSTANCES)["cull"] == 0 and geo(500000, 960, 540, lib.CALL_SEPARATE_COUNT) == g      # the possibility, not this call's choice
+    g = geo(1000000, 1920, 1080)
+    assert (g["gpr"], g["groups_per_block"], g["rounds"], g["can_fuse"]) == (8, 32, 4, 0) and fuses(1000000, 1920, 1080) == g["can_fuse"]
+    assert geo(0, 64, 64) == dict(dict.fromkeys([n for n, _ in lib.BinGeometry._fields_], 0), n_tiles=16, gx=4)
+    assert L.egs_forward_bin_geometry(10, 64, 64, 0, None) == -1 and L.egs_forward_bin_geometry(10, 8192, 8192, 0, C.byref(q)) == -3
+    assert _C.bin_geometry(500000, 960, 540) == geo(500000, 960, 540) and _C.bin_geometry(3000, 64, 64, debug=_C.CALL_KEEP_ALL_INSTANCES)["cull"] == 0
     # ... and the library exports no setter of process-wide behaviour any more
     for gone in ("egs_debug_set_tile_culling", "egs_debug_set_fused_count", "egs_debug_set_sort_in_blend", "egs_debug_force_ballot_rank", "egs_debug_set_lossgrad"):
         assert not hasattr(L, gone), gone

@@ -11,7 +11,9 @@ allocated ONCE with `capacity` rows.  The number of live Gaussians is a host int
   * the rasterizer's preprocess kernel treats rows >= active_count as culled (radii 0, no instances, zero gradients);
   * FusedAdam(capturable) steps only the live rows (`optimizer.active_rows`);
   * densify.densify_and_prune / prune_points / reset_opacity, given such a model, plan on the live prefix, gather into
-    temporaries and copy the result back INTO the same arrays, then update the two counts.
+    temporaries and copy the result back INTO the same arrays, then update the two counts;
+  * densify.DeviceDensify does the same rewrite with the counts left on the device (a capturable chain); it changes `active_count`
+    without the host knowing, so `n_active` is a property over the cached int that fetches the word once after such a run.
 P, every launch size, every buffer layout and every tensor address stay fixed, so a captured step survives densification
 with no re-capture as long as the new count fits the capacity (otherwise `grow()` reallocates, and the step must be
 captured again).  The getters return the full capacity-sized tensors: outputs of render() (`radii`, `visibility_filter`,
@@ -45,6 +47,27 @@ class CapacityGaussians(SynthGaussians):
         self.capacity = int(capacity)
         self.n_active = int(n)
         self.active_count = torch.tensor([n], dtype=torch.int32, device=device)
+
+    @property
+    def n_active(self):
+        """The live row count as a host int.  It is a cached copy of `active_count`; densify.DeviceDensify, which changes the word on
+        the device, marks the copy stale, and the next read takes the word back once (a synchronisation).  A model that never meets
+        DeviceDensify never reads the device here."""
+        if self._n_active_stale:
+            self._n_active = self._read_active_count()
+            self._n_active_stale = False
+        return self._n_active
+
+    @n_active.setter
+    def n_active(self, n):
+        self._n_active, self._n_active_stale = int(n), False
+
+    def _read_active_count(self):
+        return int(self.active_count.item())
+
+    def mark_active_stale(self):
+        """`active_count` was (or is about to be) rewritten by device work: the next read of n_active fetches it."""
+        self._n_active_stale = True
 
     def set_active(self, n):
         """New live row count (host int + the device word the kernels read; one tiny fill, outside any capture)."""

@@ -55,6 +55,19 @@ class ObjectMotion(C.Structure):                 # egs_object_motion; goes where
     _fields_ = [("rot", ObjectRotation), ("A12", C.c_void_p), ("moved", C.c_void_p), ("grad", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class DensifyRuleBlock(C.Structure):              # egs_densify_rules_dev: twelve words of device memory
+    _fields_ = [(n, C.c_float) for n in ("max_grad", "min_opacity", "dense_extent", "big_extent", "max_screen_size")] + \
+               [(n, C.c_int32) for n in ("clone", "split", "has_curr_gen", "curr_gen", "prune_prev_gen", "has_which_object", "which_object")]
+
+
+class DensifyArray(C.Structure):                 # egs_densify_array
+    _fields_ = [("data", C.c_void_p), ("row_floats", C.c_int32), ("role", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+DENSIFY_MAX_ARRAYS = 32
+DENSIFY_PARAM, DENSIFY_MOMENT, DENSIFY_STAT, DENSIFY_TAG = 0, 1, 2, 3      # EGS_DENSIFY_* roles
+DENSIFY_TAG_I32, DENSIFY_TAG_CLONE_GEN = 1, 2                              # EGS_DENSIFY_TAG_* flags
+
 # include/egs_raster.h EGS_ACT_*: activation flags of the raw-parameter mode (_C re-exports them)
 ACT_LOG_SCALES, ACT_RAW_QUATS, ACT_LOGIT_OPACITY, ACT_OBJECT_MOTION, ACT_SCALAR_COLOR = 1, 2, 4, 8, 16
 ACT_RAW_PARAMETERS = ACT_LOG_SCALES | ACT_RAW_QUATS | ACT_LOGIT_OPACITY
@@ -232,6 +245,10 @@ SIGNATURES = {
     "egs_gather_rows_f32": (C.c_int, [i64, i32, vp, vp, i32, vp, vp, vp]),
     "egs_gather_i32": (C.c_int, [i64, vp, vp, i32, i32, vp, vp, vp]),
     "egs_split_children": (C.c_int, [i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_densify_plan_dev": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_prune_plan_dev": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "egs_densify_apply_scratch_bytes": (C.c_size_t, [i32, i32, vp]),
+    "egs_densify_apply": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(DensifyArray), i32, i32, i32, vp, vp, vp, vp]),
     "egs_knn3_mean_dist2": (C.c_int, [i32, vp, vp, vp]),
     "egs_knn3_grid_scratch_bytes": (C.c_size_t, [i32]),
     "egs_knn3_grid": (C.c_int, [i32, vp, vp, vp, vp]),

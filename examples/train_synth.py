@@ -10,6 +10,10 @@ number of live Gaussians is a device word, so the captured step is NOT re-captur
 reference's behaviour -- new tensors per densification, one re-capture each).  The step voids frames that outgrow its instance
 capacity on the device and re-captures itself with more room (GraphedTrainStep(check_every=...)).
 
+`--device-densify` densifies through densify.DeviceDensify: plan and in-place apply replayed from a hipGraph of their own, no count read
+back.  Its status words are read where the loop calls step.check() anyway; a densification the capacity refused wrote nothing, and the
+loop grows the model, re-captures and densifies again.
+
 `--entropy-iters K` appends the reference's entropy phase (trainers/train_static.py:97-102,139-141): K more iterations of the SAME
 captured step with the weight of the opacity-entropy term switched on (`step.entropy_weight = --entropy-weight`: a device scalar, no
 re-capture), then `prune_points(get_opacity < 0.5)` on the capacity model (in place: no re-capture either).
@@ -120,6 +124,9 @@ def main(argv=None):
     ap.add_argument("--out", default="")
     ap.add_argument("--plain", action="store_true", help="plain model: densification replaces the tensors, the step is re-captured each time")
     ap.add_argument("--capacity-factor", type=float, default=3.0, help="rows allocated = this x the initial number of Gaussians")
+    ap.add_argument("--device-densify", action="store_true",
+                    help="densify through densify.DeviceDensify: plan and in-place apply replayed from a hipGraph, no count read back; the status "
+                         "words are read at the step.check() points, and a densification the capacity refused is made up for after grow()")
     ap.add_argument("--report-every", type=int, default=0, help="print (and --log) progress every this many iterations")
     ap.add_argument("--log", default="")
     ap.add_argument("--min-opacity", type=float, default=0.005)
@@ -137,6 +144,8 @@ def main(argv=None):
     ap.add_argument("--bg-iters", type=int, default=50, help="background-stage steps of --mask-handoff")
     ap.add_argument("--dilate-size", type=int, default=5, help="dilation of the background stage's gate (the reference's train.py: 5)")
     a = ap.parse_args(argv)
+    if a.device_densify and a.plain:
+        ap.error("--device-densify needs the capacity-sized model (drop --plain)")
     dev = torch.device("cuda", 0)
     H, W = a.height, a.width
     teacher = make_scene(a.gaussians, H, W, seed=0, sh_degree=a.sh_degree)
@@ -186,6 +195,20 @@ def main(argv=None):
     step = GraphedTrainStep(pc, pc.optimizer, bg, lambda_dssim=0.2, densify_stats=True, check_every=50, entropy_reg=a.entropy_iters > 0)
     step.capture(cams[0], gts[0], warmup=2, capacity_margin=1.5, capacity_cams=cams[::max(1, a.frames // 6)])
     manual_recaptures, t_eval, next_report = 0, 0.0, a.report_every
+    dd, last_rules, refusals = None, None, 0
+
+    def regrow_if_refused(dd):
+        """--device-densify: the one read of the densifier's status words.  A densification that needed more rows than the capacity wrote
+        nothing; the model grows to hold it (new arrays) and a new DeviceDensify is captured on them -> the object to go on with."""
+        nonlocal refusals
+        st = dd.check()
+        if not st["refused_since_last_check"]:
+            return dd
+        refusals += 1
+        pc.grow(max(int(st["rows_needed"] * 1.5), st["rows_needed"] + 1024))
+        report(f"densify refused on the device: {st['rows_needed']} rows needed; capacity grown to {pc.capacity}")
+        return densify.DeviceDensify(pc).capture()
+
     t0, it = time.perf_counter(), 2
     while it < a.iters:
         k = it % a.frames
@@ -200,14 +223,24 @@ def main(argv=None):
             step.check()                                             # a frame that outgrew the capacity was voided on the device; make room now
             size_threshold = 20 if it > a.opacity_reset_interval else None
             ptr = pc._xyz.data_ptr()
-            n0, n1 = densify.densify_and_prune(pc, a.grad_threshold, a.min_opacity, extent, size_threshold)
+            if a.device_densify:
+                # plan and apply stay on the device: one graph launch, nothing read back.  What the previous densification did is read
+                # here, where step.check() has synchronised anyway; one that did not fit wrote nothing and is made up for first.
+                if dd is None:
+                    dd = densify.DeviceDensify(pc).capture()
+                dd = regrow_if_refused(dd)                           # (new arrays: the address test below re-captures the step)
+                last_rules = (a.grad_threshold, a.min_opacity, extent, size_threshold)
+                dd.replay(*last_rules)
+                n0 = n1 = None                                       # known at the next check()
+            else:
+                n0, n1 = densify.densify_and_prune(pc, a.grad_threshold, a.min_opacity, extent, size_threshold)
             if it % a.opacity_reset_interval == 0:
                 densify.reset_opacity(pc)
             if a.plain or pc._xyz.data_ptr() != ptr:                 # new parameter tensors (plain model, or the capacity had to grow) -> new graph
                 step.recapture(warmup=1); manual_recaptures += 1
                 it += 1
             if not a.report_every:
-                report(f"iter {it}: densify {n0} -> {n1} Gaussians")
+                report(f"iter {it}: densify {n0} -> {n1} Gaussians" if n0 is not None else f"iter {it}: densify enqueued on the device")
         if a.report_every and it >= next_report:
             next_report += a.report_every
             torch.cuda.synchronize()
@@ -237,12 +270,18 @@ def main(argv=None):
         report(f"entropy phase: {a.entropy_iters} iterations at weight {a.entropy_weight}, mean entropy of the visible opacities {h_end:.4f}; "
                f"pruned opacity < 0.5: {n_before} -> {live()} Gaussians, {entropy_report['recaptures']} re-capture(s)")
     torch.cuda.synchronize()
+    if dd is not None:                                               # the last densification's status; one that was refused is done again
+        dd2 = regrow_if_refused(dd)
+        if dd2 is not dd:
+            step.recapture(warmup=1); manual_recaptures += 1
+            dd2.replay(*last_rules)
+            torch.cuda.synchronize()
     dt = time.perf_counter() - t0 - t_eval
     step.check()
     # (what the run was, for callers that assert on it: tests/test_gpu_densify.py runs the reference's full schedule through this function)
     pc.train_report = dict(gaussians_start=a.gaussians, gaussians_end=live(), psnr_end=quality(), its_per_s=a.iters / dt, recaptures=manual_recaptures + step.recaptures,
                            recaptures_after_overflow=step.recaptures, overflow_events=step.skipped_frames_seen, iterations=it, instance_capacity=step.capacity,
-                           entropy_phase=entropy_report)
+                           entropy_phase=entropy_report, densify_refusals=refusals)
     report(f"end: {live()} Gaussians, held-out PSNR {quality():.2f} dB, {a.iters / dt:.0f} it/s including densification, opacity resets and "
            f"{manual_recaptures + step.recaptures} re-capture(s) ({step.recaptures} after an instance-capacity overflow, {step.skipped_frames_seen} overflow events)")
     # the evaluation pass over the training cameras: 8-bit PSNR / SSIM as the reference's eval_and_metric reports them (no hand here: every

@@ -1121,6 +1121,64 @@ int egs_split_children(int64_t rows, const int32_t* src_index, const uint8_t* ki
                        const float* z /*[2 n_split, 3]*/, const float* xyz_old, const float* scaling_old, const float* rotation_old,
                        float* xyz_new, float* scaling_new, void* stream);
 
+/* ---- f-4, capturable: densify / prune of a capacity-sized model with no host read.  The two calls above size their launches
+ * by a live count the host knows and hand the host `totals` to size the new model; the four below take every count from device
+ * memory, so one recorded chain (plan + apply) serves every later state of the model.
+ *      egs_densify_plan_dev      egs_densify_plan over `capacity` rows.  The live count is *active_count (clamped to
+ *                                [0, capacity]); rows at or beyond it set no flag, so src_index / kind / split_rank / totals[0..3]
+ *                                are what egs_densify_plan gives on the live prefix (split_rank = -1 on dead rows).  The rule
+ *                                values come from a device block (egs_densify_rules_dev), not from launch arguments: the size
+ *                                threshold switches on once per schedule and curr_gen changes per dynamic frame.
+ *                                totals is uint64[5]: totals[4] = the live count the plan was made for.  Plan buffers are sized
+ *                                for capacity: scratch egs_densify_plan_scratch_bytes(capacity), src_index / kind [3 capacity].
+ *                                is_object is read in the model's own type: is_object_is_float != 0 -> float32 (truncated as
+ *                                torch's .to(int32) does), else int32.
+ *      egs_prune_plan_dev        egs_prune_plan the same way: kept = !mask on the live rows; prune_mask has capacity bytes.
+ *      egs_densify_apply         rewrites every array of the table in place from the plan, in two launches whatever the table
+ *                                holds: a gather of rows [0, n_new) of every array into `scratch`, then a commit that copies
+ *                                them back, zeroes what the roles below say and writes the count.  n_new = totals[0] + totals[1]
+ *                                + 2 totals[2], n_old = totals[4], n_split = totals[3], all read on the device.
+ *                                   PARAM   row k = old row src_index[k]; in the arrays named by xyz_index / scaling_index rows of
+ *                                           kind 2 / 3 take egs_split_children's arithmetic (rotation_index: the quaternions);
+ *                                           child c of split rank r reads row c * n_split + r of z [2 capacity, 3]
+ *                                   MOMENT  as PARAM, zero where kind[k] != 0
+ *                                   STAT    rules != NULL and (clone || split): zeroed over all capacity rows; else gathered
+ *                                   TAG     gathered (EGS_DENSIFY_TAG_I32: int32 rows; else float32 rows holding integers);
+ *                                           EGS_DENSIFY_TAG_CLONE_GEN: a clone takes rules->curr_gen when has_curr_gen;
+ *                                           rows [n_new, n_old) are zeroed
+ *                                rules == NULL: a prune plan (no clone value, statistics gathered; z may be NULL).
+ *                                n_new > capacity: NOTHING is written but status.  n_old == 0: nothing is written but status
+ *                                (an application of 0 rows).  Else *active_count = n_new, by the commit launch.
+ *                                status (device uint32[4], zeroed once by the caller): [0] refusals so far, [1] rows the latest
+ *                                refusal needed, [2] applications done, [3] n_new of the latest application.
+ *                                No allocation, no read-back, no synchronisation; EGS_ERR_ARG before any device work.
+ *      egs_densify_apply_scratch_bytes   capacity * sum(row_floats) * 4: one shadow row per row rewritten, nothing else. */
+#define EGS_DENSIFY_MAX_ARRAYS 32
+enum { EGS_DENSIFY_PARAM = 0, EGS_DENSIFY_MOMENT = 1, EGS_DENSIFY_STAT = 2, EGS_DENSIFY_TAG = 3 };
+enum { EGS_DENSIFY_TAG_I32 = 1, EGS_DENSIFY_TAG_CLONE_GEN = 2 };
+typedef struct {
+    float max_grad, min_opacity, dense_extent /* percent_dense * extent */, big_extent /* 0.1 * extent */, max_screen_size /* <= 0: off */;
+    int32_t clone, split, has_curr_gen, curr_gen, prune_prev_gen, has_which_object, which_object;
+} egs_densify_rules_dev;                                   /* 12 words of device memory */
+typedef struct {
+    void* data;                                            /* [capacity, row_floats] float32 (or int32: EGS_DENSIFY_TAG_I32), contiguous */
+    int32_t row_floats, role, flags, reserved;
+} egs_densify_array;
+int egs_densify_plan_dev(int capacity, const int32_t* active_count, const float* grad_accum, const float* denom,
+                         const float* scaling_raw /*[capacity,3]*/, const float* opacity_raw, const float* max_radii2D,
+                         const int32_t* generation, const void* is_object, int is_object_is_float,
+                         const egs_densify_rules_dev* rules /*device*/, void* scratch, int32_t* src_index /*[3 capacity] out*/,
+                         uint8_t* kind /*[3 capacity] out*/, int32_t* split_rank /*[capacity] out*/, uint64_t* totals /*device [5] out*/,
+                         void* stream);
+int egs_prune_plan_dev(int capacity, const int32_t* active_count, const uint8_t* prune_mask /*[capacity]*/, void* scratch,
+                       int32_t* src_index, uint8_t* kind, int32_t* split_rank, uint64_t* totals /*device [5] out*/, void* stream);
+size_t egs_densify_apply_scratch_bytes(int capacity, int n_arrays, const int32_t* row_floats /*HOST [n_arrays]*/);
+int egs_densify_apply(int capacity, int32_t* active_count /*device, in/out*/, const int32_t* src_index, const uint8_t* kind,
+                      const int32_t* split_rank, const uint64_t* totals /*device [5]*/, const egs_densify_rules_dev* rules /*device or NULL*/,
+                      int n_arrays, const egs_densify_array* arrays /*HOST [n_arrays]*/, int xyz_index, int scaling_index,
+                      int rotation_index, const float* z /*[2 capacity, 3] or NULL*/, void* scratch, uint32_t* status /*device [4]*/,
+                      void* stream);
+
 /* ---- f-2: mean squared distance of every point to its 3 nearest neighbours (self excluded by index).
  *      Replaces simple_knn._C.distCUDA2 (un-vendored submodule, /root/reference/.gitmodules:4-6), imported at
  *      /root/reference/scene/gaussian_model.py:21 and called at :301.  Exact (all pairs).  A point with fewer than three

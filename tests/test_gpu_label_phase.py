@@ -239,10 +239,16 @@ def test_loss_gradient_formed_in_the_blend(N, H, W, seed, smul, border, gated):
     assert torch.equal(run, torch.full((1,), 10.0, device=dev) + loss)
 
 
-def test_adam_step_in_the_finish_launch_is_bit_identical():
+@pytest.mark.parametrize("active_rows", ["N-17", -1, 0, 1, 256, "N", "N+9"])
+def test_adam_step_in_the_finish_launch_is_bit_identical(active_rows):
+    """active_rows: the live-row word -- below zero, zero, one row, a workgroup edge of k_label_finish, all rows, more rows than there are.
+    The rows that take the step are those below min(N, max(word, 0)); the step is counted whatever the word holds, by the prologue's
+    egs_adam_tick as by k_adam."""
     from egogaussian_amd import _C, lib, _hip
     dev = _dev()
     N, H, W = 3000, 70, 100
+    word = {"N-17": N - 17, "N": N, "N+9": N + 9}.get(active_rows, active_rows)
+    live = min(N, max(word, 0))
     out, label0, mask, gate = _label_scene(N, H, W, 1, 4.0, dev)
     radii = out[4]
     assert int((radii <= 0).sum()) > 17, "rows that were never rendered: their gradient is 0, their moments still decay"
@@ -251,7 +257,8 @@ def test_adam_step_in_the_finish_launch_is_bit_identical():
     gen = torch.Generator().manual_seed(11)
     p = label0.clone().to(dev); m = (torch.randn(N, generator=gen) * 1e-3).to(dev); v = (torch.rand(N, generator=gen) * 1e-6).to(dev)
     step = torch.full((1,), 4.0, device=dev); lr = torch.full((1,), 2.5e-3, device=dev); coef = torch.zeros(12, device=dev)
-    active = torch.tensor([N - 17], dtype=torch.int32, device=dev)
+    active = torch.tensor([word], dtype=torch.int32, device=dev)
+    m0, v0 = m.clone(), v.clone()
     leaf = lib.AdamLeaf(); leaf.param, leaf.exp_avg, leaf.exp_avg_sq, leaf.lr, leaf.step = p.data_ptr(), m.data_ptr(), v.data_ptr(), lr.data_ptr(), step.data_ptr()
     G = int(L.egs_adam_workgroups(N))
     for it in range(3):
@@ -267,9 +274,13 @@ def test_adam_step_in_the_finish_launch_is_bit_identical():
         assert float(g[radii <= 0].abs().max()) == 0.0 and float(g.abs().max()) > 0
         assert float(step) == 5.0 + it and torch.equal(step, rstep)
         assert torch.equal(p, rp) and torch.equal(m, rm) and torch.equal(v, rv), f"call {it}: fused and stand-alone Adam disagree"
-        never = (radii <= 0)[: N - 17]
-        assert bool((m[: N - 17][never] != 0).any()) and bool((p[: N - 17][never] != label0.to(dev)[: N - 17][never]).any()), "dense Adam: zero-gradient rows move on momentum"
-    assert torch.equal(p[N - 17:], label0.to(dev)[N - 17:]), "rows at and beyond active_rows are untouched"
+        never = (radii <= 0)[:live]
+        assert live < N - 17 or bool(never.any())
+        if bool(never.any()):
+            assert bool((m[:live][never] != 0).any()) and bool((p[:live][never] != label0.to(dev)[:live][never]).any()), "dense Adam: zero-gradient rows move on momentum"
+        assert bool((m[:live] != m0[:live]).all()), "every live row is stepped: its first moment decays whatever its gradient"
+    assert torch.equal(p[live:], label0.to(dev)[live:]), "rows at and beyond active_rows are untouched"
+    assert torch.equal(m[live:], m0[live:]) and torch.equal(v[live:], v0[live:]), "... and so are their moments"
 
 
 def test_overflow_word_voids_the_step():

@@ -613,7 +613,7 @@ static int backward_impl(const BackwardCall& c) {
     const bool colors_only = c.grad_mask == EGS_GRAD_COLORS && sc.colors && !sink && !st.grad_accum;
     if (!c.background || lacks_pointers(sc, cam, c.radii, c.geom_buffer) || !c.image_buffer || !dL_dout_color || (!d.means2D && !colors_only) || !c.scratch)
         return EGS_ERR_ARG;
-    if (misaligned(c.geom_buffer, c.binning_buffer, c.image_buffer) || ((uintptr_t)c.scratch & 15u)) return EGS_ERR_ARG;
+    if (misaligned(c.geom_buffer, c.binning_buffer, c.image_buffer) || ((uintptr_t)c.scratch & 63u)) return EGS_ERR_ARG;      // (accumulator lines: 64 bytes on 64-byte boundaries)
     EgsGeomPtrs g = geom_ptrs(const_cast<void*>(c.geom_buffer), P);
     float* grad_acc = (float*)c.scratch;
     if (colors_only) {
@@ -780,7 +780,7 @@ int egs_backward_entropy_lossgrad(int P, int sh_degree, int sh_coeffs, int64_t R
 // egs_backward_prologue (HOST struct) -> the side jobs a loss backward launch carries
 static int prologue_args(const egs_backward_prologue* side, EgsPrologueArgs& pa) {
     int rc = check_dims(side->P, side->width, side->height); if (rc) return rc;
-    if (side->P <= 0 || !side->image_buffer || !side->scratch) return EGS_ERR_ARG;
+    if (side->P <= 0 || !side->image_buffer || !side->scratch || ((uintptr_t)side->scratch & 63u)) return EGS_ERR_ARG;
     EgsImgPtrs im = img_ptrs(side->image_buffer, side->width, side->height);
     pa.n_tiles = (int)egs_tiles(side->width, side->height);
     pa.quad_work = im.quad_work; pa.tile_order = im.tile_order;
@@ -911,7 +911,7 @@ int egs_backward_label(int P, int64_t R, int width, int height, const int32_t* r
         return 0;
     }
     if (!radii || !geom_buffer || !image_buffer || !scratch || (R > 0 && !binning_buffer)) return EGS_ERR_ARG;
-    if (misaligned(geom_buffer, binning_buffer, image_buffer) || ((uintptr_t)scratch & 15u)) return EGS_ERR_ARG;
+    if (misaligned(geom_buffer, binning_buffer, image_buffer) || ((uintptr_t)scratch & 63u)) return EGS_ERR_ARG;
     EgsGeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
     EgsImgPtrs im = img_ptrs(const_cast<void*>(image_buffer), width, height);
     float* grad_acc = (float*)scratch;

@@ -20,16 +20,22 @@
 #define EGS_LOG2E 1.4426950408889634f
 #define EGS_LN2   0.6931471805599453f
 
-// Per-Gaussian accumulator written by the blend backward (one 48-B line per Gaussian).  With gd = dL/dalpha * G per
-// (pixel, splat) pair and d = splat centre - pixel:
+// Per-Gaussian accumulator written by the blend backward: float [P][16], one 64-byte line per Gaussian on a 64-byte boundary (the
+// scratch's base is checked on the host).  With gd = dL/dalpha * G per (pixel, splat) pair and d = splat centre - pixel:
 //   [0]=sum gd dx  [1]=sum gd dy  [2]=sum gd dx^2  [3]=sum gd dx dy  [4]=sum gd dy^2  [5]=sum gd = dL/dopacity
-//   [6..8]=dL/dcolor rgb  [9]=dL/ddepth
+//   [6..8]=dL/dcolor rgb  [9]=dL/ddepth  [10..15] spare
 // k_preprocess_backward converts the five moments into dL/dmean2D and dL/dconic with the Gaussian's own opacity and conic, the
-// conic -> cov2D step in float64 (preprocess.hip: the one place where float32 lost a recorded parity case).  Slots 10 and 11 of the
-// 48-byte line are spare.  (Round 6 tried "FAR" splats here -- a per-pixel cancelled form of dL/dmean2D for splats whose pixels all lie
-// far from the centre, accumulated into the two spare slots: 7 more vector instructions per visit of the backward blend and no change
-// in any gradient of the off-screen family, whose loss turned out to sit in the chain behind the sums; experiments/far_mean2d.patch.)
-#define EGS_GRAD_STRIDE 12
+// conic -> cov2D step in float64 (preprocess.hip: the one place where float32 lost a recorded parity case).
+// Why 64 bytes for ten floats: float atomics leave L2 as 64-byte memory-side requests.  In the 48-byte lines of earlier rounds the sums
+// of every second Gaussian (bytes [48, 88) and [96, 136) of each 192) crossed a 64-byte boundary and cost two requests per visit: 0.081 ns
+// per line chip-wide against 0.056 for aligned lines (tools/ubench/atomic_lanes.hip patterns 0 and 10-12, profiles/backward_lines.md).
+// The whole array, spare words included, is cleared contiguously.
+// (Round 6 tried "FAR" splats here -- a per-pixel cancelled form of dL/dmean2D for splats whose pixels all lie far from the centre,
+// accumulated into two spare slots: 7 more vector instructions per visit of the backward blend and no change in any gradient of the
+// off-screen family, whose loss turned out to sit in the chain behind the sums; experiments/far_mean2d.patch.)
+#define EGS_GRAD_STRIDE 16
+// The deterministic mode's integer lines (det_accum.h) are not reached by float atomics and keep twelve words per Gaussian.
+#define EGS_DET_STRIDE 12
 
 // Hot Gaussians.  A splat whose alpha >= 1/255 box covers EGS_HOT_MIN_TILES tiles or more is visited by hundreds to thousands of
 // quadrant-waves, all of which add into ITS ONE accumulator line -- and the waves of every tile reach it at about the same point of
@@ -248,7 +254,7 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
                                       const float* dL_dalpha, float* grad_acc, int colors_only /*2: one scalar colour (k_render_backward<3>)*/, const EgsLossGradHost* lg, hipStream_t s,
                                       void* det_lines = nullptr /*EGS_CALL_DETERMINISTIC: egs_det_bytes(P) of ZEROS (det_accum.h); the blend runs as two integer passes and a decode*/);
 // The deterministic mode's lines behind the float accumulator in the backward's scratch: uint32[P][12] maxima, then int64[P][12] sums
-static inline size_t egs_det_bytes(size_t P) { return egs_align(P * EGS_GRAD_STRIDE * (sizeof(uint32_t) + sizeof(int64_t))); }
+static inline size_t egs_det_bytes(size_t P) { return egs_align(P * EGS_DET_STRIDE * (sizeof(uint32_t) + sizeof(int64_t))); }
 // colors_only: the blend left only the colour sums (k_render_backward<0>); this turns them into dL/dcolors_precomp [P,3]
 hipError_t egs_launch_colors_from_acc(int P, const float* grad_acc, const uint8_t* clamped, const int32_t* radii, float* dcolors, hipStream_t s);
 // The label step's last launch (label_loss.hip k_label_finish): dL/dlabel[i] = slot 6 of Gaussian i's line (+ its replica lines), 0 when radii[i] <= 0;

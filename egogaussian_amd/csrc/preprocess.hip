@@ -380,7 +380,7 @@ __device__ __forceinline__ void pp_bwd_one(
     // Adam to its 256 rows; their dX arrays may then be NULL (nothing written)
     const unsigned tid = threadIdx.x;
     const bool vis = radii[i] > 0;
-    float acc[EGS_GRAD_STRIDE];
+    float acc[12];                                                    // slots 0..9 (+ two spare) of the 64-byte line: three of its four float4
     {
         const float4* ga = reinterpret_cast<const float4*>(grad_acc + (size_t)i * EGS_GRAD_STRIDE);
 #pragma unroll

@@ -12,13 +12,16 @@
 //   * the 10 per-splat partial sums (five moments of gd = dL/dalpha * G, opacity, rgb, depth) are reduced across the 64 lanes in three
 //     stages priced with tools/ubench/xlane_rate.hip (cycles per SIMD at 8 waves: plain VALU 2.4, DPP add 6.8,
 //     v_permlane{16,32}_swap 11.5, v_readlane 8, ds_bpermute 22):
-//       1. v_permlane32_swap "transpose-and-add" folds the ten registers into five (lanes 0-31: even value, 32-63: odd);
-//       2. the five registers go through a wave-private 1.25 KiB LDS slice (5 ds_write_b32), and lane 4v+g reads eight
-//          consecutive partials of value v (2 ds_read_b128) and adds them -- the LDS pipe is otherwise nearly idle here;
-//       3. two quad_perm DPP adds finish the sum in lanes 0, 4, ..., 36,
-//     about 100 VALU-cycles instead of 196 for swaps + DPP rows alone (and 408 for ten DPP butterflies);
-//   * those ten lanes issue ONE global_atomic_add_f32 instruction into the Gaussian's 48-byte accumulator line
-//     (egs_common.h) instead of ten.
+//       1. ONE v_permlane32_swap "transpose-and-add" folds the last two registers into one (lanes 0-31: one value, 32-63: the other;
+//          two swaps with depth / alpha gradients, MODE 2): eight registers = eight rows of 64 partials;
+//       2. the eight registers go through a wave-private 2 KiB LDS slice (8 ds_write_addtid_b32: red_write_rows8), and every lane reads
+//          eight consecutive partials (2 ds_read_b128) and adds them -- the LDS pipe is otherwise nearly idle here;
+//       3. two quad_perm DPP adds and a row_half_mirror one finish the sums in lanes 0, 8, ..., 48 (+ 56, 60: the folded pair),
+//     about 55 VALU-cycles instead of 100 for five swaps and five rows (rounds 1-6; MODE 0 still folds its three sums that way), 196 for swaps +
+//     DPP rows alone and 408 for ten DPP butterflies.  The cheaper arithmetic pays only with the 64-byte lines below: under ~90 us of VALU
+//     work the accumulator atomics are what the launch waits for, and in 48-byte lines they were as slow as that (profiles/backward_lines.md);
+//   * those lanes issue ONE global_atomic_add_f32 instruction into the Gaussian's 64-byte accumulator line
+//     (egs_common.h) instead of ten: the line lies on a 64-byte boundary, so the instruction is ONE memory-side request.
 #include "egs_common.h"
 #include "blend_common.h"
 #include "backward_prologue.h"
@@ -98,8 +101,22 @@ struct EgsLossGrad { const float* img; const float* gt; const float* m0; const f
                      const float* fin_partial; size_t fin_n; float fin_lambda; float* fin_loss; float* fin_running;
                      EgsObjLossK obj; EgsLabelLossK lab; };      // obj (read by <2, true> only); lab (read by <3, true> only, label_bce.h); obj: the object stages' loss: the alpha plane the forward wrote, the mask, the alpha weights
 #define LG_COLS 27
+#define BWD_STAGE_F4 160          // float4 per wave of staged records: [0, 64) f4[0], [64, 128) f4[1], [128, 160) the first half of f4[2] as 64 float2
+#define BWD_RED_ROWS 8            // rows of 64 partials in a wave's reduction slice (MODE 1 / 2; MODE 0 uses two)
+
+// MODE 1 / 2, stage 1 of the reduction: eight registers = eight rows of 64 partials into the wave's slice, row r at byte 256 r.
+// ds_write_addtid_b32 takes its address from M0 + offset + 4 x lane: no address register and 2 LDS cycles each.  M0 is written in the same
+// statement (the compiler keeps nothing there across it); the s_nop covers the wait state the hardware wants between s_mov m0 and an LDS
+// instruction that reads it -- the assembler does not pad inline assembly, and without it the first row of a wave's first visit went to the
+// address M0 held before.  LDS instructions of a wave execute in order: the ds_read_b128 pair behind this needs no wait of its own.
+__device__ __forceinline__ void red_write_rows8(uint32_t slice_byte, float r0, float r1, float r2, float r3, float r4, float r5, float r6, float r7) {
+    asm volatile("s_mov_b32 m0, %8\n\ts_nop 1\n\t"
+                 "ds_write_addtid_b32 %0\n\tds_write_addtid_b32 %1 offset:256\n\tds_write_addtid_b32 %2 offset:512\n\tds_write_addtid_b32 %3 offset:768\n\t"
+                 "ds_write_addtid_b32 %4 offset:1024\n\tds_write_addtid_b32 %5 offset:1280\n\tds_write_addtid_b32 %6 offset:1536\n\tds_write_addtid_b32 %7 offset:1792"
+                 :: "v"(r0), "v"(r1), "v"(r2), "v"(r3), "v"(r4), "v"(r5), "v"(r6), "v"(r7), "s"(slice_byte) : "memory");
+}
 // DET (EGS_CALL_DETERMINISTIC; det_accum.h): 0 = the float atomics above.  Otherwise the blend runs twice over the same lists, `grad_acc`
-// then points to the mode's lines -- uint32[P][12] maxima, and hot_base words behind them int64[P][12] sums; no replica lines -- and a wave publishes
+// then points to the mode's lines -- uint32[P][12] maxima, and hot_base (= P * EGS_DET_STRIDE) words behind them int64[P][12] sums; no replica lines -- and a wave publishes
 //   1: float_bits(|out|) with an integer atomic max (the maximum of non-negative floats' bit patterns does not depend on the order),
 //   2: out / quantum(that maximum) as an integer with a 64-bit atomic add (integer sums associate).
 // The partial `out` of a (quadrant, splat) is the same bits in both passes and in every run: one wave, fixed lanes, a fixed fold order.
@@ -115,9 +132,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     constexpr bool HAS_DA = MODE == 2;
     constexpr int NV = MODE == 0 ? 3 : MODE == 3 ? 1 : 10;             // sums per (wave, splat)
     constexpr bool COLOR_SUMS = MODE == 0 || MODE == 3;                // no dL/dalpha recurrence, no background term, no moments
-    __shared__ float4 smem[4 * 64 * EGS_SPLAT_REC_F4 + 4 * 5 * 16];      // the staged records of four waves, then their reduction slices
-    float4 (*lds)[64 * EGS_SPLAT_REC_F4] = reinterpret_cast<float4 (*)[64 * EGS_SPLAT_REC_F4]>(smem);
-    float (*red)[5 * 64] = reinterpret_cast<float (*)[5 * 64]>(smem + 4 * 64 * EGS_SPLAT_REC_F4);
+#ifdef EGS_RED5                                                       // A/B switch: the five folded rows of rounds 1-6 for MODE 1 / 2 as well
+    constexpr bool ROWS8 = false;
+#else
+    constexpr bool ROWS8 = MODE == 1 || MODE == 2;
+#endif
+    // Per wave: the 40 bytes of a staged record the loop reads, as 64 float4 + 64 float4 + 64 float2 (2.5 KiB; the box words stay in registers),
+    // then, behind those of all four waves, the wave's reduction slice of eight rows of 64 partials (2 KiB): 18 KiB per workgroup, eight per CU.
+    __shared__ float4 smem[4 * BWD_STAGE_F4 + 4 * BWD_RED_ROWS * 16];
+    float4 (*lds)[BWD_STAGE_F4] = reinterpret_cast<float4 (*)[BWD_STAGE_F4]>(smem);
+    float (*red)[BWD_RED_ROWS * 64] = reinterpret_cast<float (*)[BWD_RED_ROWS * 64]>(smem + 4 * BWD_STAGE_F4);
     static_assert(sizeof(smem) >= 9 * 16 * LG_COLS * sizeof(float), "the loss-gradient prologue's blurred maps fit the loop's LDS");
     __shared__ uint32_t quad_claimed;
     const uint32_t order_word = tile_order[blockIdx.x];              // 0xffffffff = padding workgroup
@@ -144,6 +168,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         q = (unsigned)__builtin_amdgcn_readfirstlane((int)want);
     }
     float4* my = lds[wv];
+    float2* my_half = reinterpret_cast<float2*>(my + 128);
     float* myred = red[wv];
     EGS_BWD_MEASURE(const uint64_t t_start = wall_clock64(); uint32_t meas = 0;)
     const int qx0 = (tile % gx) * EGS_TILE + (int)(q & 1) * 8, qy0 = (tile / gx) * EGS_TILE + (int)(q >> 1) * 8;
@@ -267,6 +292,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const float4* red_src = reinterpret_cast<const float4*>(myred + (rv < (unsigned)NV ? (rv >> 1) * 64 + (rv & 1) * 32 + rg * 8 : 0));
     int slot = MODE == 3 ? (lane == 63 ? 6 : -1)                      // (MODE 3: lane 63 holds the one sum; slot 6, the first colour slot)
                          : (rg == 0 && rv < (unsigned)NV) ? (int)rv + (MODE == 0 ? 6 : 0) : -1;      // (MODE 0: the three colour slots of the line)
+    // MODE 1 / 2, the eight-row reduction: rows 0 .. UNF - 1 of the slice hold the 64 partials of values 0 .. UNF - 1 as they are, each further row
+    // two values folded by one v_permlane32_swap (32 partials each) -- MODE 1: seven rows + (v7, v8), its tenth sum is a constant 0 and is not
+    // published; MODE 2: six rows + (v6, v7) + (v8, v9).  Lane l adds the eight partials [8 l, 8 l + 8) of the slice (two ds_read_b128, lanes with
+    // bit 4 set take the upper half first: no bank is asked twice in a pass), two quad_perm DPP adds finish a folded value in lanes 8 r, 8 r + 4, a
+    // third (row_half_mirror) a whole row in lane 8 r.
+    constexpr unsigned UNF = HAS_DA ? 6u : 7u;
+    const uint32_t red_byte = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)myred);
+    const bool whole_row = lane < 8u * UNF;
+    if (ROWS8) {
+        red_src = reinterpret_cast<const float4*>(myred + 8 * lane);
+        slot = whole_row ? ((lane & 7u) == 0u ? (int)(lane >> 3) : -1) : ((lane & 3u) == 0u ? (int)(UNF + 2u * ((lane >> 3) - UNF) + ((lane >> 2) & 1u)) : -1);
+    }
+    const unsigned red_first = (lane >> 4) & 1u;
     // (MODE 3: kept opaque -- with a provably uniform address the compiler wraps the one-lane atomic into its own cross-lane reduction loop)
     if (MODE == 3) asm volatile("" : "+v"(slot));
 
@@ -302,7 +340,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
         uint64_t mask = __ballot(have && egs_block_hits(c0, c1, c2, (uint32_t)qx0, qx1, (uint32_t)qy0, qy1));
         if (mask == 0ull) continue;
-        my[lane * 3 + 0] = c0; my[lane * 3 + 1] = c1; my[lane * 3 + 2] = c2;
+        my[lane] = c0; my[64 + lane] = c1; my_half[lane] = make_float2(c2.x, c2.y);
         __builtin_amdgcn_wave_barrier();
         // entries whose Gaussian is hot (egs_common.h): their sums go to one of the Gaussian's replica lines instead of its own
         const uint32_t my_code = egs_hot_code(__float_as_uint(c2.z), __float_as_uint(c2.w));
@@ -323,8 +361,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 }
                 remaining--;
             })
-            const float4 s0 = my[j * 3 + 0], s1 = my[j * 3 + 1];
-            const float2 s2 = *reinterpret_cast<const float2*>(&my[j * 3 + 2]);
+            const float4 s0 = my[j], s1 = my[64 + j];
+            const float2 s2 = my_half[j];
             const float dx = s0.x - pxf, dy = s0.y - pyf;
             // log2 falloff with its intermediates kept: t = qa dx + qb dy, n = qc dy   (same arithmetic as egs_alpha)
             const float m = __fmul_rn(s0.z, dx);
@@ -371,28 +409,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const float v6 = w * g_r, v7 = w * g_g, v8 = w * g_b, v9 = HAS_DA ? w * g_d : 0.f;
 
             EGS_BWD_ABL5(abl_sink += ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)) + (v8 + v9); continue;)
-            // 64-lane sums of v0..v9 (see the header): swap-fold, LDS regroup, quad DPP
+            // 64-lane sums of v0..v9 (see the header): eight rows, LDS regroup, DPP
+            if (ROWS8) {
+                if (HAS_DA) red_write_rows8(red_byte, v0, v1, v2, v3, v4, v5, fold32(v6, v7), fold32(v8, v9));
+                else red_write_rows8(red_byte, v0, v1, v2, v3, v4, v5, v6, fold32(v7, v8));
+            } else {
             myred[0 * 64 + lane] = fold32(v0, v1); myred[1 * 64 + lane] = fold32(v2, v3); myred[2 * 64 + lane] = fold32(v4, v5);
             myred[3 * 64 + lane] = fold32(v6, v7); myred[4 * 64 + lane] = fold32(v8, v9);
             }
-            const float4 pa = red_src[0], pb = red_src[1];
+            }
+            const float4 pa = red_src[ROWS8 ? red_first : 0u], pb = red_src[ROWS8 ? red_first ^ 1u : 1u];
             out = ((pa.x + pa.y) + (pa.z + pa.w)) + ((pb.x + pb.y) + (pb.z + pb.w));
             out = dpp_add<0xB1>(out);       // quad_perm [1,0,3,2]
             out = dpp_add<0x4E>(out);       // quad_perm [2,3,0,1]
+            if (ROWS8) { const float row = dpp_add<0x141>(out); out = whole_row ? row : out; }       // row_half_mirror: the other quad of the lane's eight
             }
             const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)my_id, j);
             if (DET != 0) {                                             // (compile-time; the Gaussian's own line whether it is hot or not)
                 (void)hot_mask; (void)hot_slots;
                 if (slot >= 0) {
                     uint32_t* det_max = reinterpret_cast<uint32_t*>(grad_acc);
-                    const uint32_t word = gid * (uint32_t)EGS_GRAD_STRIDE + (uint32_t)slot;
+                    const uint32_t word = gid * (uint32_t)EGS_DET_STRIDE + (uint32_t)slot;
                     if (DET == 1) atomicMax(det_max + word, egs_det_abs_bits(out));
                     else atomicAdd(reinterpret_cast<unsigned long long*>(det_max + hot_base) + word, (unsigned long long)egs_det_encode(out, det_max[word]));
                 }
                 continue;
             }
-            EGS_BWD_ABL7(my[j * 3 + 2])
-            uint32_t line = gid * (uint32_t)EGS_GRAD_STRIDE;            // first float of the accumulator line (48 P < 2^32 bytes: P < 89 M)
+            EGS_BWD_ABL7(make_float4(0.f, 0.f, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(c2.z), j)),
+                                     __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(c2.w), j))))      // (the box words are not staged)
+            uint32_t line = gid * (uint32_t)EGS_GRAD_STRIDE;            // first float of the accumulator line (64 P < 2^32 bytes: P < 67 M)
             if ((hot_mask >> j) & 1ull) {                               // (wave-uniform, rare)
                 const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)my_code, j);
                 // replica = the XCD this workgroup runs on (b % 8); the replicas of a Gaussian lie hot_slots lines apart (egs_common.h)
@@ -446,13 +491,13 @@ hipError_t egs_launch_backward_prologue(int P, int W, int H, EgsImgPtrs im, floa
     return hipGetLastError();
 }
 
-// The deterministic mode's third step: the int64 sums of every (Gaussian, slot) as float32 in the accumulator's regular lines -- all twelve slots of
-// all P lines, visited or not (an untouched pair decodes to 0), so the per-Gaussian kernels behind the blend read what they always read.  The float
+// The deterministic mode's third step: the int64 sums of every (Gaussian, slot) as float32 in the accumulator's regular lines -- the first twelve slots
+// (EGS_DET_STRIDE) of all P lines, visited or not (an untouched pair decodes to 0), so the per-Gaussian kernels behind the blend read what they always read.  The float
 // replica lines keep the zeros the prologue gave them.
 namespace {
 __global__ __launch_bounds__(256) void k_det_decode(size_t n, const uint32_t* __restrict__ det_max, const int64_t* __restrict__ det_sum, float* __restrict__ grad_acc) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) grad_acc[i] = egs_det_decode(det_sum[i], det_max[i]);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;      // det word EGS_DET_STRIDE g + s -> float word EGS_GRAD_STRIDE g + s (the float line's other words keep their zeros)
+    if (i < n) { const size_t g = i / EGS_DET_STRIDE; grad_acc[g * EGS_GRAD_STRIDE + (i - g * EGS_DET_STRIDE)] = egs_det_decode(det_sum[i], det_max[i]); }
 }
 }  // namespace
 hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsGeomPtrs g, const uint32_t* point_list,
@@ -472,7 +517,7 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
               if (lg->lab) lgk.lab = *lg->lab; }
 #define EGS_BWD_LAUNCH_DET(MODE, LGF, DET, ACC) hipLaunchKernelGGL((k_render_backward<MODE, LGF, DET>), dim3(egs_blocks_for_tiles(n_tiles)), dim3(256), 0, s, W, H, gx, n_tiles, \
                            im.ranges, point_list, g.rec, bg, im.final_T, im.n_contrib, dL_dcolor, dL_ddepth, dL_dalpha, \
-                           im.tile_order, ACC, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * EGS_GRAD_STRIDE), (uint32_t)egs_hot_slots((size_t)P), lgk)
+                           im.tile_order, ACC, im.quad_pairs + (size_t)4 * n_tiles, (uint32_t)((size_t)P * ((DET) ? EGS_DET_STRIDE : EGS_GRAD_STRIDE)), (uint32_t)egs_hot_slots((size_t)P), lgk)
     // det_lines (EGS_CALL_DETERMINISTIC): the maxima pass, the integer-sum pass, then the lines decoded into the float accumulator
 #define EGS_BWD_LAUNCH(MODE, LGF) do { if (!det_lines) EGS_BWD_LAUNCH_DET(MODE, LGF, 0, grad_acc); else { \
                            EGS_BWD_LAUNCH_DET(MODE, LGF, 1, (float*)det_lines); EGS_BWD_LAUNCH_DET(MODE, LGF, 2, (float*)det_lines); } } while (0)
@@ -484,7 +529,7 @@ hipError_t egs_launch_render_backward(int P, int W, int H, const float* bg, EgsG
     else if (lg) EGS_BWD_LAUNCH(1, true);
     else EGS_BWD_LAUNCH(1, false);
     if (det_lines) {
-        const size_t n = (size_t)P * EGS_GRAD_STRIDE;
+        const size_t n = (size_t)P * EGS_DET_STRIDE;
         hipLaunchKernelGGL(k_det_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, (const uint32_t*)det_lines,
                            (const int64_t*)((const uint32_t*)det_lines + n), grad_acc);
     }

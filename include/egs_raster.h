@@ -107,7 +107,7 @@ int         egs_device_info(char* name, int name_len, char* arch, int arch_len, 
 size_t egs_geom_bytes(int P);
 size_t egs_binning_bytes(int P, int64_t R, int width, int height);
 size_t egs_image_bytes(int width, int height);
-size_t egs_backward_scratch_bytes(int P);
+size_t egs_backward_scratch_bytes(int P);      /* the scratch itself: 64-byte aligned (one 64-byte accumulator line per Gaussian; EGS_ERR_ARG otherwise) */
 /* the same for a backward called with `flags` (EGS_CALL_* bits): == egs_backward_scratch_bytes(P) unless EGS_CALL_DETERMINISTIC is among them,
  * which adds the mode's lines (12 P uint32 maxima + 12 P int64 sums, rounded up to 256 bytes) behind the float accumulator */
 size_t egs_backward_scratch_bytes_ex(int P, int flags);

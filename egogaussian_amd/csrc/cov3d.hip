@@ -8,22 +8,9 @@
 // `L @ L.transpose`, a 500k-batch 3x3 GEMM that rocBLAS runs for milliseconds).  Here: one streaming kernel each way,
 // 28 B in / 24 B out per Gaussian forward, 52 B in / 28 B out backward; HBM-bound.
 #include "egs_common.h"
+#include "splat_geom.h"          // the chain itself: the one text preprocess.hip's in-rasterizer rotation runs too
 
 namespace {
-
-__device__ __forceinline__ void rot_from_unit_quat(const float* q, float* R) {
-    const float r = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - r * z); R[2] = 2.f * (x * z + r * y);
-    R[3] = 2.f * (x * y + r * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - r * x);
-    R[6] = 2.f * (x * z - r * y); R[7] = 2.f * (y * z + r * x); R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-__device__ __forceinline__ void mat3_mul(const float* A, const float* B, float* C) {      // C = A B
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
 
 // `log_scaling`: the scaling tensor holds the RAW parameters (log of the scales, /root/reference/scene/gaussian_model.py:36
 // scaling_activation = torch.exp); the exponential and its derivative are then applied here instead of by two more
@@ -36,32 +23,10 @@ __global__ __launch_bounds__(256) void k_cov3d_forward(int N, const float* __res
     if (i >= N) return;
     if (opacity_raw) opacity[i] = 1.f / (1.f + expf(-opacity_raw[i]));           // opacity_activation = torch.sigmoid (gaussian_model.py:40)
     float q[4] = { rotation[4 * i], rotation[4 * i + 1], rotation[4 * i + 2], rotation[4 * i + 3] };
-    const float inv = 1.f / sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] *= inv; q[1] *= inv; q[2] *= inv; q[3] *= inv;
-    float R[9]; rot_from_unit_quat(q, R);
     float s3[3] = { scaling[3 * i], scaling[3 * i + 1], scaling[3 * i + 2] };
-    if (log_scaling) { s3[0] = expf(s3[0]); s3[1] = expf(s3[1]); s3[2] = expf(s3[2]); }
-    const float sc[3] = { mod * s3[0], mod * s3[1], mod * s3[2] };
-    float L[9];
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) L[3 * a + k] = R[3 * a + k] * sc[k];
-    if (M && (!sel || sel[i])) {
-        float Mm[9], L2[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) Mm[k] = M[k];
-        mat3_mul(Mm, L, L2);
-#pragma unroll
-        for (int k = 0; k < 9; k++) L[k] = L2[k];
-    }
-    float* o = cov + 6 * (size_t)i;
-    o[0] = L[0] * L[0] + L[1] * L[1] + L[2] * L[2];
-    o[1] = L[0] * L[3] + L[1] * L[4] + L[2] * L[5];
-    o[2] = L[0] * L[6] + L[1] * L[7] + L[2] * L[8];
-    o[3] = L[3] * L[3] + L[4] * L[4] + L[5] * L[5];
-    o[4] = L[3] * L[6] + L[4] * L[7] + L[5] * L[8];
-    o[5] = L[6] * L[6] + L[7] * L[7] + L[8] * L[8];
+    float inv; activate_scale_rot(log_scaling != 0, true, s3, q, inv);
+    CovFactor f; cov_factor(s3, mod, q, M && (!sel || sel[i]), M, f);
+    cov_from_factor(f.L, cov + 6 * (size_t)i);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -87,65 +52,20 @@ __global__ __launch_bounds__(256) void k_cov3d_backward(int N, const float* __re
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     float gM[9] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
     if (i < N) {
-        const float q0[4] = { rotation[4 * i], rotation[4 * i + 1], rotation[4 * i + 2], rotation[4 * i + 3] };
-        const float inv = 1.f / sqrtf(q0[0] * q0[0] + q0[1] * q0[1] + q0[2] * q0[2] + q0[3] * q0[3]);
-        const float q[4] = { q0[0] * inv, q0[1] * inv, q0[2] * inv, q0[3] * inv };
-        float R[9]; rot_from_unit_quat(q, R);
+        float q[4] = { rotation[4 * i], rotation[4 * i + 1], rotation[4 * i + 2], rotation[4 * i + 3] };
         float s3[3] = { scaling[3 * i], scaling[3 * i + 1], scaling[3 * i + 2] };
-        if (log_scaling) { s3[0] = expf(s3[0]); s3[1] = expf(s3[1]); s3[2] = expf(s3[2]); }
-        const float sc[3] = { mod * s3[0], mod * s3[1], mod * s3[2] };
-        float L0[9], L[9];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int k = 0; k < 3; k++) L0[3 * a + k] = R[3 * a + k] * sc[k];
+        float inv; activate_scale_rot(log_scaling != 0, true, s3, q, inv);
         const bool moved = M && (!sel || sel[i]);
-        float Mm[9];
-        if (moved) {
-#pragma unroll
-            for (int k = 0; k < 9; k++) Mm[k] = M[k];
-            mat3_mul(Mm, L0, L);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 9; k++) L[k] = L0[k];
-        }
+        CovFactor f; cov_factor(s3, mod, q, moved, M, f);
         const float* g6 = dcov + 6 * (size_t)i;
-        const float Gs[9] = { g6[0], 0.5f * g6[1], 0.5f * g6[2], 0.5f * g6[1], g6[3], 0.5f * g6[4], 0.5f * g6[2], 0.5f * g6[4], g6[5] };
-        float gL[9];                                                   // dL/dL = 2 Gs L
-        mat3_mul(Gs, L, gL);
         const float mult = (moved && i == 0) ? (row0_mult_dev ? row0_mult_dev[0] : row0_mult) : 1.f;   // the reference's duplicated-index gradient (covariance.py)
+        CovGrad g; cov_factor_backward(f, s3, mod, q, inv, moved, M, g6, mult, true, log_scaling != 0, true, g);
 #pragma unroll
-        for (int k = 0; k < 9; k++) gL[k] *= 2.f * mult;
-        float gL0[9];
-        if (moved) {
+        for (int k = 0; k < 9; k++) gM[k] = g.dM[k];
 #pragma unroll
-            for (int a = 0; a < 3; a++)
+        for (int k = 0; k < 3; k++) dscaling[3 * i + k] = g.dscale[k];   // d/d raw = d/d scale * exp(raw) under log_scaling
 #pragma unroll
-                for (int b = 0; b < 3; b++) {
-                    gM[3 * a + b] = gL[3 * a] * L0[3 * b] + gL[3 * a + 1] * L0[3 * b + 1] + gL[3 * a + 2] * L0[3 * b + 2];   // gL L0^T
-                    gL0[3 * a + b] = Mm[a] * gL[b] + Mm[3 + a] * gL[3 + b] + Mm[6 + a] * gL[6 + b];                          // M^T gL
-                }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 9; k++) gL0[k] = gL[k];
-        }
-        float gR[9];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float ds = mod * (gL0[k] * R[k] + gL0[3 + k] * R[3 + k] + gL0[6 + k] * R[6 + k]);
-            dscaling[3 * i + k] = log_scaling ? ds * s3[k] : ds;           // d/d raw = d/d scale * exp(raw)
-#pragma unroll
-            for (int a = 0; a < 3; a++) gR[3 * a + k] = gL0[3 * a + k] * sc[k];
-        }
-        const float r = q[0], x = q[1], y = q[2], z = q[3];
-        float gq[4];
-        gq[0] = 2.f * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
-        gq[1] = 2.f * (y * gR[1] + z * gR[2] + y * gR[3] - 2.f * x * gR[4] - r * gR[5] + z * gR[6] + r * gR[7] - 2.f * x * gR[8]);
-        gq[2] = 2.f * (-2.f * y * gR[0] + x * gR[1] + r * gR[2] + x * gR[3] + z * gR[5] - r * gR[6] + z * gR[7] - 2.f * y * gR[8]);
-        gq[3] = 2.f * (-2.f * z * gR[0] - r * gR[1] + x * gR[2] + r * gR[3] - 2.f * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
-        const float dot = q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];      // back through q/|q|
-#pragma unroll
-        for (int k = 0; k < 4; k++) drotation[4 * i + k] = (gq[k] - q[k] * dot) * inv;
+        for (int k = 0; k < 4; k++) drotation[4 * i + k] = g.gq[k];
     }
     // d/dM is a sum over every Gaussian.  One float atomic per wave and component (70k device-scope atomics on nine words
     // of one cache line at 500k Gaussians) serialises at the memory side: 896 us for this kernel instead of 9.  Workgroup

@@ -21,100 +21,18 @@
 #include "object_motion.h"          // the rigid object motion of the positions (EGS_ACT_OBJECT_MOTION)
 #include "opacity_entropy.h"        // the opacity-entropy term joins dL/dopacity in k_preprocess_backward<.., ENT = true>
 #include "sh_basis.h"               // colour of the inline M = 1 harmonics, forward and backward
+#include "splat_geom.h"             // transforms, covariance chain (shared with cov3d.hip) and EWA projection
 #include <type_traits>
 
 namespace {
 
-__device__ __forceinline__ void xform43(const float* p, const float* m, float* o) {
-    o[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
-    o[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
-    o[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
-}
-__device__ __forceinline__ void xform44(const float* p, const float* m, float* o) {
-    o[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
-    o[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
-    o[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
-    o[3] = m[3] * p[0] + m[7] * p[1] + m[11] * p[2] + m[15];
-}
-
-__device__ __forceinline__ void quat_to_rot(const float* q, float* R) {
-    float r = q[0], x = q[1], y = q[2], z = q[3];
-    R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - r * z); R[2] = 2.f * (x * z + r * y);
-    R[3] = 2.f * (x * y + r * z); R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - r * x);
-    R[6] = 2.f * (x * z - r * y); R[7] = 2.f * (y * z + r * x); R[8] = 1.f - 2.f * (x * x + y * y);
-}
-
-// cov3D = (R S)(R S)^T, six unique entries (00,01,02,11,12,22); quaternion used as given.
-// Mrot != NULL: the object rotation of the `fine_all` call shape, L <- M L, with the operation order of cov3d.hip (k_cov3d_forward), so
-// that the covariance -- hence radii, rectangles, sort order -- is the one the stand-alone producer would have handed over.
-__device__ __forceinline__ void cov3d_from_scale_rot(const float* s, float mod, const float* q, float* c6, const float* Mrot = nullptr) {
-    float R[9]; quat_to_rot(q, R);
-    float sc[3] = { mod * s[0], mod * s[1], mod * s[2] };
-    float L[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) L[3 * i + k] = R[3 * i + k] * sc[k];
-    if (Mrot) {
-        float L2[9];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) L2[3 * i + j] = Mrot[3 * i] * L[j] + Mrot[3 * i + 1] * L[3 + j] + Mrot[3 * i + 2] * L[6 + j];
-#pragma unroll
-        for (int k = 0; k < 9; k++) L[k] = L2[k];
-    }
-    c6[0] = L[0] * L[0] + L[1] * L[1] + L[2] * L[2];
-    c6[1] = L[0] * L[3] + L[1] * L[4] + L[2] * L[5];
-    c6[2] = L[0] * L[6] + L[1] * L[7] + L[2] * L[8];
-    c6[3] = L[3] * L[3] + L[4] * L[4] + L[5] * L[5];
-    c6[4] = L[3] * L[6] + L[4] * L[7] + L[5] * L[8];
-    c6[5] = L[6] * L[6] + L[7] * L[7] + L[8] * L[8];
-}
-
-// Raw-parameter mode (EGS_ACT_*, egs_common.h): the model's activations -- exp on the scales, normalisation of the
-// quaternion, sigmoid on the opacity (/root/reference/scene/gaussian_model.py:36-44) -- applied in place of separate
-// PyTorch launches.  `qinv` returns 1/|q_raw| for the backward.
-__device__ __forceinline__ void activate_scale_rot(int act, float* s, float* q, float& qinv) {
-    if (act & EGS_ACT_LOG_SCALES) { s[0] = expf(s[0]); s[1] = expf(s[1]); s[2] = expf(s[2]); }
-    qinv = 1.f;
-    if (act & EGS_ACT_RAW_QUATS) {
-        qinv = 1.f / sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        q[0] *= qinv; q[1] *= qinv; q[2] *= qinv; q[3] *= qinv;
-    }
-}
-
-// Everything the forward and backward share: camera-space point, clamped Jacobian rows (J R), Sigma*m.
-struct Ewa {
-    float t[3], tx, ty, txtz, tytz, limx, limy, fx, fy;
-    float m0[3], m1[3], S0[3], S1[3], a, b, c;
+// What both forward kernels are given: the scene, the camera, and the arrays the projection writes.
+struct EgsPreArgs {
+    int P, D, M; const float* means3D; const float* shs; const float* colors; const float* opac; const float* scales; float mod;
+    const float* rots; const float* cov3D_in; int act; const float* V; const float* PM; const float* campos; int W, H; float tanfovx, tanfovy;
+    int32_t* radii; float4* rec; uint2* rect_out; uint32_t* tiles_touched; uint8_t* clamped_out; uint8_t* visible;
+    uint32_t* block_sums; uint32_t* block_hot; const int32_t* active_count;
 };
-__device__ __forceinline__ void ewa_project(const float* p, const float* c6, const float* V, int W, int H,
-                                            float tanfovx, float tanfovy, Ewa& e) {
-    xform43(p, V, e.t);
-    e.fx = (float)W / (2.f * tanfovx); e.fy = (float)H / (2.f * tanfovy);
-    e.limx = 1.3f * tanfovx; e.limy = 1.3f * tanfovy;
-    e.txtz = e.t[0] / e.t[2]; e.tytz = e.t[1] / e.t[2];
-    e.tx = fminf(e.limx, fmaxf(-e.limx, e.txtz)) * e.t[2];
-    e.ty = fminf(e.limy, fmaxf(-e.limy, e.tytz)) * e.t[2];
-    float j00 = e.fx / e.t[2], j02 = -(e.fx * e.tx) / (e.t[2] * e.t[2]);
-    float j11 = e.fy / e.t[2], j12 = -(e.fy * e.ty) / (e.t[2] * e.t[2]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        e.m0[k] = j00 * V[4 * k + 0] + j02 * V[4 * k + 2];
-        e.m1[k] = j11 * V[4 * k + 1] + j12 * V[4 * k + 2];
-    }
-    e.S0[0] = c6[0] * e.m0[0] + c6[1] * e.m0[1] + c6[2] * e.m0[2];
-    e.S0[1] = c6[1] * e.m0[0] + c6[3] * e.m0[1] + c6[4] * e.m0[2];
-    e.S0[2] = c6[2] * e.m0[0] + c6[4] * e.m0[1] + c6[5] * e.m0[2];
-    e.S1[0] = c6[0] * e.m1[0] + c6[1] * e.m1[1] + c6[2] * e.m1[2];
-    e.S1[1] = c6[1] * e.m1[0] + c6[3] * e.m1[1] + c6[4] * e.m1[2];
-    e.S1[2] = c6[2] * e.m1[0] + c6[4] * e.m1[1] + c6[5] * e.m1[2];
-    e.a = e.m0[0] * e.S0[0] + e.m0[1] * e.S0[1] + e.m0[2] * e.S0[2] + 0.3f;
-    e.b = e.m0[0] * e.S1[0] + e.m0[1] * e.S1[1] + e.m0[2] * e.S1[2];
-    e.c = e.m1[0] * e.S1[0] + e.m1[1] * e.S1[1] + e.m1[2] * e.S1[2] + 0.3f;
-}
-
 struct PreOut { uint2 rect; float4 r0, r1, r2; };
 // Returns the number of tiles the Gaussian touches (0 = culled).
 // MOTION: a moved row is placed first, p <- A p + b (object_motion.h), and everything below sees the placed position.
@@ -141,11 +59,13 @@ __device__ __forceinline__ uint32_t preprocess_one(
     } else {
         float s[3] = { scales[3 * i], scales[3 * i + 1], scales[3 * i + 2] };
         float q[4] = { rots[4 * i], rots[4 * i + 1], rots[4 * i + 2], rots[4 * i + 3] };
-        float qinv; activate_scale_rot(act, s, q, qinv);
-        cov3d_from_scale_rot(s, mod, q, c6, (rot.M && (!rot.sel || rot.sel[i])) ? rot.M : nullptr);
+        float qinv; activate_scale_rot(act & EGS_ACT_LOG_SCALES, act & EGS_ACT_RAW_QUATS, s, q, qinv);
+        // the object rotation of the `fine_all` call shape: L <- M L, the text k_cov3d_forward runs (splat_geom.h)
+        CovFactor f; cov_factor(s, mod, q, rot.M && (!rot.sel || rot.sel[i]), rot.M, f);
+        cov_from_factor(f.L, c6);
     }
     Ewa e; ewa_project(p, c6, V, W, H, tanfovx, tanfovy, e);
-    if (e.t[2] <= 0.2f) return 0u;                                // near-plane cull
+    if (e.t[2] <= 0.2f) return 0u;                              // near-plane cull
     float hom[4]; xform44(p, PM, hom);
     const float pw = 1.f / (hom[3] + 0.0000001f);
     const float ndc_x = hom[0] * pw, ndc_y = hom[1] * pw;
@@ -220,45 +140,25 @@ __device__ __forceinline__ uint32_t preprocess_one(
     return (uint32_t)((rx1 - rx0) * (ry1 - ry0));
 }
 
-// PLACE: the first eight workgroups do not preprocess anything -- each orders one XCD band of the forward blend's tiles by the
-// costs the image buffer holds (backward_prologue.h), a job that needs doing before that blend and fits under this launch.
-template <bool PLACE, bool MOTION>
-__global__ __launch_bounds__(256) void k_preprocess(
-    int P, int D, int M, const float* __restrict__ means3D, const float* __restrict__ shs,
-    const float* __restrict__ colors, const float* __restrict__ opac, const float* __restrict__ scales, float mod,
-    const float* __restrict__ rots, const float* __restrict__ cov3D_in, int act, const float* __restrict__ V,
-    const float* __restrict__ PM, const float* __restrict__ campos, int W, int H, float tanfovx, float tanfovy,
-    int32_t* __restrict__ radii, float4* __restrict__ rec, uint2* __restrict__ rect_out,
-    uint32_t* __restrict__ tiles_touched, uint8_t* __restrict__ clamped_out, uint8_t* __restrict__ visible,
-    uint32_t* __restrict__ block_sums, uint32_t* __restrict__ block_hot, uint32_t* __restrict__ zero_words, size_t zero_n,
-    const int32_t* __restrict__ active_count, EgsPrologueArgs place, EgsObjRot rot, EgsMotion mot) {
-    __shared__ uint32_t wsum[4], whot[4];
-    if (PLACE) {
-        __shared__ EgsOrderLds order_lds;
-        if (blockIdx.x < EGS_XCDS) { egs_order_band<256>(place, (int)blockIdx.x, order_lds); return; }
-    }
-    const unsigned bid = blockIdx.x - (PLACE ? EGS_XCDS : 0u), nblk = gridDim.x - (PLACE ? EGS_XCDS : 0u);
-    const int i = (int)(bid * blockDim.x + threadIdx.x);
-    for (size_t z = (size_t)i; z < zero_n; z += (size_t)nblk * blockDim.x) zero_words[z] = 0u;   // on the side (egs_common.h)
-    uint32_t my_tiles = 0;
-    // capacity-sized models (include/egs_raster.h): rows at and beyond the device-side live count are culled whatever they hold
-    const int live = active_count ? min(P, max(*active_count, 0)) : P;
-    if (i >= live && i < P) { radii[i] = 0; tiles_touched[i] = 0; visible[i] = 0; }
-    bool hot = false;
-    if (i < live) my_tiles = preprocess_one<MOTION>(i, D, M, means3D, shs, colors, opac, scales, mod, rots, cov3D_in, act, V, PM, campos, W, H,
-                                         tanfovx, tanfovy, radii, rec, rect_out, tiles_touched, clamped_out, visible, rot, mot, hot);
-    hot = hot && my_tiles != 0;
-    const uint64_t hot_wave = __ballot(hot);
-    // per-block instance count; the host adds the block sums to get R (no contended atomic, deterministic)
+// The tail of a 256-Gaussian block in both forward kernels, in two halves around the caller's barrier.  Before it: a wave's instance count and
+// hot count go to wsum / whot.  After it: the block's first wave w0 (0 in k_preprocess, w & ~3 in k_preprocess_count) writes the per-block
+// instance count -- the host adds the block sums to get R (no contended atomic, deterministic) -- and the hot count; a hot Gaussian takes its
+// rank among the block's hot ones -> the code that names its replica lines (egs_common.h; few per frame).
+__device__ __forceinline__ void pp_tail_publish(uint32_t my_tiles, uint64_t hot_wave, unsigned w, unsigned lane, uint32_t* wsum, uint32_t* whot) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) my_tiles += (uint32_t)__shfl_xor((int)my_tiles, d, 64);
-    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = my_tiles; whot[threadIdx.x >> 6] = (uint32_t)__popcll(hot_wave); }
-    __syncthreads();
-    if (threadIdx.x == 0) { block_sums[bid] = wsum[0] + wsum[1] + wsum[2] + wsum[3]; block_hot[bid] = min(whot[0] + whot[1] + whot[2] + whot[3], EGS_HOT_PER_BLOCK); }
-    if (hot) {   // rank among the workgroup's hot Gaussians -> the code that names this one's replica lines (egs_common.h); few per frame
-        const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { wsum[w] = my_tiles; whot[w] = (uint32_t)__popcll(hot_wave); }
+}
+__device__ __forceinline__ void pp_tail_finish(const uint32_t* wsum, const uint32_t* whot, unsigned w0, unsigned w, unsigned lane, bool first, unsigned blk, int i, bool hot,
+                                               uint64_t hot_wave, float4* __restrict__ rec, uint8_t* __restrict__ clamped_out,
+                                               uint32_t* __restrict__ block_sums, uint32_t* __restrict__ block_hot) {
+    if (first) {
+        block_sums[blk] = wsum[w0] + wsum[w0 + 1] + wsum[w0 + 2] + wsum[w0 + 3];
+        block_hot[blk] = min(whot[w0] + whot[w0 + 1] + whot[w0 + 2] + whot[w0 + 3], EGS_HOT_PER_BLOCK);
+    }
+    if (hot) {
         uint32_t rank = (uint32_t)__popcll(hot_wave & (lane ? (~0ull >> (64 - lane)) : 0ull));
-        for (unsigned k = 0; k < w; k++) rank += whot[k];
+        for (unsigned k = w0; k < w; k++) rank += whot[k];
         if (rank < EGS_HOT_PER_BLOCK) {
             float4* r2 = rec + (size_t)i * EGS_SPLAT_REC_F4 + 2;
             uint32_t bbx = __float_as_uint(r2->z), bby = __float_as_uint(r2->w);
@@ -269,6 +169,32 @@ __global__ __launch_bounds__(256) void k_preprocess(
     }
 }
 
+// PLACE: the first eight workgroups do not preprocess anything -- each orders one XCD band of the forward blend's tiles by the
+// costs the image buffer holds (backward_prologue.h), a job that needs doing before that blend and fits under this launch.
+template <bool PLACE, bool MOTION>
+__global__ __launch_bounds__(256) void k_preprocess(EgsPreArgs a, uint32_t* __restrict__ zero_words, size_t zero_n, EgsPrologueArgs place, EgsObjRot rot, EgsMotion mot) {
+    __shared__ uint32_t wsum[4], whot[4];
+    if (PLACE) {
+        __shared__ EgsOrderLds order_lds;
+        if (blockIdx.x < EGS_XCDS) { egs_order_band<256>(place, (int)blockIdx.x, order_lds); return; }
+    }
+    const unsigned bid = blockIdx.x - (PLACE ? EGS_XCDS : 0u), nblk = gridDim.x - (PLACE ? EGS_XCDS : 0u);
+    const int i = (int)(bid * blockDim.x + threadIdx.x);
+    for (size_t z = (size_t)i; z < zero_n; z += (size_t)nblk * blockDim.x) zero_words[z] = 0u;   // on the side (egs_common.h)
+    uint32_t my_tiles = 0;
+    // capacity-sized models (include/egs_raster.h): rows at and beyond the device-side live count are culled whatever they hold
+    const int P = a.P, live = a.active_count ? min(P, max(*a.active_count, 0)) : P;
+    if (i >= live && i < P) { a.radii[i] = 0; a.tiles_touched[i] = 0; a.visible[i] = 0; }
+    bool hot = false;
+    if (i < live) my_tiles = preprocess_one<MOTION>(i, a.D, a.M, a.means3D, a.shs, a.colors, a.opac, a.scales, a.mod, a.rots, a.cov3D_in, a.act, a.V, a.PM, a.campos,
+                                                     a.W, a.H, a.tanfovx, a.tanfovy, a.radii, a.rec, a.rect_out, a.tiles_touched, a.clamped_out, a.visible, rot, mot, hot);
+    hot = hot && my_tiles != 0;
+    const uint64_t hot_wave = __ballot(hot);
+    pp_tail_publish(my_tiles, hot_wave, threadIdx.x >> 6, threadIdx.x & 63, wsum, whot);
+    __syncthreads();
+    pp_tail_finish(wsum, whot, 0u, threadIdx.x >> 6, threadIdx.x & 63, threadIdx.x == 0, bid, i, hot, hot_wave, a.rec, a.clamped_out, a.block_sums, a.block_hot);
+}
+
 // k_preprocess and the COUNT pass of the tile bucketing (binning.hip k_bin_count) in one launch.  The count pass's workgroup is a chain
 // of latencies -- launch, set-up loads (~4 us with every workgroup asking at once), walk, flush -- of which the first two only fetch
 // what k_preprocess had in registers a launch earlier (profiles/r5_bucketing_experiments.md); here wave w of a 16-wave workgroup
@@ -277,12 +203,6 @@ __global__ __launch_bounds__(256) void k_preprocess(
 // Blocks of 256 Gaussians are dealt to workgroups (bin_walk.h): the per-block instance and hot counts are those of k_preprocess
 // (block B = Gaussians 256 B .. 256 B + 255; waves 4 m .. 4 m + 3 of a round hold one block).  Needs gpr % 4 == 0 (egs_can_fuse_count).
 // PLACE: the first eight workgroups order the forward blend's tiles instead (as in k_preprocess), in the dynamic LDS block.
-struct EgsPreArgs {
-    int P, D, M; const float* means3D; const float* shs; const float* colors; const float* opac; const float* scales; float mod;
-    const float* rots; const float* cov3D_in; int act; const float* V; const float* PM; const float* campos; int W, H; float tanfovx, tanfovy;
-    int32_t* radii; float4* rec; uint2* rect_out; uint32_t* tiles_touched; uint8_t* clamped_out; uint8_t* visible;
-    uint32_t* block_sums; uint32_t* block_hot; const int32_t* active_count;
-};
 struct EgsCountArgs { int gpr, gx, n_tiles; uint32_t nblocks; int cull, use_map; uint32_t* table; uint32_t stride; uint32_t* chunk_sum; };
 extern __shared__ __attribute__((aligned(16))) uint32_t pc_dyn_lds[];
 // ONE_ROUND: every workgroup's groups fit one round (no loop: what the projection loads is dead before the walk starts -- inside a loop the
@@ -321,31 +241,11 @@ __global__ __launch_bounds__(EGS_BIN_THREADS) __attribute__((amdgpu_waves_per_eu
             hot_wave = __ballot(hot);
             if (my_tiles == 0) { o.rect = make_uint2(0u, 0u); o.r0 = o.r1 = o.r2 = make_float4(0.f, 0.f, 0.f, 0.f); }      // (culled: preprocess_one left `o` alone)
             bin_park_group(L, w, lane, i >= 0 && i < P, my_tiles, o.rect, o.r0, o.r1, o.r2, false, c.cull != 0, c.use_map != 0);
-            uint32_t sum = my_tiles;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
-            if (lane == 0) { wsum[w] = sum; whot[w] = (uint32_t)__popcll(hot_wave); }
+            pp_tail_publish(my_tiles, hot_wave, w, lane, wsum, whot);
         }
         __syncthreads();
-        if ((int)w < c.gpr && i >= 0) {
-            // the 256-Gaussian block of this wave: waves (w & ~3) .. (w & ~3) + 3 of the round (all present: gpr is a multiple of four)
-            const unsigned w0 = w & ~3u, blk = (unsigned)i >> 8;
-            if ((w & 3u) == 0 && lane == 0) {
-                a.block_sums[blk] = wsum[w0] + wsum[w0 + 1] + wsum[w0 + 2] + wsum[w0 + 3];
-                a.block_hot[blk] = min(whot[w0] + whot[w0 + 1] + whot[w0 + 2] + whot[w0 + 3], EGS_HOT_PER_BLOCK);
-            }
-            if (hot) {   // rank among the block's hot Gaussians -> the code that names this one's replica lines (egs_common.h); few per frame
-                uint32_t rank = (uint32_t)__popcll(hot_wave & (lane ? (~0ull >> (64 - lane)) : 0ull));
-                for (unsigned k = w0; k < w; k++) rank += whot[k];
-                if (rank < EGS_HOT_PER_BLOCK) {
-                    float4* r2 = a.rec + (size_t)i * EGS_SPLAT_REC_F4 + 2;
-                    uint32_t bbx = __float_as_uint(r2->z), bby = __float_as_uint(r2->w);
-                    egs_hot_code_set(bbx, bby, rank + 1u);
-                    r2->z = __uint_as_float(bbx); r2->w = __uint_as_float(bby);
-                    a.clamped_out[i] = (uint8_t)((a.clamped_out[i] & EGS_CLAMP_MASK) | ((rank + 1u) << 3));   // where the backward looks for it
-                }
-            }
-        }
+        // the 256-Gaussian block of this wave: waves (w & ~3) .. (w & ~3) + 3 of the round (all present: gpr is a multiple of four)
+        if ((int)w < c.gpr && i >= 0) pp_tail_finish(wsum, whot, w & ~3u, w, lane, (w & 3u) == 0 && lane == 0, (unsigned)i >> 8, i, hot, hot_wave, a.rec, a.clamped_out, a.block_sums, a.block_hot);
         bin_walk_round(L, bid, c.nblocks, g0, c.gpr, c.gx, false, c.cull != 0, c.use_map != 0, a.W, a.H,
                        [&](uint32_t tile, uint32_t, uint32_t) { atomicAdd(&hist[tile], 1u); });
         g0 += (unsigned)c.gpr;
@@ -455,8 +355,9 @@ __device__ __forceinline__ void pp_bwd_one(
     } else {
         s[0] = scales[3 * i]; s[1] = scales[3 * i + 1]; s[2] = scales[3 * i + 2];
         q[0] = rots[4 * i]; q[1] = rots[4 * i + 1]; q[2] = rots[4 * i + 2]; q[3] = rots[4 * i + 3];
-        activate_scale_rot(act, s, q, qinv);
-        cov3d_from_scale_rot(s, mod, q, c6, (rot.M && (!rot.sel || rot.sel[i])) ? rot.M : nullptr);
+        activate_scale_rot(act & EGS_ACT_LOG_SCALES, act & EGS_ACT_RAW_QUATS, s, q, qinv);
+        CovFactor f; cov_factor(s, mod, q, rot.M && (!rot.sel || rot.sel[i]), rot.M, f);
+        cov_from_factor(f.L, c6);
     }
     Ewa e; ewa_project(p, c6, V, W, H, tanfovx, tanfovy, e);
 
@@ -547,77 +448,26 @@ __device__ __forceinline__ void pp_bwd_one(
 
     // cov3D -> scale, quaternion (only when the forward built cov3D itself)
     if (!cov3D_in) {
-        float Rm[9]; quat_to_rot(q, Rm);
-        const float sc[3] = { mod * s[0], mod * s[1], mod * s[2] };
-        const float Gs[9] = { g6[0], 0.5f * g6[1], 0.5f * g6[2], 0.5f * g6[1], g6[3], 0.5f * g6[4],
-                              0.5f * g6[2], 0.5f * g6[4], g6[5] };
-        float L[9], gL[9], gR[9];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int k = 0; k < 3; k++) L[3 * a + k] = Rm[3 * a + k] * sc[k];
-        // object rotation (egs_object_rotation; operation for operation k_cov3d_backward of cov3d.hip): L = M L0, dL/dL0 = M^T dL/dL, and
-        // the reference's duplicated-index multiplier on row 0 (covariance.py)
+        // splat_geom.h, the text k_cov3d_backward runs: under the object rotation (egs_object_rotation) L = M L0, dL/dL0 = M^T dL/dL, with the
+        // reference's duplicated-index multiplier on row 0 (covariance.py)
         const bool moved = rot.M && (!rot.sel || rot.sel[i]);
-        float Mm[9];
-        if (moved) {
-            float L0[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) { Mm[k] = rot.M[k]; L0[k] = L[k]; }
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) L[3 * a + b] = Mm[3 * a] * L0[b] + Mm[3 * a + 1] * L0[3 + b] + Mm[3 * a + 2] * L0[6 + b];
-        }
         const float mult = (moved && i == 0) ? (rot.mult_dev ? rot.mult_dev[0] : rot.mult) : 1.f;
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int k = 0; k < 3; k++)
-                gL[3 * a + k] = (Gs[3 * a] * L[k] + Gs[3 * a + 1] * L[3 + k] + Gs[3 * a + 2] * L[6 + k]) * (2.f * mult);
+        bool want_dM = false;
+        if constexpr (MOT != 0) want_dM = moved && mot.dM_partial;
+        CovFactor f; cov_factor(s, mod, q, moved, rot.M, f);
+        CovGrad g; cov_factor_backward(f, s, mod, q, qinv, moved, rot.M, g6, mult, want_dM, act & EGS_ACT_LOG_SCALES, act & EGS_ACT_RAW_QUATS, g);
         if constexpr (MOT != 0) {
-            if (moved && mot.dM_partial) {                            // dL/dM = gL L0^T, operation for operation k_cov3d_backward's gM (the row-0 multiplier is in gL)
-                float L0[9];
+            if (want_dM) {                                            // dL/dM = gL L0^T (the row-0 multiplier is in gL)
 #pragma unroll
-                for (int a = 0; a < 3; a++)
-#pragma unroll
-                    for (int k = 0; k < 3; k++) L0[3 * a + k] = Rm[3 * a + k] * sc[k];
-#pragma unroll
-                for (int a = 0; a < 3; a++)
-#pragma unroll
-                    for (int b = 0; b < 3; b++)
-                        red[EGS_MOTION_POSE_SUMS + 3 * a + b] = gL[3 * a] * L0[3 * b] + gL[3 * a + 1] * L0[3 * b + 1] + gL[3 * a + 2] * L0[3 * b + 2];
+                for (int k = 0; k < 9; k++) red[EGS_MOTION_POSE_SUMS + k] = g.dM[k];
             }
-        }
-        if (moved) {
-            float g0[9];
-#pragma unroll
-            for (int a = 0; a < 3; a++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) g0[3 * a + b] = Mm[a] * gL[b] + Mm[3 + a] * gL[3 + b] + Mm[6 + a] * gL[6 + b];
-#pragma unroll
-            for (int k = 0; k < 9; k++) gL[k] = g0[k];
         }
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float ds = mod * (gL[k] * Rm[k] + gL[3 + k] * Rm[3 + k] + gL[6 + k] * Rm[6 + k]);
-            const float dsk = (act & EGS_ACT_LOG_SCALES) ? ds * s[k] : ds;                  // d/d log-scale = d/d scale * scale
-            if (dscales) dscales[3 * i + k] = dsk;
-            if (SINK && (fused & (1u << EGS_SINK_SCALES))) stage[ST_SCALES + 3 * tid + k] = dsk;
-#pragma unroll
-            for (int a = 0; a < 3; a++) gR[3 * a + k] = gL[3 * a + k] * sc[k];
+            if (dscales) dscales[3 * i + k] = g.dscale[k];
+            if (SINK && (fused & (1u << EGS_SINK_SCALES))) stage[ST_SCALES + 3 * tid + k] = g.dscale[k];
         }
-        const float r = q[0], qx = q[1], qy = q[2], qz = q[3];
-        float gq[4];
-        gq[0] = 2.f * (-qz * gR[1] + qy * gR[2] + qz * gR[3] - qx * gR[5] - qy * gR[6] + qx * gR[7]);
-        gq[1] = 2.f * (qy * gR[1] + qz * gR[2] + qy * gR[3] - 2.f * qx * gR[4] - r * gR[5] + qz * gR[6] + r * gR[7] - 2.f * qx * gR[8]);
-        gq[2] = 2.f * (-2.f * qy * gR[0] + qx * gR[1] + r * gR[2] + qx * gR[3] + qz * gR[5] - r * gR[6] + qz * gR[7] - 2.f * qy * gR[8]);
-        gq[3] = 2.f * (-2.f * qz * gR[0] - r * gR[1] + qx * gR[2] + r * gR[3] - 2.f * qz * gR[4] + qy * gR[5] + qx * gR[6] + qy * gR[7]);
-        if (act & EGS_ACT_RAW_QUATS) {                                  // back through q = q_raw / |q_raw|
-            const float dot = q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];
-#pragma unroll
-            for (int k = 0; k < 4; k++) gq[k] = (gq[k] - q[k] * dot) * qinv;
-        }
+        const float* gq = g.gq;
         if (drots) { drots[4 * i + 0] = gq[0]; drots[4 * i + 1] = gq[1]; drots[4 * i + 2] = gq[2]; drots[4 * i + 3] = gq[3]; }
         if (SINK && (fused & (1u << EGS_SINK_ROTATIONS))) *reinterpret_cast<float4*>(stage + ST_ROTS + 4 * tid) = make_float4(gq[0], gq[1], gq[2], gq[3]);
     }
@@ -753,8 +603,8 @@ hipError_t egs_launch_zero_f4(float4* p, size_t n4, hipStream_t s) {
 // kernel is given (NULL when the spherical harmonics run as launches of their own, and for the backward of precomputed colours).
 #define PP_SCENE sc.P, sc.D, sc.M, sc.means3D, shs
 #define PP_SHAPE_CAM sc.scales, sc.mod, sc.rots, sc.cov3D, sc.act, cam.view, cam.proj, cam.campos, cam.W, cam.H, cam.tanfovx, cam.tanfovy, radii
-// k_preprocess's loose parameters up to the region it clears; member for member the EgsPreArgs of k_preprocess_count up to active_count
-#define PP_ARGS PP_SCENE, sc.colors, sc.opac, PP_SHAPE_CAM, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot
+// the record of the forward kernels, member for member
+#define PP_ARGS(active_count) { PP_SCENE, sc.colors, sc.opac, PP_SHAPE_CAM, g.rec, g.rect, g.offsets, g.clamped, g.visible, g.scan_scratch, g.block_hot, active_count }
 
 hipError_t egs_launch_preprocess(const EgsScene& sc, EgsCamera cam, int32_t* radii, EgsGeomPtrs g, uint32_t* zero_words, size_t zero_n,
                                  const int32_t* active_count, const EgsImgPtrs* place, EgsObjRot rot, EgsMotion mot, hipStream_t s) {
@@ -762,15 +612,16 @@ hipError_t egs_launch_preprocess(const EgsScene& sc, EgsCamera cam, int32_t* rad
     if (P == 0) return hipSuccess;
     if (!zero_words) zero_n = 0;
     const float* shs = egs_sh_apart(sc) ? nullptr : sc.shs;
+    const EgsPreArgs a = PP_ARGS(active_count);
     EgsPrologueArgs pa = {};
     if (place) {
         pa.n_tiles = (int)egs_tiles(cam.W, cam.H);
         pa.quad_work = place->fwd_cost; pa.tile_order = place->fwd_order;
-        if (mot.A) hipLaunchKernelGGL((k_preprocess<true, true>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess<true, false>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<true, true>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, a, zero_words, zero_n, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<true, false>), dim3((P + 255) / 256 + EGS_XCDS), dim3(256), 0, s, a, zero_words, zero_n, pa, rot, mot);
     } else {
-        if (mot.A) hipLaunchKernelGGL((k_preprocess<false, true>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
-        else hipLaunchKernelGGL((k_preprocess<false, false>), dim3((P + 255) / 256), dim3(256), 0, s, PP_ARGS, zero_words, zero_n, active_count, pa, rot, mot);
+        if (mot.A) hipLaunchKernelGGL((k_preprocess<false, true>), dim3((P + 255) / 256), dim3(256), 0, s, a, zero_words, zero_n, pa, rot, mot);
+        else hipLaunchKernelGGL((k_preprocess<false, false>), dim3((P + 255) / 256), dim3(256), 0, s, a, zero_words, zero_n, pa, rot, mot);
     }
     return hipGetLastError();
 }
@@ -789,7 +640,7 @@ hipError_t egs_launch_preprocess_count(const EgsScene& sc, EgsCamera cam, int32_
     const int P = sc.P;
     const EgsBinGeometry q = egs_bin_geometry(P, cam.W, cam.H, cull);
     const float* shs = egs_sh_apart(sc) ? nullptr : sc.shs;
-    EgsPreArgs a = { PP_ARGS, active_count };
+    const EgsPreArgs a = PP_ARGS(active_count);
     EgsCountArgs c = { q.gpr, q.gx, q.n_tiles, q.nblocks, q.cull, q.use_map, b.table, q.stride, b.chunk_sum };
     EgsPrologueArgs pa = {};
     const unsigned grid = ((q.nblocks + 7) / 8) * 8;

@@ -1,6 +1,6 @@
 """GPU: the covariance producer (cov3d.hip) against covariance.py evaluated in float64 on the CPU, with the same functions in float32 on the
-CPU as the yardstick -- the producer that the preprocess's raw-parameter mode and the in-rasterizer object rotation are each asserted equal
-to.  Values per row, gradients per row against the row's own magnitude, the dM reduction, block edges.  Figures: profiles/anchor_parity.md."""
+CPU as the yardstick -- the producer whose arithmetic (csrc/splat_geom.h) the preprocess's raw-parameter mode and the in-rasterizer object
+rotation run too, and are each asserted equal to.  Values per row, gradients per row against the row's own magnitude, the dM reduction, block edges.  Figures: profiles/anchor_parity.md."""
 import functools
 
 import numpy as np

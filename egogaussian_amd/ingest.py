@@ -16,9 +16,11 @@ The resize (Pillow Resample.c, modes L and RGB, no box, no reducing gap): a hori
 when the height changes; the intermediate is 8-bit, rounded and clamped like the output; a pass whose size does not change is skipped.  A
 pixel of a pass is clamp((2^21 + sum in[xmin + x] * kk[x]) >> 22, 0, 255) in int32 with an arithmetic shift.
 
-Files: FrameIngest.put_files takes 8-bit grey or RGB PNG files (paths or bytes) in place of arrays and decodes them on the device
-(egogaussian_amd/png.py PngReader, csrc/png_decode.hip) in front of the same kernel; put() with host-decoded arrays is unchanged.  JPEG, and
-the PNG modes Pillow resizes differently (palette, alpha, 16-bit, interlaced ones too), are decoded on the host and go through put().
+Files: FrameIngest.put_files takes 8-bit grey or RGB PNG files and baseline JPEG files (paths or bytes, told apart by their first two
+bytes) in place of arrays and decodes them on the device (egogaussian_amd/png.py PngReader, csrc/png_decode.hip; egogaussian_amd/jpeg.py
+JpegReader, csrc/jpeg_decode.hip) in front of the same kernel; put() with host-decoded arrays is unchanged.  Progressive, multi-scan and
+CMYK JPEG files, and the PNG modes Pillow resizes differently (palette, alpha, 16-bit, interlaced ones too), are decoded on the host and go
+through put().
 """
 import math
 
@@ -181,6 +183,7 @@ class FrameIngest:
         self._uploaded = [None, None, None]
         from . import png as _png
         self._reader = _png.PngReader(dev, batch=3)                    # put_files: its buffers are allocated by the first decode
+        self._jpeg_reader = None                                        # put_files: created by the first JPEG file
 
     source = staticmethod(_source)      # (array, name, h, w, channels) -> uint8 [h,w,C] tensor, or the refusal
 
@@ -230,29 +233,58 @@ class FrameIngest:
             self._launch(i, plane, slot, t)
 
     def put_files(self, i, cam, image=None, hand_mask=None, obj_mask=None, accum_R=None, accum_T=None, pose_rows=None, segments=False):
-        """put() with 8-bit PNG files -- paths or bytes -- in place of the arrays.  The sizes and channel counts are checked from IHDR
-        against src_hw before any device work (png.parse; a mode this path does not take is refused there); the files are then uploaded as
-        they are and decoded on the device on the store's stream, in front of the ingest launches.  Nothing is read back but the decoder's
-        status words, once; a file the device refuses raises ValueError and the store is left as it was.  The store ends up bit-identical
-        to put() with the decoded arrays.  segments=True decodes with the segmented route (png.PngReader: a wave per IDAT chunk for the files
-        that allow it, e.g. this project's own; the same store either way)."""
+        """put() with 8-bit PNG files or baseline JPEG files -- paths or bytes, each told by its first two bytes (FF D8: JPEG; a call may
+        mix them, a JPEG image with PNG masks being the usual dataset) -- in place of the arrays.  The sizes and channel counts are checked
+        from the headers against src_hw before any device work (png.parse, jpeg.parse; a mode this path does not take is refused there); the
+        files are then uploaded as they are and decoded on the device on the store's stream, in front of the ingest launches.  Nothing is
+        read back but each decoder's status words, once; a file the device refuses raises ValueError and the store is left as it was.  The
+        store ends up bit-identical to put() with the decoded arrays.  segments=True decodes the PNG files with the segmented route
+        (png.PngReader: a wave per IDAT chunk for the files that allow it, e.g. this project's own; the same store either way); it means
+        nothing for JPEG."""
         from . import png as _png
         self._reader.flags = (self._reader.flags & ~_png.SEGMENTS) | (_png.SEGMENTS if segments else 0)
         given = [(name, f) for name, f in (("obj_mask", obj_mask), ("hand_mask", hand_mask), ("image", image)) if f is not None]
         who = ", ".join(f"file {k} is {name}" for k, (name, _) in enumerate(given))
-        try:
-            loaded = self._reader.load([f for _, f in given])           # host only: the chunk walk and IHDR of every file
-        except ValueError as e:
-            raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
-        for (name, _), (W, H, C, _, _) in zip(given, loaded[2]):
+        blobs, names = [], []                                           # (as the readers' load() names them: the index is the call's)
+        for k, (_, f) in enumerate(given):
+            if isinstance(f, (bytes, bytearray, memoryview)):
+                blobs.append(f)
+                names.append(f"file {k}")
+            else:
+                with open(f, "rb") as fh:
+                    blobs.append(fh.read())
+                names.append(f"file {k} ({f})")
+        is_jpeg = [bytes(b[:2]) == b"\xff\xd8" for b in blobs]
+        parsed = []
+        for name, b, j in zip(names, blobs, is_jpeg):                    # host only: the header walk of every file
+            try:
+                if j:
+                    from . import jpeg as _jpeg
+                    parsed.append(dict(_jpeg.parse(b), nbytes=len(b)))
+                else:
+                    parsed.append(_png.parse(b) + (len(b),))
+            except ValueError as e:
+                raise ValueError(f"FrameIngest.put_files: {name}: {e} ({who})") from None
+        for (name, _), p, j in zip(given, parsed, is_jpeg):
+            W, H, C = (p["W"], p["H"], p["C"]) if j else p[:3]
             if (H, W) != (self.h, self.w) or (name == "image" and C != 3):
                 raise ValueError(f"FrameIngest.put_files: {name} is {W}x{H} with {C} channel(s); the source resolution is {self.w}x{self.h}"
                                  f"{' and an image has 3' if name == 'image' else ''}; {_ADVICE}")
+        if any(is_jpeg) and self._jpeg_reader is None:
+            from . import jpeg as _jpeg
+            self._jpeg_reader = _jpeg.JpegReader(self.store.device, batch=3)
+        decoded = [None] * len(given)
         with _hip.device_ctx(self.store.device):
-            try:
-                decoded = self._reader.decode(*loaded)
-            except ValueError as e:
-                raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
+            for reader, kind in ((self._reader, False), (self._jpeg_reader, True)):
+                idx = [k for k, j in enumerate(is_jpeg) if j == kind]
+                if not idx:
+                    continue
+                try:                                                    # (both decoders run before the first ingest launch)
+                    part = reader.decode([blobs[k] for k in idx], [names[k] for k in idx], [parsed[k] for k in idx])
+                except ValueError as e:
+                    raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
+                for k, t in zip(idx, part):
+                    decoded[k] = t
         arrays = {name: t for (name, _), t in zip(given, decoded)}
         self.put(i, cam, image=arrays.get("image"), hand_mask=arrays.get("hand_mask"), obj_mask=arrays.get("obj_mask"), accum_R=accum_R,
                  accum_T=accum_T, pose_rows=pose_rows)

@@ -211,6 +211,9 @@ SIGNATURES = {
     "egs_png_decode_phases": (C.c_int, [i32, vp, C.c_size_t, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32]),
     "egs_png_decode_scratch_bytes_ex": (C.c_size_t, [i32, C.c_size_t, C.c_size_t, i32]),
     "egs_png_decode_ex": (C.c_int, [i32, vp, C.c_size_t, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32, i32, vp]),
+    "egs_jpeg_decode_scratch_bytes": (C.c_size_t, [i32, i32, C.c_size_t, C.c_size_t]),
+    "egs_jpeg_decode": (C.c_int, [i32, vp, C.c_size_t, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, C.c_size_t, vp]),
+    "egs_jpeg_decode_phases": (C.c_int, [i32, vp, C.c_size_t, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32]),
     "egs_pose_head": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp]),
     "egs_pose_tail": (C.c_int, [C.POINTER(PoseSequence), vp, vp, vp, vp, vp]),
     "egs_pose_accumulate": (C.c_int, [C.POINTER(PoseSequence), vp]),

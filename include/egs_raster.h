@@ -804,6 +804,78 @@ int egs_png_decode_ex(int n_files, const uint8_t* files, size_t files_bytes, con
                       uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases, int flags,
                       uint32_t* route /*device [n_files] out, or NULL*/);
 
+/* ---- baseline JPEG files read on the device (added within ABI 6: new entries only).
+ *      The reference opens its frames with Image.open (scene/dataset_readers.py:83-97, 140, 213), which takes .jpg as readily as .png.  This
+ *      entry takes the bytes of a batch of baseline JPEG files as they are on disk and leaves interleaved uint8 [height][width][channels]
+ *      arrays in `out`, bit for bit what libjpeg-turbo's default path (islow IDCT, fancy upsampling, fixed-point colour) -- and so Pillow --
+ *      gives; egogaussian_amd/jpeg.py decode() is the statement of every step.  Accepted: SOF0, 8-bit samples, Huffman coding, ONE scan of
+ *      all components; one component, or three marked as YCbCr with luma sampling 1x1, 2x1 or 2x2 and 1x1 chroma; any restart interval.
+ *      Everything else is the caller's to refuse from the marker segments (egogaussian_amd/jpeg.py parse does).
+ *      Host work is the segment walk up to the SOS header -- no entropy-coded byte touched -- which fills two tables:
+ *        egs_jpeg_file    per file: width, height, channels (1 or 3); hs, vs the luma sampling; restart_interval in MCUs (0: none);
+ *                         mcus_x = ceil(width / (8 hs)), mcus_y = ceil(height / (8 vs)); its restart intervals
+ *                         [interval_begin, interval_begin + n_intervals) of the batch's, n_intervals = ceil(mcus_x mcus_y / restart_interval)
+ *                         or 1; entropy_begin, the offset of the first entropy-coded byte inside the file, entropy_bytes = file_bytes -
+ *                         entropy_begin; tq / td / ta, per component the index of its quantisation, DC and AC table; file_offset /
+ *                         file_bytes, the file inside `files`; coef_offset and plane_offset (multiples of 16), its places in the scratch
+ *                         areas of the coefficients (128 bytes per block: mcus_x mcus_y (hs vs + 2) blocks, or mcus_x mcus_y with one
+ *                         component) and of the component planes (64 bytes per block); out_offset, where its pixels go in `out`.
+ *        egs_jpeg_tables  per file: four 64-byte quantisation tables in NATURAL order, four DC and four AC Huffman tables as (counts[16],
+ *                         values[256]).  Tables a component refers to must be valid: no zero divisor, at most 256 symbols, counts that do
+ *                         not over-subscribe the code space.
+ *      Both tables are passed twice: a host copy, which the entry checks, and a device copy with the same content, which the kernels read
+ *      (the caller uploads it with the files; the entry copies nothing, allocates nothing, synchronises nothing: the call can be captured).
+ *      Four launches, ordered by launch boundaries only:
+ *        intervals  one workgroup per file walks the entropy-coded bytes in order, 256 lanes x 16 bytes per step, carrying the count:
+ *                   FF 00 is a stuffed byte, FF D0 .. D7 starts restart interval k + 1 behind it (its number must be k mod 8), FF D9 ends
+ *                   the data.  Leaves a [start, end) byte pair per interval.
+ *        entropy    one lane per restart interval, the intervals of a file in workgroups that hold its decode tables in LDS (a first-level
+ *                   look-up of 8 bits, the canonical-code walk beyond).  DC predictors start at 0; dequantised int16 coefficients, 64 per
+ *                   block in natural order.  A lane reads no byte outside its interval and writes no block but its interval's.  A file
+ *                   without restart markers is one interval on one lane: that serial chain is the format's.
+ *        idct       eight lanes per block: column pass (descaled by 11) into a workspace, row pass (descaled by 18), + 128, saturating
+ *                   clamp, in int32 -> uint8 component planes padded to whole MCUs.
+ *        colour     one lane per output pixel: triangle-filter chroma upsampling with the edge rules of jpeg.py upsample(), fixed-point
+ *                   YCbCr -> RGB (or a copy of Y); also writes the status word.  A file whose status is not 0 receives no pixel.
+ *      The range rule: a dequantised coefficient (or a DC predictor) outside int16 is status 8, a workspace value outside int16 status 9;
+ *      inside those bounds no int32 expression of the inverse DCT can overflow (jpeg.py, the module text).
+ *      status[i] (device): 0, or the first failure of file i --
+ *          1  a marker inside the entropy-coded data           4 | k << 8  bits no Huffman code owns            7 | k << 8  interval k has bytes left over
+ *          2  a restart marker out of sequence or miscounted   5 | k << 8  a coefficient index beyond 63        8  coefficient range
+ *          3  no EOI                                           6 | k << 8  interval k ends before its MCUs do   9  workspace range
+ *      (k: the lowest failing restart interval of the file).  Nothing outside a file's slots is written and the other files are unaffected.
+ *      EGS_ERR_ARG before any device work: n_files or n_intervals < 1, a NULL pointer, a misaligned scratch (16), status (4) or device
+ *      table (8), files / coefficients / planes / outputs that are not ascending, overlap, are misaligned or leave their buffers,
+ *      mcus_x / mcus_y / n_intervals / interval_begin / entropy_bytes that disagree with the geometry, a table index above 3 or an
+ *      invalid table in use, a scratch smaller than egs_jpeg_decode_scratch_bytes.  EGS_ERR_RANGE: a side outside 1 .. 32767, channels
+ *      not 1 or 3, sampling outside the accepted set, a restart interval outside 0 .. 65535, n_files > 65535, a file or an output of
+ *      2 GiB or more.
+ *        egs_jpeg_decode_scratch_bytes  256-aligned areas: 16 n_files bytes of stage words, 8 n_intervals bytes of byte pairs, the
+ *                                       coefficients, the planes (totals as the offsets above imply: the sums of the 16-byte-rounded
+ *                                       sizes); 0 for n_files or n_intervals < 1.  Host arithmetic.
+ *        egs_jpeg_decode_phases         the same call restricted to some of its launches, for measurements (tools/time_jpeg_decode.py):
+ *                                       phases is a mask of 1 (intervals), 2 (entropy), 4 (idct), 8 (colour), 1 .. 15 (else EGS_ERR_ARG).  A
+ *                                       later launch alone reads what an earlier call with the same arguments left in `scratch`.
+ *                                       egs_jpeg_decode is phases = 15. */
+enum { EGS_JPEG_OK = 0, EGS_JPEG_MARKER = 1, EGS_JPEG_RESTART = 2, EGS_JPEG_NO_EOI = 3, EGS_JPEG_CODE = 4, EGS_JPEG_INDEX = 5,
+       EGS_JPEG_SHORT = 6, EGS_JPEG_LEFT_OVER = 7, EGS_JPEG_COEF_RANGE = 8, EGS_JPEG_WORKSPACE_RANGE = 9 };
+typedef struct egs_jpeg_file {
+    int32_t width, height, channels, hs, vs, restart_interval, mcus_x, mcus_y;
+    uint32_t interval_begin, n_intervals, entropy_begin, entropy_bytes;
+    uint8_t tq[4], td[4], ta[4];
+    uint32_t reserved;
+    uint64_t file_offset, file_bytes, coef_offset, plane_offset, out_offset;
+} egs_jpeg_file;
+typedef struct egs_jpeg_huffman { uint8_t counts[16], values[256]; } egs_jpeg_huffman;
+typedef struct egs_jpeg_tables { uint8_t quant[4][64]; egs_jpeg_huffman dc[4], ac[4]; } egs_jpeg_tables;
+size_t egs_jpeg_decode_scratch_bytes(int n_files, int n_intervals, size_t coef_bytes, size_t plane_bytes);
+int egs_jpeg_decode(int n_files, const uint8_t* files /*device*/, size_t files_bytes, const egs_jpeg_file* desc_host, const egs_jpeg_file* desc_device,
+                    const egs_jpeg_tables* tables_host, const egs_jpeg_tables* tables_device, int n_intervals, uint8_t* out /*device*/,
+                    size_t out_bytes, uint32_t* status /*device [n_files] out*/, void* scratch, size_t scratch_bytes, void* stream);
+int egs_jpeg_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_jpeg_file* desc_host, const egs_jpeg_file* desc_device,
+                           const egs_jpeg_tables* tables_host, const egs_jpeg_tables* tables_device, int n_intervals, uint8_t* out,
+                           size_t out_bytes, uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases);
+
 /* ---- the object pose sequence on the device (added within ABI 6: new entries only).
  *      The object stages train ONE pose pair per dynamic frame on top of the pose accumulated over the earlier keys, store it under the
  *      frame's key and rebuild the accumulated sequence (/root/reference/trainers/fine_obj.py:97-126,216-224,

@@ -18,6 +18,7 @@
 // Between the launches a file's verdict lives in four stage words in scratch (JpgdWords), so that no launch reads a word another workgroup
 // of the same launch writes.
 #include "egs_common.h"
+#include "decode_args.h"
 
 #define JPGD_WG 256
 #define JPGD_MAX_SIDE 32767
@@ -442,8 +443,6 @@ __global__ __launch_bounds__(JPGD_WG) void k_jpgd_colour(JpgdArgs a) {
     }
 }
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // counts that fit the code space, at most 256 symbols, and for a DC table no symbol above 15
 bool table_ok(const egs_jpeg_huffman& h, bool dc) {
     uint32_t code = 0, total = 0;
@@ -471,10 +470,8 @@ size_t egs_jpeg_decode_scratch_bytes(int n_files, int n_intervals, size_t coef_b
 int egs_jpeg_decode_phases(int n_files, const uint8_t* files, size_t files_bytes, const egs_jpeg_file* desc_host, const egs_jpeg_file* desc_device,
                            const egs_jpeg_tables* tables_host, const egs_jpeg_tables* tables_device, int n_intervals, uint8_t* out,
                            size_t out_bytes, uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases) {
-    if (n_files < 1 || n_intervals < 1 || phases < 1 || phases > 15) return EGS_ERR_ARG;
-    if (n_files > 65535) return EGS_ERR_RANGE;
-    if (!files || !desc_host || !desc_device || !tables_host || !tables_device || !out || !status || !scratch) return EGS_ERR_ARG;
-    if (((uintptr_t)scratch & 15) || ((uintptr_t)status & 3) || ((uintptr_t)desc_device & 7) || ((uintptr_t)tables_device & 7)) return EGS_ERR_ARG;
+    if (phases < 1 || phases > 15) return EGS_ERR_ARG;
+    if (const int e = decode_open(n_files, n_intervals, files, desc_host, desc_device, tables_host, tables_device, 8, out, status, scratch)) return e;
     size_t coef_total = 0, plane_total = 0, file_end = 0, out_end = 0;
     uint64_t interval_next = 0, max_intervals = 0, max_blocks = 0, max_pixels = 0;
     for (int i = 0; i < n_files; i++) {
@@ -490,19 +487,12 @@ int egs_jpeg_decode_phases(int n_files, const uint8_t* files, size_t files_bytes
         const uint64_t want = f.restart_interval ? (mcus + (uint64_t)f.restart_interval - 1) / (uint64_t)f.restart_interval : 1;
         if (f.n_intervals != want || f.interval_begin != interval_next || interval_next + want > (uint64_t)n_intervals) return EGS_ERR_ARG;
         interval_next += want;
-        // files, coefficients, planes and outputs each in ascending order without overlap, and inside their buffers
-        // (sizes first, then offset > room - size: no sum that could wrap)
-        if (f.file_offset < file_end || f.file_bytes > files_bytes || f.file_offset > files_bytes - f.file_bytes) return EGS_ERR_ARG;
-        file_end = (size_t)(f.file_offset + f.file_bytes);
+        // files, coefficients, planes and outputs each in ascending order without overlap, and inside their buffers (decode_args.h)
+        if (!decode_region(f.file_offset, f.file_bytes, 1, files_bytes, &file_end)) return EGS_ERR_ARG;
         if (f.entropy_begin >= f.file_bytes || (uint64_t)f.entropy_begin + f.entropy_bytes != f.file_bytes) return EGS_ERR_ARG;
-        const size_t coef_room = up16((size_t)(mcus * bpm * 128)), plane_room = up16((size_t)(mcus * bpm * 64));
-        if (coef_room > scratch_bytes || plane_room > scratch_bytes) return EGS_ERR_ARG;
-        if ((f.coef_offset & 15) || f.coef_offset < coef_total || f.coef_offset > scratch_bytes - coef_room) return EGS_ERR_ARG;
-        coef_total = (size_t)f.coef_offset + coef_room;
-        if ((f.plane_offset & 15) || f.plane_offset < plane_total || f.plane_offset > scratch_bytes - plane_room) return EGS_ERR_ARG;
-        plane_total = (size_t)f.plane_offset + plane_room;
-        if (f.out_offset < out_end || pixels > out_bytes || f.out_offset > out_bytes - pixels) return EGS_ERR_ARG;
-        out_end = (size_t)(f.out_offset + pixels);
+        if (!decode_region(f.coef_offset, up16((size_t)(mcus * bpm * 128)), 16, scratch_bytes, &coef_total) ||
+            !decode_region(f.plane_offset, up16((size_t)(mcus * bpm * 64)), 16, scratch_bytes, &plane_total) ||
+            !decode_region(f.out_offset, pixels, 1, out_bytes, &out_end)) return EGS_ERR_ARG;
         const egs_jpeg_tables& tb = tables_host[i];
         for (int c = 0; c < f.channels; c++) {
             if (f.tq[c] > 3 || f.td[c] > 3 || f.ta[c] > 3) return EGS_ERR_ARG;

@@ -23,6 +23,7 @@
 #include "png_inflate.h"
 #include "png_segments.h"
 #include "png_common.h"
+#include "decode_args.h"
 
 #define PNGD_WG 256
 #define PNGD_CRC_IDAT 0x35af061eu            // CRC-32 of the four bytes "IDAT"
@@ -238,8 +239,6 @@ __global__ __launch_bounds__(64) void k_pngd_unfilter(PngdArgs a) {
     else pngd_unfilter<1>(infl, out, W, H);
 }
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" {
@@ -259,10 +258,8 @@ size_t egs_png_decode_scratch_bytes_ex(int n_idat, size_t total_stream_bytes, si
 int egs_png_decode_ex(int n_files, const uint8_t* files, size_t files_bytes, const egs_png_file* desc_host, const egs_png_file* desc_device,
                       const egs_png_idat* idat_host, const egs_png_idat* idat_device, int n_idat, uint8_t* out, size_t out_bytes,
                       uint32_t* status, void* scratch, size_t scratch_bytes, void* stream, int phases, int flags, uint32_t* route) {
-    if (n_files < 1 || n_idat < 1 || phases < 1 || phases > 7 || (flags & ~EGS_PNG_SEGMENTS) || ((uintptr_t)route & 3)) return EGS_ERR_ARG;
-    if (n_files > 65535) return EGS_ERR_RANGE;
-    if (!files || !desc_host || !desc_device || !idat_host || !idat_device || !out || !status || !scratch) return EGS_ERR_ARG;
-    if (((uintptr_t)scratch & 15) || ((uintptr_t)status & 3) || ((uintptr_t)desc_device & 7) || ((uintptr_t)idat_device & 3)) return EGS_ERR_ARG;
+    if (phases < 1 || phases > 7 || (flags & ~EGS_PNG_SEGMENTS) || ((uintptr_t)route & 3)) return EGS_ERR_ARG;
+    if (const int e = decode_open(n_files, n_idat, files, desc_host, desc_device, idat_host, idat_device, 4, out, status, scratch)) return e;
     size_t stream_total = 0, inflate_total = 0, file_end = 0, out_end = 0;
     uint32_t idat_next = 0;
     for (int i = 0; i < n_files; i++) {
@@ -271,18 +268,12 @@ int egs_png_decode_ex(int n_files, const uint8_t* files, size_t files_bytes, con
         const uint64_t pixels = (uint64_t)f.height * (uint64_t)f.width * (uint64_t)f.channels;
         if (pixels >= ((uint64_t)1 << 31) || f.stream_bytes >= (1u << 31)) return EGS_ERR_RANGE;
         const uint64_t inflated = pixels + (uint64_t)f.height;
-        // files, streams, inflated data and outputs each in ascending order without overlap, and inside their buffers
-        if (f.file_offset < file_end || f.file_bytes > files_bytes || f.file_offset > files_bytes - f.file_bytes) return EGS_ERR_ARG;
-        file_end = (size_t)(f.file_offset + f.file_bytes);
-        // (sizes first, then offset > room - size: no sum that could wrap; both sizes are below 2^32)
-        const size_t stream_room = up16(f.stream_bytes), inflate_room = up16((size_t)inflated);
-        if (stream_room > scratch_bytes || inflate_room > scratch_bytes) return EGS_ERR_ARG;
-        if ((f.stream_offset & 15) || f.stream_offset < stream_total || f.stream_offset > scratch_bytes - stream_room) return EGS_ERR_ARG;
-        stream_total = (size_t)f.stream_offset + stream_room;
-        if ((f.inflate_offset & 15) || f.inflate_offset < inflate_total || f.inflate_offset > scratch_bytes - inflate_room) return EGS_ERR_ARG;
-        inflate_total = (size_t)f.inflate_offset + inflate_room;
-        if (f.out_offset < out_end || pixels > out_bytes || f.out_offset > out_bytes - pixels) return EGS_ERR_ARG;
-        out_end = (size_t)(f.out_offset + pixels);
+        // files, streams, inflated data and outputs each in ascending order without overlap, and inside their buffers (decode_args.h; both
+        // rooms are below 2^32)
+        if (!decode_region(f.file_offset, f.file_bytes, 1, files_bytes, &file_end) ||
+            !decode_region(f.stream_offset, up16(f.stream_bytes), 16, scratch_bytes, &stream_total) ||
+            !decode_region(f.inflate_offset, up16((size_t)inflated), 16, scratch_bytes, &inflate_total) ||
+            !decode_region(f.out_offset, pixels, 1, out_bytes, &out_end)) return EGS_ERR_ARG;
         // the file's chunks: consecutive in the table, inside the file, tiling its stream
         if (f.n_idat < 1 || f.idat_begin != idat_next || (uint64_t)f.idat_begin + (uint64_t)f.n_idat > (uint64_t)n_idat) return EGS_ERR_ARG;
         uint64_t at = 0;

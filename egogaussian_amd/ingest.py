@@ -29,6 +29,7 @@ import torch
 
 from . import lib as _lib
 from . import _hip
+from .file_reader import load_files
 
 PRECISION_BITS = 22
 MAX_SCALE = 8               # per axis: ksize <= 33, what bounds the kernel's tile in LDS
@@ -155,6 +156,15 @@ def _source(a, name, h, w, channels):
     return t.contiguous()
 
 
+def _parse_file(blob):
+    """-> (the file's reader class, told by its first two bytes (FF D8: JPEG); its entry of that reader's `parsed`)."""
+    if bytes(blob[:2]) == b"\xff\xd8":
+        from .jpeg import JpegReader as kind
+    else:
+        from .png import PngReader as kind
+    return kind, kind._parse_one(blob)
+
+
 class FrameIngest:
     """Fills the rows of `store` (a FrameStore on a HIP device) from source-resolution 8-bit arrays of src_hw = (h, w).  Owns the device
     tables of (h -> store.H) and (w -> store.W), one pinned staging buffer and one device buffer per plane group."""
@@ -241,42 +251,26 @@ class FrameIngest:
         store ends up bit-identical to put() with the decoded arrays.  segments=True decodes the PNG files with the segmented route
         (png.PngReader: a wave per IDAT chunk for the files that allow it, e.g. this project's own; the same store either way); it means
         nothing for JPEG."""
-        from . import png as _png
+        from . import jpeg as _jpeg, png as _png
         self._reader.flags = (self._reader.flags & ~_png.SEGMENTS) | (_png.SEGMENTS if segments else 0)
         given = [(name, f) for name, f in (("obj_mask", obj_mask), ("hand_mask", hand_mask), ("image", image)) if f is not None]
         who = ", ".join(f"file {k} is {name}" for k, (name, _) in enumerate(given))
-        blobs, names = [], []                                           # (as the readers' load() names them: the index is the call's)
-        for k, (_, f) in enumerate(given):
-            if isinstance(f, (bytes, bytearray, memoryview)):
-                blobs.append(f)
-                names.append(f"file {k}")
-            else:
-                with open(f, "rb") as fh:
-                    blobs.append(fh.read())
-                names.append(f"file {k} ({f})")
-        is_jpeg = [bytes(b[:2]) == b"\xff\xd8" for b in blobs]
-        parsed = []
-        for name, b, j in zip(names, blobs, is_jpeg):                    # host only: the header walk of every file
-            try:
-                if j:
-                    from . import jpeg as _jpeg
-                    parsed.append(dict(_jpeg.parse(b), nbytes=len(b)))
-                else:
-                    parsed.append(_png.parse(b) + (len(b),))
-            except ValueError as e:
-                raise ValueError(f"FrameIngest.put_files: {name}: {e} ({who})") from None
-        for (name, _), p, j in zip(given, parsed, is_jpeg):
-            W, H, C = (p["W"], p["H"], p["C"]) if j else p[:3]
+        try:                                                            # host only: the header walk of every file, the names' index the call's
+            blobs, names, found = load_files([f for _, f in given], _parse_file)
+        except ValueError as e:
+            raise ValueError(f"FrameIngest.put_files: {e} ({who})") from None
+        kinds, parsed = [kind for kind, _ in found], [p for _, p in found]
+        for (name, _), p, kind in zip(given, parsed, kinds):
+            W, H, C = kind._shape(p)
             if (H, W) != (self.h, self.w) or (name == "image" and C != 3):
                 raise ValueError(f"FrameIngest.put_files: {name} is {W}x{H} with {C} channel(s); the source resolution is {self.w}x{self.h}"
                                  f"{' and an image has 3' if name == 'image' else ''}; {_ADVICE}")
-        if any(is_jpeg) and self._jpeg_reader is None:
-            from . import jpeg as _jpeg
+        if _jpeg.JpegReader in kinds and self._jpeg_reader is None:
             self._jpeg_reader = _jpeg.JpegReader(self.store.device, batch=3)
         decoded = [None] * len(given)
         with _hip.device_ctx(self.store.device):
-            for reader, kind in ((self._reader, False), (self._jpeg_reader, True)):
-                idx = [k for k, j in enumerate(is_jpeg) if j == kind]
+            for reader, kind in ((self._reader, _png.PngReader), (self._jpeg_reader, _jpeg.JpegReader)):
+                idx = [k for k, c in enumerate(kinds) if c is kind]
                 if not idx:
                     continue
                 try:                                                    # (both decoders run before the first ingest launch)

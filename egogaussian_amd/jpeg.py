@@ -4,7 +4,7 @@
     decode       the strict host reader, integer numpy / Python written from the standard and libjpeg's documented arithmetic: the STATEMENT
                  the kernels answer to (csrc/jpeg_decode.hip), status words included.  Not a call into any library.
     plan         the descriptor and table arrays of egs_jpeg_decode for a batch
-    JpegReader   file bytes -> device uint8 [h, w, C]; PngReader's contract
+    JpegReader   file bytes -> device uint8 [h, w, C]; DeviceFileReader's contract (file_reader.py)
 
 The arithmetic, in the order decode() applies it (libjpeg-turbo's default path, which Pillow uses: tests/golden/jpeg_files.npz):
   Huffman decode with the DC predictors reset at every restart; dequantise; the `islow` inverse DCT (CONST_BITS 13, PASS1_BITS 2: column
@@ -23,10 +23,10 @@ Pillow there.  Genuine encoder output stays below +-2 200.
 import struct
 
 import numpy as np
-import torch
 
 from . import lib as _lib
 from . import _hip
+from .file_reader import DeviceFileReader, _up
 
 MAX_SIDE = 32767
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
@@ -464,10 +464,6 @@ WRONG = ("nearest-neighbour chroma", "the rounding constants swapped", "the MCU-
 
 
 # ---- the device --------------------------------------------------------------------------------------------------------------------------
-def _up(v, a):
-    return (v + a - 1) // a * a
-
-
 def plan(parsed, out_gap=0):
     """parsed: [parse(file) with "nbytes": the file's length] -> dict(desc, tables: the two arrays of egs_jpeg_decode with files, coefficients,
     planes and outputs packed in order -- files, coefficients and planes at multiples of 16, outputs at multiples of 256 with `out_gap` bytes
@@ -496,144 +492,37 @@ def plan(parsed, out_gap=0):
     return dict(desc=desc, tables=tables, n_intervals=k, files_bytes=fo, coef_bytes=co, plane_bytes=po, out_bytes=oo)
 
 
-class JpegReader:
-    """Baseline JPEG files -> device uint8 [h, w, C] tensors; PngReader's contract.  Owns the pinned staging, the device buffer the files
-    and their tables are uploaded to, the scratch, the outputs and the status words; each grows to what the largest batch so far needed
-    (max_file_bytes / max_pixels reserve it up front).  Per batch of at most `batch` files: the host walks the marker segments (parse), ONE
-    upload, four launches, ONE read of the status words.  guard > 0 (a multiple of 256) is for tests: every byte of the device buffers that a
-    call is not entitled to holds 0xA5 before the launches, and check_guards() says whether all of it still does."""
-    GUARD_BYTE = 0xA5
-
-    def __init__(self, device, batch=32, max_file_bytes=0, max_pixels=0, guard=0):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"JpegReader: the JPEG decoder has no CPU path (device {self.device}); jpeg.decode is the host reader")
-        self.batch, self.guard = int(batch), int(guard)
-        if self.batch < 1 or self.batch > 65535 or self.guard < 0 or self.guard % 256:
-            raise ValueError("JpegReader: batch of 1 .. 65535, guard a multiple of 256")
-        self._dev, self._pin = {}, None
-        self.host_reads = 0                                             # reads of the status words (one per batch)
-        self.last_status, self.last_results = [], []                    # of the last read(): a refused batch leaves them to look at
-        self._slack_ok, self._gaps = True, []
-        if max_file_bytes or max_pixels:
-            up = self.batch * (_up(int(max_file_bytes), 16) + 4096)
-            self._pinned(up)
-            self._buffer("blob", up)
-            self._buffer("out", self.batch * _up(3 * int(max_pixels) + self.guard, 256))
-            self._buffer("scratch", self.batch * (9 * (int(max_pixels) + 2 * MAX_SIDE) + 4096))
-
-    def _pinned(self, nbytes):
-        if self._pin is None or self._pin.numel() < nbytes:
-            self._pin = torch.empty(_up(nbytes, 4096), dtype=torch.uint8).pin_memory()
-        return self._pin
-
-    def _buffer(self, name, nbytes):
-        """The inner `nbytes` (at least) of a device buffer with `guard` bytes on either side."""
-        g, t = self.guard, self._dev.get(name)
-        if t is None or t.numel() < nbytes + 2 * g:
-            t = torch.full((_up(nbytes, 4096) + 2 * g,), self.GUARD_BYTE, dtype=torch.uint8, device=self.device)
-            self._dev[name] = t
-        return t[g:t.numel() - g]
-
-    def _intact(self, t):
-        return bool((t == self.GUARD_BYTE).all())
-
-    def check_guards(self):
-        """True when every guard byte still holds GUARD_BYTE: around the buffers, between and behind the output slots of the last read(),
-        and -- looked at after every batch of that read() -- behind the status words and the scratch bytes the batch used."""
-        g = self.guard
-        ok = self._slack_ok
-        for name, t in self._dev.items():
-            if g:
-                ok = ok and self._intact(t[:g]) and self._intact(t[t.numel() - g:])
-        for lo, hi in self._gaps:
-            ok = ok and self._intact(self._dev["out"][lo:hi])
-        return ok
-
-    def read(self, files):
-        """files: a list of bytes or paths -> a list of device uint8 [h, w, C] tensors, views into the reader's output buffer, valid until the
-        next call.  ValueError for a file parse() refuses, and for a file the device refuses: it names the file's index (and path) and says
-        what the status word says; the other files of the batch are decoded all the same (last_results)."""
-        return self.decode(*self.load(files))
+class JpegReader(DeviceFileReader):
+    """Baseline JPEG files -> device uint8 [h, w, C] tensors: DeviceFileReader's contract (file_reader.py: the buffers, the batches, one
+    upload and one read of the status words per batch, the guard bytes).  Per batch the host walks the marker segments (parse) and the
+    device runs four launches."""
+    NAME, FORMAT, HOST_READER = "JpegReader", "JPEG", "jpeg.decode"
+    status_text = staticmethod(status_text)
 
     @staticmethod
-    def load(files):
-        """The host's share of read(): files (bytes or paths) -> (blobs, names, parsed).  No device work; ValueError for a file parse()
-        refuses."""
-        blobs, names = [], []
-        for i, f in enumerate(files):
-            if isinstance(f, (bytes, bytearray, memoryview)):
-                blobs.append(f)
-                names.append(f"file {i}")
-            else:
-                with open(f, "rb") as fh:
-                    blobs.append(fh.read())
-                names.append(f"file {i} ({f})")
-        parsed = []
-        for name, b in zip(names, blobs):
-            try:
-                parsed.append(dict(parse(b), nbytes=len(b)))
-            except ValueError as e:
-                raise ValueError(f"{name}: {e}") from None
-        return blobs, names, parsed
+    def _parse_one(blob):
+        return dict(parse(blob), nbytes=len(blob))
 
-    def decode(self, blobs, names, parsed):
-        """The device's share of read(), from what load() returned."""
-        self._slack_ok, self._gaps = True, []
-        if not parsed:
-            return []
-        whole = plan(parsed, self.guard)
-        out = self._buffer("out", whole["out_bytes"])
-        g0 = self.guard
-        if g0:
-            out.fill_(self.GUARD_BYTE)
-            self._gaps.append((g0 + whole["out_bytes"], g0 + out.numel()))      # behind the last slot, up to the end of the allocation
-        results, failures = [], []
-        lib = _lib.load()
-        for lo in range(0, len(parsed), self.batch):
-            part = parsed[lo:lo + self.batch]
-            p = plan(part, self.guard)
-            n = len(part)
-            t_desc, t_tab = _up(n * _FILE.itemsize, 256), _up(n * _TABLES.itemsize, 256)
-            up_bytes = t_desc + t_tab + p["files_bytes"]
-            pin = self._pinned(up_bytes)
-            host = pin.numpy()
-            host[:n * _FILE.itemsize] = p["desc"].view(np.uint8).reshape(-1)
-            host[t_desc:t_desc + n * _TABLES.itemsize] = p["tables"].view(np.uint8).reshape(-1)
-            for d, b in zip(p["desc"], blobs[lo:lo + n]):
-                at = t_desc + t_tab + int(d["file_offset"])
-                host[at:at + len(b)] = np.frombuffer(b, dtype=np.uint8)
-            blob = self._buffer("blob", up_bytes)
-            blob[:up_bytes].copy_(pin[:up_bytes], non_blocking=True)
-            need = int(lib.egs_jpeg_decode_scratch_bytes(n, p["n_intervals"], p["coef_bytes"], p["plane_bytes"]))
-            scratch = self._buffer("scratch", need)
-            status = self._buffer("status", 4 * self.batch)
-            base = int(whole["desc"]["out_offset"][lo])                  # this batch's slots inside the call's output buffer
-            self.last_call = (n, blob.data_ptr() + t_desc + t_tab, p["files_bytes"], pin.data_ptr(), blob.data_ptr(), pin.data_ptr() + t_desc,
-                              blob.data_ptr() + t_desc, p["n_intervals"], out.data_ptr() + base, p["out_bytes"], status.data_ptr(),
-                              scratch.data_ptr(), need)
-            if g0:                                                      # everything behind the bytes in use holds the guard byte
-                status[4 * n:].fill_(self.GUARD_BYTE)
-                scratch[need:].fill_(self.GUARD_BYTE)
-            with _hip.device_ctx(self.device):
-                _lib.check(lib.egs_jpeg_decode(*self.last_call, _hip.stream_of(self.device)))
-            words = [w & 0xFFFFFFFF for w in status[:4 * n].view(torch.int32).cpu().tolist()]      # (synchronises: the staging may be refilled)
-            self.host_reads += 1
-            if g0:
-                self._slack_ok = self._slack_ok and self._intact(status[4 * n:]) and self._intact(scratch[need:])
-            for k, (d, w) in enumerate(zip(p["desc"], words)):
-                W, H, C = int(d["width"]), int(d["height"]), int(d["channels"])
-                o = base + int(d["out_offset"])
-                results.append(out[o:o + H * W * C].view(H, W, C))
-                if g0:
-                    self._gaps.append((g0 + o + H * W * C, g0 + o + _up(H * W * C + g0, 256)))
-                if w:
-                    failures.append(f"{names[lo + k]}: {status_text(w)} (status {w})")
-            self.last_status = (self.last_status if lo else []) + words
-        self.last_results = results
-        if failures:
-            raise ValueError("JpegReader.read: " + "; ".join(failures))
-        return results
+    @staticmethod
+    def _shape(entry):
+        return entry["W"], entry["H"], entry["C"]
+
+    _plan = staticmethod(plan)
+
+    def _second_table(self, p):
+        return p["tables"], p["n_intervals"]
+
+    def _scratch_need(self, lib, n, p):
+        return int(lib.egs_jpeg_decode_scratch_bytes(n, p["n_intervals"], p["coef_bytes"], p["plane_bytes"]))
+
+    def _reserve_scratch(self, max_file_bytes, max_pixels):
+        return self.batch * (9 * (max_pixels + 2 * MAX_SIDE) + 4096)
+
+    def _status_allocation(self):
+        return 4 * self.batch
+
+    def _launch(self, lib, call, n, status):
+        _lib.check(lib.egs_jpeg_decode(*call, _hip.stream_of(self.device)))
 
 
 def decode_device(file_bytes, device="cuda"):

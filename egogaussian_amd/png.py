@@ -33,6 +33,7 @@ import torch
 
 from . import lib as _lib
 from . import _hip
+from .file_reader import DeviceFileReader, _up
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 SEGMENT_BYTES = 4096          # csrc/png.hip PNG_SEG
@@ -406,10 +407,6 @@ def parse(file_bytes):
     return W, H, 3 if colour == 2 else 1, idat
 
 
-def _up(v, a):
-    return (v + a - 1) // a * a
-
-
 def plan(parsed, out_gap=0):
     """parsed: [(W, H, C, idat, file length)] -> dict(desc, idat: the two tables of egs_png_decode with files, streams, inflated data and outputs
     packed in order -- files at multiples of 16, outputs at multiples of 256 with `out_gap` bytes between them --, files_bytes, stream_bytes,
@@ -434,159 +431,59 @@ def plan(parsed, out_gap=0):
     return dict(desc=desc, idat=idat, files_bytes=fo, stream_bytes=so, inflate_bytes=io, out_bytes=oo)
 
 
-class PngReader:
-    """8-bit PNG files -> device uint8 [h, w, C] tensors: the mirror of PngWriter.  Owns the pinned staging, the device buffer the files and
-    their tables are uploaded to, the scratch, the outputs and the status words; each grows to what the largest batch so far needed
-    (max_file_bytes / max_pixels reserve it up front).  Per batch of at most `batch` files: the host walks the chunks (parse), ONE upload,
-    three launches, ONE read of the status words.  segments=True asks for the segmented route (egs_png_decode_ex with EGS_PNG_SEGMENTS: a file
+class PngReader(DeviceFileReader):
+    """8-bit PNG files -> device uint8 [h, w, C] tensors: the mirror of PngWriter, and DeviceFileReader's contract (file_reader.py: the
+    buffers, the batches, one upload and one read of the status words per batch, the guard bytes).  Per batch the host walks the chunks
+    (parse) and the device runs three launches.  segments=True asks for the segmented route (egs_png_decode_ex with EGS_PNG_SEGMENTS: a file
     whose IDAT chunks are independent deflate segments -- the device encoder's files, zlib with a full flush per chunk -- is inflated by one
     wave per chunk, every other file by the serial wave as before; statuses and pixels are the same either way); last_route then holds the
-    route word per file of the last read() (route_text), read with the status words in the same one read.  guard > 0 (a multiple of 256) is for tests: every byte of the device buffers that a
-    call is not entitled to -- `guard` bytes before and behind each buffer, the gaps between the output slots, and everything behind the
-    status words, the scratch bytes and the outputs IN USE up to the end of their allocations -- holds 0xA5 before the launches, and
-    check_guards() says whether all of it still does."""
-    GUARD_BYTE = 0xA5
+    route word per file of the last read() (route_text), read with the status words in the same one read."""
+    NAME, FORMAT, HOST_READER = "PngReader", "PNG", "png.decode"
+    status_text = staticmethod(status_text)
 
     def __init__(self, device, batch=32, max_file_bytes=0, max_pixels=0, guard=0, segments=False):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PngReader: the PNG decoder has no CPU path (device {self.device}); png.decode is the host reader")
-        self.batch, self.guard = int(batch), int(guard)
         self.flags = SEGMENTS if segments else 0
-        if self.batch < 1 or self.batch > 65535 or self.guard < 0 or self.guard % 256:
-            raise ValueError("PngReader: batch of 1 .. 65535, guard a multiple of 256")
-        self._dev, self._pin = {}, None
-        self.host_reads = 0                                             # reads of the status words (one per batch)
-        self.last_status, self.last_results = [], []                    # of the last read(): a refused batch leaves them to look at
-        self.last_route = []                                            # with segments=True: the route word per file (else zeros)
-        self._slack_ok, self._gaps = True, []
-        if max_file_bytes or max_pixels:
-            self._pinned(self.batch * (_up(int(max_file_bytes), 16) + 4096))
-            self._buffer("blob", self.batch * (_up(int(max_file_bytes), 16) + 4096))
-            self._buffer("out", self.batch * _up(3 * int(max_pixels) + self.guard, 256))
-            self._buffer("scratch", self.batch * (_up(int(max_file_bytes), 16) + _up(3 * int(max_pixels) + MAX_SIDE, 16)) + 4096)
-
-    def _pinned(self, nbytes):
-        if self._pin is None or self._pin.numel() < nbytes:
-            self._pin = torch.empty(_up(nbytes, 4096), dtype=torch.uint8).pin_memory()
-        return self._pin
-
-    def _buffer(self, name, nbytes):
-        """The inner `nbytes` (at least) of a device buffer with `guard` bytes on either side."""
-        g, t = self.guard, self._dev.get(name)
-        if t is None or t.numel() < nbytes + 2 * g:
-            t = torch.full((_up(nbytes, 4096) + 2 * g,), self.GUARD_BYTE, dtype=torch.uint8, device=self.device)
-            self._dev[name] = t
-        return t[g:t.numel() - g]
-
-    def _intact(self, t):
-        return bool((t == self.GUARD_BYTE).all())
-
-    def check_guards(self):
-        """True when every guard byte still holds GUARD_BYTE: around the buffers, between and behind the output slots of the last read(),
-        and -- looked at after every batch of that read() -- behind the status words and the scratch bytes the batch used."""
-        g = self.guard
-        ok = self._slack_ok
-        for name, t in self._dev.items():
-            if g:
-                ok = ok and bool((t[:g] == self.GUARD_BYTE).all()) and bool((t[t.numel() - g:] == self.GUARD_BYTE).all())
-        for lo, hi in self._gaps:
-            ok = ok and bool((self._dev["out"][lo:hi] == self.GUARD_BYTE).all())
-        return ok
-
-    def read(self, files):
-        """files: a list of bytes or paths -> a list of device uint8 [h, w, C] tensors, views into the reader's output buffer, valid until the
-        next call.  ValueError for a file parse() refuses, and for a file the device refuses: it names the file's index (and path) and says
-        what the status word says."""
-        return self.decode(*self.load(files))
+        self.last_route, self.last_route_ptr = [], None                 # with segments=True: the route word per file (else zeros)
+        super().__init__(device, batch, max_file_bytes, max_pixels, guard)
 
     @staticmethod
-    def load(files):
-        """The host's share of read(): files (bytes or paths) -> (blobs, names, parsed), parsed[i] = parse(blob) + (len(blob),).  No device
-        work; ValueError for a file parse() refuses."""
-        blobs, names = [], []
-        for i, f in enumerate(files):
-            if isinstance(f, (bytes, bytearray, memoryview)):
-                blobs.append(f)
-                names.append(f"file {i}")
-            else:
-                with open(f, "rb") as fh:
-                    blobs.append(fh.read())
-                names.append(f"file {i} ({f})")
-        parsed = []
-        for name, b in zip(names, blobs):
-            try:
-                parsed.append(parse(b) + (len(b),))
-            except ValueError as e:
-                raise ValueError(f"{name}: {e}") from None
-        return blobs, names, parsed
+    def _parse_one(blob):
+        return parse(blob) + (len(blob),)
 
-    def decode(self, blobs, names, parsed):
-        """The device's share of read(), from what load() returned."""
-        self._slack_ok, self._gaps = True, []
-        if not parsed:
-            return []
-        whole = plan(parsed, self.guard)
-        out = self._buffer("out", whole["out_bytes"])
-        g0 = self.guard
-        if g0:
-            out.fill_(self.GUARD_BYTE)
-            self._gaps.append((g0 + whole["out_bytes"], g0 + out.numel()))      # behind the last slot, up to the end of the allocation
-        results, failures = [], []
-        lib = _lib.load()
-        for lo in range(0, len(parsed), self.batch):
-            part = parsed[lo:lo + self.batch]
-            p = plan(part, self.guard)
-            n, n_idat = len(part), len(p["idat"])
-            t_desc, t_idat = _up(n * _FILE.itemsize, 256), _up(n_idat * _IDAT.itemsize, 256)
-            up_bytes = t_desc + t_idat + p["files_bytes"]
-            pin = self._pinned(up_bytes)
-            host = pin.numpy()
-            host[:n * _FILE.itemsize] = p["desc"].view(np.uint8).reshape(-1)
-            host[t_desc:t_desc + n_idat * _IDAT.itemsize] = p["idat"].view(np.uint8).reshape(-1)
-            for d, b in zip(p["desc"], blobs[lo:lo + n]):
-                at = t_desc + t_idat + int(d["file_offset"])
-                host[at:at + len(b)] = np.frombuffer(b, dtype=np.uint8)
-            blob = self._buffer("blob", up_bytes)
-            blob[:up_bytes].copy_(pin[:up_bytes], non_blocking=True)
-            routed = bool(self.flags & SEGMENTS)
-            need = int(lib.egs_png_decode_scratch_bytes_ex(n_idat, p["stream_bytes"], p["inflate_bytes"], self.flags) if self.flags else
-                       lib.egs_png_decode_scratch_bytes(n_idat, p["stream_bytes"], p["inflate_bytes"]))
-            scratch = self._buffer("scratch", need)
-            status = self._buffer("status", 8 * self.batch)             # the status words, then (segments) the route words: one read
-            words_bytes = 8 * n if routed else 4 * n
-            base = int(whole["desc"]["out_offset"][lo])                  # this batch's slots inside the call's output buffer
-            self.last_call = (n, blob.data_ptr() + t_desc + t_idat, p["files_bytes"], pin.data_ptr(), blob.data_ptr(), pin.data_ptr() + t_desc,
-                              blob.data_ptr() + t_desc, n_idat, out.data_ptr() + base, p["out_bytes"], status.data_ptr(), scratch.data_ptr(), need)
-            self.last_route_ptr = status.data_ptr() + 4 * n if routed else None
-            if g0:                                                      # everything behind the bytes in use holds the guard byte
-                status[words_bytes:].fill_(self.GUARD_BYTE)
-                scratch[need:].fill_(self.GUARD_BYTE)
-            with _hip.device_ctx(self.device):
-                if self.flags:
-                    _lib.check(lib.egs_png_decode_ex(*self.last_call, _hip.stream_of(self.device), 7, self.flags,
-                                                     status.data_ptr() + 4 * n if routed else None))
-                else:
-                    _lib.check(lib.egs_png_decode(*self.last_call, _hip.stream_of(self.device)))
-            words = status[:words_bytes].view(torch.int32).cpu().tolist()      # (synchronises: the staging may be refilled)
-            words, routes = words[:n], [r & 0xFFFFFFFF for r in words[n:]] if routed else [0] * n
-            self.host_reads += 1
-            if g0:
-                self._slack_ok = self._slack_ok and self._intact(status[words_bytes:]) and self._intact(scratch[need:])
-            for k, (d, w) in enumerate(zip(p["desc"], words)):
-                W, H, C = int(d["width"]), int(d["height"]), int(d["channels"])
-                o = base + int(d["out_offset"])
-                results.append(out[o:o + H * W * C].view(H, W, C))
-                if self.guard:
-                    self._gaps.append((g0 + o + H * W * C, g0 + o + _up(H * W * C + self.guard, 256)))
-                if w:
-                    failures.append(f"{names[lo + k]}: {status_text(w & 0xFFFFFFFF)} (status {w & 0xFFFFFFFF})")
-            self.last_status = (self.last_status if lo else []) + [w & 0xFFFFFFFF for w in words]
-            self.last_route = (self.last_route if lo else []) + routes
-        self.last_results = results
-        if failures:
-            raise ValueError("PngReader.read: " + "; ".join(failures))
-        return results
+    @staticmethod
+    def _shape(entry):
+        return entry[:3]
+
+    _plan = staticmethod(plan)
+
+    def _second_table(self, p):
+        return p["idat"], len(p["idat"])
+
+    def _scratch_need(self, lib, n, p):
+        n_idat = len(p["idat"])
+        return int(lib.egs_png_decode_scratch_bytes_ex(n_idat, p["stream_bytes"], p["inflate_bytes"], self.flags) if self.flags else
+                   lib.egs_png_decode_scratch_bytes(n_idat, p["stream_bytes"], p["inflate_bytes"]))
+
+    def _reserve_scratch(self, max_file_bytes, max_pixels):
+        return self.batch * (_up(max_file_bytes, 16) + _up(3 * max_pixels + MAX_SIDE, 16)) + 4096
+
+    def _status_allocation(self):
+        return 8 * self.batch                                           # the status words, then (segments) the route words: one read
+
+    def _status_bytes(self, n):
+        return 8 * n if self.flags & SEGMENTS else 4 * n
+
+    def _launch(self, lib, call, n, status):
+        self.last_route_ptr = status.data_ptr() + 4 * n if self.flags & SEGMENTS else None
+        if self.flags:
+            _lib.check(lib.egs_png_decode_ex(*call, _hip.stream_of(self.device), 7, self.flags, self.last_route_ptr))
+        else:
+            _lib.check(lib.egs_png_decode(*call, _hip.stream_of(self.device)))
+
+    def _after_words(self, words, lo, n):
+        routes = [r & 0xFFFFFFFF for r in words[n:]] if self.flags & SEGMENTS else [0] * n
+        self.last_route = (self.last_route if lo else []) + routes
+        return words[:n]
 
 
 def decode_device(file_bytes, device="cuda", segments=False):
